@@ -17,15 +17,22 @@ The timed region: W warm-up steps, a checkpoint of the time loop on the device
 (fedm_state_snapshot), >= 0.3 s of real stepping from it (clocks up, graphs captured), then the
 window of EXACTLY K steps between two barriers R times, each from the checkpoint (the restore is
 untimed).  ``ms_per_step`` is the MEDIAN window; the first window, the spread and the per-step
-spans of the median window are in ``windows``.
+spans of the median window are in ``windows``.  The repeats stop at 3 s of windows (an odd number of
+them); a first window of 3 s or more is timed once, without pre-roll.
 
-Records in the line, besides the driver's contract:
+A plain run does only that: set-up, warm-up, the timed windows, the headline line.
+``--dump-outputs DIR`` then writes what the last timed step computed (the state a caller of the time
+loop receives) as DIR/*.npy; the inputs depend on the arguments only, so two builds can be compared
+output for output.  Everything else below is measured with ``--full`` only.
+
+Records in the line with ``--full``, besides the driver's contract (each on min(K, 20) steps after min(W, 20)
+warm-up steps, whatever K the headline is given):
 * ``roofline`` / ``roofline_other`` / ``assembly_plus_spmv``: HIP-event timings of the hot kernels
   against the 8 TB/s HBM3E peak (and against the copy rate measured on this box);
-* ``late_window``: the same K steps timed again from the developed streamer (step 200, t ~ 1 ns),
+* ``late_window``: the steps timed again from the developed streamer (step 200, t ~ 1 ns),
   where a step needs several times the Krylov iterations of the first steps;
 * ``multi_gpu`` (N > 1): transport, ranks, halo exchanges / all-reduces per step and their latency;
-* ``tensor_mesh`` (N = 1): the same K steps on the 576x576 graded tensor-product mesh (998 787 DOFs: the
+* ``tensor_mesh`` (N = 1): the steps on the 576x576 graded tensor-product mesh (998 787 DOFs: the
   headline of rounds 1-3) with its own roofline blocks;
 * ``roofline_beyond_infinity_cache`` (N = 1): assembly and SpMV fractions on the 1152x1152 mesh (4 M
   DOFs, Jacobian 670 MB > the 256 MiB Infinity Cache): rates that cannot come from the last-level cache;
@@ -87,7 +94,7 @@ def parse_args():
     ap.add_argument("--grading", type=float, default=4.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-mesh", type=int, default=None, help="CPU baseline mesh (default: --mesh)")
-    ap.add_argument("--cpu-steps", type=int, default=0, help="0: as many as --steps")
+    ap.add_argument("--cpu-steps", type=int, default=0, help="0: as many as the other --full records (min(--steps, 20))")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every core this process may use")
     ap.add_argument("--late-start", type=int, default=200,
                     help="accepted steps before the late window (0 disables it)")
@@ -108,6 +115,12 @@ def parse_args():
     # rehearsal of the N > 1 path on a one-GPU box: all ranks on cuda:0, gloo process group (RCCL
     # refuses two ranks on one device, so the library falls back to its host-staged transport)
     ap.add_argument("--rehearse-on-one-gpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also every record beside the headline: rooflines and kernel timings, the late window, the "
+                         "other mesh family, the 4 M-DOF mesh, the glow discharge, the multi-GPU figures and configs[4], "
+                         "the CPU baseline (the options above that select them act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step as DIR/<name>.npy (float64)")
     return ap.parse_args()
 
 
@@ -224,10 +237,12 @@ def pin_to_gpu_numa_node(torch, local_rank):
         return f"unchanged ({type(exc).__name__})"
 
 
-def timed_steps(runner, steps, barrier, torch, dist, distributed):
+def timed_steps(runner, steps, barrier, torch, dist, distributed, events=True):
     """K steps between two barriers; wall time is the MAX over ranks.  Returns (seconds, Newton
-    iterations, GMRES iterations, assembly profile, per-step spans in ms on this rank)."""
-    runner.profile(1)             # HIP events around the assembly kernels, on the library's stream
+    iterations, GMRES iterations, assembly profile (None without `events`), per-step spans in ms on
+    this rank)."""
+    if events:
+        runner.profile(1)         # HIP events around the assembly kernels, on the library's stream
     barrier()
     t0 = time.perf_counter()
     n0 = (runner.newton_iterations, runner.linear_iterations)
@@ -238,8 +253,10 @@ def timed_steps(runner, steps, barrier, torch, dist, distributed):
     barrier()
     elapsed = time.perf_counter() - t0
     n1 = (runner.newton_iterations, runner.linear_iterations)
-    prof = runner.profile_read()
-    runner.profile(False)
+    prof = None
+    if events:
+        prof = runner.profile_read()
+        runner.profile(False)
     if distributed:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -248,49 +265,94 @@ def timed_steps(runner, steps, barrier, torch, dist, distributed):
     return elapsed, n1[0] - n0[0], n1[1] - n0[1], prof, spans
 
 
-def timed_windows(runner, steps, repeats, preroll_s, barrier, torch, dist, distributed):
+WINDOW_BUDGET_S = 3.0
+# steps (and at most as many warm-up steps) of every --full record beside the headline: --full stays a matter of
+# minutes whatever --steps the headline is given
+RECORD_STEPS = 20
+
+
+def timed_windows(runner, steps, repeats, preroll_s, barrier, torch, dist, distributed, events=True):
     """The contract's window -- EXACTLY `steps` steps between two barriers -- `repeats` times from ONE
     checkpoint of the time loop (device-side copy of the three states + the script's scalars; the restore
-    is outside the timed region), after `preroll_s` seconds of untimed stepping from the same checkpoint
+    is outside the timed region), after `preroll_s` seconds of stepping from the same checkpoint
     (clock ramp, graph capture, first-touch effects: the first 31-ms window of round 3's driver run was 20 %
-    slower than the same window on a warm chip).  Returns the MEDIAN window's record plus the spread; the
-    runner is left at the end of the last window."""
+    slower than the same window on a warm chip).  The repeats stop at WINDOW_BUDGET_S seconds of windows
+    (an odd number of them); a first window that long is measured once, without pre-roll.  `events`: HIP
+    events around the assembly kernels in every window (the roofline records read them).  Returns the
+    MEDIAN window's record plus the spread; the runner is left at the end of the last window."""
     snap = runner.snapshot()
-    # pre-roll: whole windows, their number agreed between the ranks; with the in-run kernel timing on, as in the
-    # timed windows (its first use is not free: event pool, the queue's profiling mode)
-    runner.profile(1)
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        runner.step()
-    first = time.perf_counter() - t0
-    extra = int(min(20, max(0, np.ceil(preroll_s / max(first, 1e-4)) - 1)))
-    if distributed:
-        e = torch.tensor([float(extra)], dtype=torch.float64, device="cuda")
-        dist.all_reduce(e, op=dist.ReduceOp.MAX)
-        extra = int(e.item())
-    for _ in range(extra):
-        runner.restore(snap)
-        for _ in range(steps):
-            runner.step()
-    runner.profile_read()
-    runner.profile(False)
-    windows = []
-    prof_sum = None
-    for r in range(max(1, repeats)):
-        runner.restore(snap)
-        el, nw, gm, prof, spans = timed_steps(runner, steps, barrier, torch, dist, distributed)
-        windows.append(dict(elapsed=el, newton=nw, gmres=gm, spans=spans))
-        prof_sum = prof if prof_sum is None else {k: (prof_sum[k][0] + v[0], prof_sum[k][1] + v[1]) for k, v in prof.items()}
+    # the first window, timed like the others (its time, the max over the ranks, is the same number on every
+    # rank, and so is everything decided from it); with the in-run kernel timing on, as in the timed windows
+    # (its first use is not free: event pool, the queue's profiling mode)
+    first, nw, gm, prof, spans = timed_steps(runner, steps, barrier, torch, dist, distributed, events)
+    if first >= WINDOW_BUDGET_S:
+        # clock ramp and graph capture are a small part of a window this long, and a pre-roll or a second
+        # window would cost as much again
+        extra, windows, prof_sum = -1, [dict(elapsed=first, newton=nw, gmres=gm, spans=spans)], prof
+    else:
+        # pre-roll: the first window and further whole ones
+        extra = int(min(20, max(0, np.ceil(preroll_s / max(first, 1e-4)) - 1)))
+        if events:
+            runner.profile(1)
+        for _ in range(extra):
+            runner.restore(snap)
+            for _ in range(steps):
+                runner.step()
+        if events:
+            runner.profile_read()
+            runner.profile(False)
+        fit = max(1, int(WINDOW_BUDGET_S / first))
+        fit -= 1 - fit % 2
+        windows = []
+        prof_sum = None
+        for r in range(min(max(1, repeats), fit)):
+            runner.restore(snap)
+            el, nw, gm, prof, spans = timed_steps(runner, steps, barrier, torch, dist, distributed, events)
+            windows.append(dict(elapsed=el, newton=nw, gmres=gm, spans=spans))
+            if events:
+                prof_sum = prof if prof_sum is None else {k: (prof_sum[k][0] + v[0], prof_sum[k][1] + v[1])
+                                                          for k, v in prof.items()}
     order = sorted(range(len(windows)), key=lambda i: windows[i]["elapsed"])
     med = windows[order[len(order) // 2]]
     ms = [1e3 * w["elapsed"] / steps for w in windows]
     record = {"repeats": len(windows), "window_ms_per_step": ms, "window_ms_min": min(ms), "window_ms_max": max(ms),
               "window_spread": (max(ms) - min(ms)) / min(ms), "first_window_ms_per_step": ms[0],
+              "cold_window_ms_per_step": 1e3 * first / steps,
               "median_window_step_spans_ms": med["spans"], "preroll_windows": 1 + extra,
-              "preroll": f"{1 + extra} untimed windows of {steps} steps from the checkpoint before the first timed one",
+              "preroll": f"{1 + extra} windows of {steps} steps from the checkpoint before the first counted one "
+                         "(the first of them: 'cold_window_ms_per_step')",
               "how": "every window restarts from the same device-side checkpoint taken after the warm-up steps "
                      "(fedm_state_snapshot / fedm_state_restore, untimed); ms_per_step and value are the median window's"}
     return med["elapsed"], med["newton"], med["gmres"], prof_sum, len(windows), record
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(directory, runner, dist, distributed, rank):
+    """What the timed path hands its caller after its last step, as DIR/<name>.npy (float64):
+    ``state`` (vertices x [ion log-density, electron log-density, potential], global vertex order),
+    ``time`` (t) and ``time_step`` (the step size the controller chose next).  Across ranks the owned rows
+    are gathered on rank 0.  A state over the size limit is written as a fixed sample of its rows (seed 0,
+    ascending): ``state`` then holds those rows and ``state_rows`` their vertex numbers."""
+    U = runner.prob.get_state()
+    if distributed:
+        lm = runner.lm
+        parts = [None] * runner.world_size
+        dist.all_gather_object(parts, (lm.vertex_global[:lm.n_owned], U[:lm.n_owned]))
+        U = np.empty((sum(len(v) for v, _ in parts), U.shape[1]))
+        for v, rows in parts:
+            U[v] = rows
+    if rank != 0:
+        return
+    out = {"state": U, "time": np.array([runner.t]), "time_step": np.array([runner.dt.time_step])}
+    if U.nbytes > DUMP_LIMIT_BYTES - 1024:
+        n = (DUMP_LIMIT_BYTES - 1024) // (U.shape[1] * 8 + 8)
+        rows = np.sort(np.random.default_rng(0).choice(U.shape[0], size=n, replace=False))
+        out["state"], out["state_rows"] = U[rows], rows.astype(np.float64)
+    Path(directory).mkdir(parents=True, exist_ok=True)
+    for name, a in out.items():
+        np.save(Path(directory) / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
 
 
 def main():
@@ -372,18 +434,23 @@ def main():
         msh = streamer.mesh(n_per_gpu, args.grading)
         return streamer.Stepper(streamer.device_problem(msh.coords, msh.cells, device=local_rank)), msh, 0.0
 
-    copy_gbs = measured_copy_ceiling(local_rank) if rank == 0 else None
+    copy_gbs = measured_copy_ceiling(local_rank) if rank == 0 and args.full else None
 
-    def hot_path(runner, steps, warmup, tr, tr_source, repeats):
-        """W warm-up steps, the window of K timed steps `repeats` times from one checkpoint (HIP events around
-        the assembly kernels, on the library's stream), then a second, untimed pass with plain launches for the
-        kernels inside the Krylov iterations (events cannot sit inside the replayed per-iteration graphs).
-        Returns the record pieces."""
+    def hot_path(runner, steps, warmup, tr, tr_source, repeats, dump=None):
+        """W warm-up steps, the window of K timed steps `repeats` times from one checkpoint (with --full: HIP
+        events around the assembly kernels, on the library's stream), the outputs of the last timed step into
+        `dump`, then -- with --full -- a second, untimed pass with plain launches for the kernels inside the
+        Krylov iterations (events cannot sit inside the replayed per-iteration graphs).  Returns the record
+        pieces."""
         for _ in range(warmup):
             runner.step()
-        before = runner.prob.comm_stats() if distributed else None
+        before = runner.prob.comm_stats() if distributed and args.full else None
         elapsed, newton, gmres, prof, n_win, windows = timed_windows(runner, steps, repeats, args.preroll, barrier,
-                                                                    torch, dist, distributed)
+                                                                    torch, dist, distributed, events=args.full)
+        if dump:
+            dump_outputs(dump, runner, dist, distributed, rank)
+        if not args.full:
+            return dict(elapsed=elapsed, newton=newton, gmres=gmres, windows=windows)
         prof_steps = steps * n_win           # the assembly events cover every timed window
         comm0 = runner.prob.comm_stats() if distributed else None
         if distributed:      # what travelled inside ONE timed window (set-up, warm-up and pre-roll apart)
@@ -519,6 +586,7 @@ def main():
         return f"{n}x{n} right-diagonal tensor-product mesh, geometric grading {args.grading} towards the axis"
 
     # ---- the headline: K steps right after the warm-up (SURVEY 8(d)'s window) -----------------------
+    ks, kw = min(args.steps, RECORD_STEPS), min(args.warmup, RECORD_STEPS)      # the --full records beside it
     family = args.family
     n = args.mesh
     spacing = args.mesh_spacing / np.sqrt(world)          # weak scaling: N times the vertices
@@ -527,10 +595,10 @@ def main():
     runner.initialise()
     setup_s = time.perf_counter() - t_setup - t_mesh
     profiled = world == 1 and ((family == "unstructured" and args.mesh_spacing == 4e-6) or (family == "tensor" and n == 576))
-    tr, tr_source = pmc_traffic(family) if profiled else ({}, "not a profiled workload")
-    hp = hot_path(runner, args.steps, args.warmup, tr, tr_source, args.repeats)
-    elapsed, newton, gmres, sz, comm0 = hp["elapsed"], hp["newton"], hp["gmres"], hp["sz"], hp["comm0"]
-    rl_asm, rl_spmv = hp["rl_asm"], hp["rl_spmv"]
+    tr, tr_source = pmc_traffic(family) if profiled and args.full else ({}, "not a profiled workload")
+    hp = hot_path(runner, args.steps, args.warmup, tr, tr_source, args.repeats, dump=args.dump_outputs)
+    elapsed, newton, gmres = hp["elapsed"], hp["newton"], hp["gmres"]
+    sz = runner.sizes()
     total_dofs = runner.total_dofs
 
     gmres_text = ("flexible, restart 30, rtol 1e-5 on the true residual, right-preconditioned: field split, "
@@ -566,27 +634,31 @@ def main():
                    "pattern": pattern_of(sz),
                    "mesh_seconds": t_mesh, "setup_seconds": setup_s},
         "window": f"steps {args.warmup + 1}..{args.warmup + args.steps} from the initial condition "
-                  "(SURVEY 8(d)), repeated from a checkpoint: 'windows'; the developed streamer is 'late_window'",
+                  "(SURVEY 8(d)), repeated from a checkpoint: 'windows'; the developed streamer is 'late_window' (--full)",
         "windows": hp["windows"],
         "newton_iterations_per_step": newton / args.steps,
         "gmres_iterations_per_step": gmres / args.steps,
-        "roofline": rl_asm,
-        "roofline_other": rl_spmv,
-        "assembly_plus_spmv": hp["path"],
-        "vcycle": hp["vcycle"],
-        "measured_copy_ceiling_GBs": copy_gbs,
-        "copy_ceiling_how": "fedm_copy_bandwidth: the fastest of six 16-byte-per-lane copy kernels (1-8 loads in flight per "
-                            "lane, plain / non-temporal), 2 x 1 GiB, HIP events",
-        "run_to_reference_end_time": ("profiles/r04_refined_run_4um_1M_dofs.json: this mesh carries the streamer to the reference's "
-                                      "T_final = 1.4e-8 s (2801 accepted steps, none rejected)") if family == "unstructured" else None,
     }
-    if args.late_start > 0:
-        out["late_window"] = late_window(runner, hp, args.steps)
+    if args.full:
+        out.update({
+            "roofline": hp["rl_asm"],
+            "roofline_other": hp["rl_spmv"],
+            "assembly_plus_spmv": hp["path"],
+            "vcycle": hp["vcycle"],
+            "measured_copy_ceiling_GBs": copy_gbs,
+            "copy_ceiling_how": "fedm_copy_bandwidth: the fastest of six 16-byte-per-lane copy kernels (1-8 loads in flight "
+                                "per lane, plain / non-temporal), 2 x 1 GiB, HIP events",
+            "run_to_reference_end_time": ("profiles/r04_refined_run_4um_1M_dofs.json: this mesh carries the streamer to the "
+                                          "reference's T_final = 1.4e-8 s (2801 accepted steps, none rejected)")
+                                         if family == "unstructured" else None,
+        })
+    if args.full and args.late_start > 0:
+        out["late_window"] = late_window(runner, hp, ks)
         out["sustained_timesteps_per_sec"] = out["late_window"]["timesteps_per_sec"]
 
     # ---- multi-GPU plumbing: what travelled, and what one exchange / reduction costs ------------
-    if distributed:
-        cs = comm0
+    if distributed and args.full:
+        cs = hp["comm0"]
         lat = {}
         for name, kind in (("halo_state_us", 0), ("halo_scalar_us", 1), ("allreduce_32_doubles_us", 2)):
             barrier()
@@ -613,7 +685,7 @@ def main():
                     "run the exchanges overlap interior SpMV rows / sweeps / assembly patches"}
 
     # ---- the same K steps on the other mesh family (one GPU) ---------------------------------------
-    if world == 1 and args.second_mesh != "off":
+    if args.full and world == 1 and args.second_mesh != "off":
         other = "tensor" if family == "unstructured" else "unstructured"
         del runner
         t_o = time.perf_counter()
@@ -622,24 +694,24 @@ def main():
         o_setup = time.perf_counter() - t_o - o_tmesh
         o_prof = (other == "unstructured" and args.mesh_spacing == 4e-6) or (other == "tensor" and n == 576)
         otr, otr_source = pmc_traffic(other) if o_prof else ({}, "not a profiled workload")
-        oh = hot_path(orun, args.steps, args.warmup, otr, otr_source, min(args.repeats, 3))
+        oh = hot_path(orun, ks, kw, otr, otr_source, min(args.repeats, 3))
         osz = oh["sz"]
         rec = {"workload": "the same streamer case on the " + mesh_text(other, n, args.mesh_spacing),
                "vertices": osz["n_vertices"], "cells": osz["n_cells"], "dofs_total": orun.total_dofs,
-               "value": orun.total_dofs * args.steps / oh["elapsed"], "unit": "DOF-updates/s",
-               "timesteps_per_sec": args.steps / oh["elapsed"], "ms_per_step": 1e3 * oh["elapsed"] / args.steps,
+               "value": orun.total_dofs * ks / oh["elapsed"], "unit": "DOF-updates/s",
+               "timesteps_per_sec": ks / oh["elapsed"], "ms_per_step": 1e3 * oh["elapsed"] / ks,
                "windows": oh["windows"],
-               "newton_iterations_per_step": oh["newton"] / args.steps,
-               "gmres_iterations_per_step": oh["gmres"] / args.steps,
+               "newton_iterations_per_step": oh["newton"] / ks,
+               "gmres_iterations_per_step": oh["gmres"] / ks,
                "roofline": oh["rl_asm"], "roofline_other": oh["rl_spmv"], "assembly_plus_spmv": oh["path"],
                "vcycle": oh["vcycle"], "pattern": pattern_of(osz), "mesh_seconds": o_tmesh, "setup_seconds": o_setup}
         if args.late_start > 0:
-            rec["late_window"] = late_window(orun, oh, args.steps)
+            rec["late_window"] = late_window(orun, oh, ks)
         out["tensor_mesh" if other == "tensor" else "unstructured"] = rec
         runner = orun
 
     # ---- rates that cannot come from the Infinity Cache: the 4 M-DOF mesh on ONE GPU ------------------
-    if world == 1 and args.big_mesh > 0:
+    if args.full and world == 1 and args.big_mesh > 0:
         del runner
         t_b = time.perf_counter()
         bmesh = streamer.mesh(args.big_mesh, args.grading)
@@ -662,7 +734,7 @@ def main():
         runner = brun
 
     # ---- BASELINE configs[2]: glow discharge (LMEA), 141 x 141 crossed = 200 225 DOFs ------------------
-    if world == 1 and not args.no_glow_discharge:
+    if args.full and world == 1 and not args.no_glow_discharge:
         import contextlib
         import io
         from fedm_amd.cases import glow_discharge as gdc
@@ -709,36 +781,36 @@ def main():
 
     # ---- BASELINE configs[4]: ~4 M DOFs over 8 GPUs (strong-scaled counterpart of the line above) ----
     want4 = args.configs4 == "on" or (args.configs4 == "auto" and world == 8)
-    if want4 and distributed:
+    if args.full and want4 and distributed:
         del runner
         r4, _, _ = make_runner("tensor", global_n=args.configs4_mesh)
         r4.initialise()
-        for _ in range(args.warmup):
+        for _ in range(kw):
             r4.step()
         b4 = r4.prob.comm_stats()
-        e4, nw4, gm4, _, _ = timed_steps(r4, args.steps, barrier, torch, dist, distributed)
+        e4, nw4, gm4, _, _ = timed_steps(r4, ks, barrier, torch, dist, distributed)
         a4 = r4.prob.comm_stats()
         out["configs4"] = {
             "workload": f"BASELINE configs[4]: streamer_discharge, {args.configs4_mesh}x{args.configs4_mesh} "
                         f"global mesh over {world} GPUs",
-            "dofs_total": r4.total_dofs, "value": r4.total_dofs * args.steps / e4, "unit": "DOF-updates/s",
-            "timesteps_per_sec": args.steps / e4, "ms_per_step": 1e3 * e4 / args.steps,
-            "newton_iterations_per_step": nw4 / args.steps, "gmres_iterations_per_step": gm4 / args.steps,
-            "halo_exchanges_per_step": (a4["halo_exchanges"] - b4["halo_exchanges"]) / args.steps,
-            "allreduces_per_step": (a4["allreduces"] - b4["allreduces"]) / args.steps,
-            "halo_bytes_per_step": (a4.get("halo_bytes", 0) - b4.get("halo_bytes", 0)) / args.steps,
-            "allreduce_bytes_per_step": (a4.get("allreduce_bytes", 0) - b4.get("allreduce_bytes", 0)) / args.steps,
+            "dofs_total": r4.total_dofs, "value": r4.total_dofs * ks / e4, "unit": "DOF-updates/s",
+            "timesteps_per_sec": ks / e4, "ms_per_step": 1e3 * e4 / ks,
+            "newton_iterations_per_step": nw4 / ks, "gmres_iterations_per_step": gm4 / ks,
+            "halo_exchanges_per_step": (a4["halo_exchanges"] - b4["halo_exchanges"]) / ks,
+            "allreduces_per_step": (a4["allreduces"] - b4["allreduces"]) / ks,
+            "halo_bytes_per_step": (a4.get("halo_bytes", 0) - b4.get("halo_bytes", 0)) / ks,
+            "allreduce_bytes_per_step": (a4.get("allreduce_bytes", 0) - b4.get("allreduce_bytes", 0)) / ks,
             "partition": r4.partition_name}
         runner = r4
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:    # (a reported baseline: its failure must not take the measured record with it)
             label = mesh_text(family, n, spacing)
             cmesh = hmesh if hmesh is not None else streamer.mesh(args.cpu_mesh or n, args.grading)
-            out["cpu_baseline"] = cpu_baseline(cmesh, args.cpu_steps or args.steps, args.cpu_threads, label)
+            out["cpu_baseline"] = cpu_baseline(cmesh, args.cpu_steps or ks, args.cpu_threads, label)
         except Exception as exc:                          # noqa: BLE001 - reported in the record
             out["cpu_baseline"] = {"error": f"{type(exc).__name__}: {exc}"}
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(out))

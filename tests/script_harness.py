@@ -3,10 +3,11 @@ device, and condenses what the script handed over into numbers (test infrastruct
 
 Two kinds of script go through it:
 
-* our own drivers under ``examples/`` (everywhere), and
-* the reference's scripts ``examples/*/fedm-*.py`` READ FROM /root/reference AT TEST TIME (build
-  container only; nothing of their text is stored in this repo): the three ``from fedm... import *``
-  lines and ``from dolfin import *`` are pointed at ``fedm_amd``, everything else runs as written.
+* our own drivers under ``examples/`` (the tests), and
+* the reference's scripts ``examples/*/fedm-*.py``, read from the reference checkout by the fixture generator
+  tests/golden/make_script_records.py only (nothing of their text is stored in this repo): the three
+  ``from fedm... import *`` lines and ``from dolfin import *`` are pointed at ``fedm_amd``, everything else
+  runs as written.  The tests read what that run recorded from tests/golden/.
 
 What is recorded is everything `fedm.functions.Problem` + the first `PETScSNESSolver.solve` would
 upload to the GPU: the bytes of ``fedm_model_desc`` / ``fedm_gd_desc``, mesh, facet tags, Dirichlet
@@ -176,11 +177,132 @@ def run_reference_script(case, workdir):
                        env=env, cwd=str(workdir), capture_output=True, text=True, timeout=900)
     if r.returncode != 0:
         raise AssertionError(f"the reference's {SCRIPTS[case]} failed on the facade:\n{r.stderr[-3000:]}")
-    with np.load(out, allow_pickle=False) as z:
+    return load_record(out)
+
+
+def save_record(path, record):
+    """A record as an .npz without pickles: strings under s_<key>, arrays under a_<key>."""
+    np.savez(path, **{("s_" if isinstance(v, str) else "a_") + k: (np.array(v) if isinstance(v, str) else np.asarray(v))
+                      for k, v in record.items()})
+
+
+def load_record(path):
+    """The record save_record wrote."""
+    with np.load(path, allow_pickle=False) as z:
+        return {k[2:]: str(z[k]) if k.startswith("s_") else z[k] for k in z.files}
+
+
+# Arrays of a record that are compared exactly (bytes and indices); integer arrays are compared exactly anyway.
+EXACT = ("descriptor", "cells", "facet_tags", "dirichlet_dofs", "source_program_ops")
+
+
+class Exact:
+    """An array kept as the SHA-256 of its shape and values (uint8 for the descriptor, int64 otherwise): equal
+    digests <=> equal arrays, which is all an exact comparison asks."""
+
+    def __init__(self, key, hexdigest):
+        self.key, self.hexdigest = key, hexdigest
+
+    @staticmethod
+    def of(key, a):
+        a = np.asarray(a)
+        c = np.array(a, dtype="<u1" if key == "descriptor" else "<i8", order="C")
+        if not np.array_equal(a, c):
+            return None                 # values that are not integers: no exact match with an integer array
+        import hashlib
+        return hashlib.sha256(repr(tuple(c.shape)).encode() + c.tobytes()).hexdigest()
+
+    def matches(self, a):
+        return Exact.of(self.key, a) == self.hexdigest
+
+
+def _pack_floats(a):
+    """float64 array -> lossless bytes: per column the XOR of each value's bits with the previous value's, the
+    eight byte planes one after the other, xz (smooth fields and mesh coordinates share their leading bits)."""
+    import lzma
+    cols = np.ascontiguousarray(np.asarray(a, dtype="<f8").reshape(a.shape[0] if a.ndim else 1, -1).T)
+    bits = cols.view("<u8")
+    delta = bits.copy()
+    delta[:, 1:] ^= bits[:, :-1]
+    planes = delta.view(np.uint8).reshape(-1, 8).T.tobytes()
+    return np.frombuffer(lzma.compress(planes, preset=9 | lzma.PRESET_EXTREME), dtype=np.uint8)
+
+
+def _unpack_floats(blob, shape):
+    import lzma
+    shape = tuple(int(s) for s in shape)
+    rows = shape[0] if shape else 1
+    planes = np.frombuffer(lzma.decompress(blob.tobytes()), dtype=np.uint8)
+    delta = np.ascontiguousarray(planes.reshape(8, -1).T).view("<u8").reshape(-1, rows)
+    bits = np.bitwise_xor.accumulate(delta, axis=1)
+    return np.ascontiguousarray(bits.view("<f8").T).reshape(shape)
+
+
+def save_records(path, records):
+    """Several records in one small .npz without pickles, under <case>/: strings (s_), arrays compared exactly as
+    their Exact digest (h_), an array equal to an earlier one of its record as that one's name (d_), float arrays
+    packed losslessly (f_, shape under n_)."""
+    out = {}
+    for case, record in records.items():
+        seen = {}
+        for k, v in record.items():
+            p = f"{case}/"
+            if isinstance(v, str):
+                out[p + "s_" + k] = np.array(v)
+                continue
+            v = np.asarray(v)
+            same = next((name for name, w in seen.items() if w.shape == v.shape and np.array_equal(w, v)), None)
+            if k in EXACT or v.dtype.kind in "iub" or v.size == 0:
+                digest = Exact.of(k, v)
+                assert digest is not None, f"{k}: not an integer array"
+                out[p + "h_" + k] = np.array(digest)
+            elif same is not None:
+                out[p + "d_" + k] = np.array(same)
+            else:
+                out[p + "f_" + k], out[p + "n_" + k] = _pack_floats(v), np.array(v.shape, dtype=np.int64)
+                assert np.array_equal(_unpack_floats(out[p + "f_" + k], v.shape), v), k
+                seen[k] = v
+    np.savez(path, **out)
+
+
+def load_records(path, case):
+    """The record of `case` save_records wrote: strings, float arrays, and Exact digests for the exact ones."""
+    with np.load(path, allow_pickle=False) as z:
+        keys = [k[len(case) + 1:] for k in z.files if k.startswith(case + "/")]
+        get = lambda k: z[f"{case}/{k}"]         # noqa: E731
         rec = {}
-        for key in z.files:
-            rec[key[2:]] = str(z[key]) if key.startswith("s_") else z[key]
+        for k in keys:
+            kind, name = k[:2], k[2:]
+            if kind == "s_":
+                rec[name] = str(get(k))
+            elif kind == "h_":
+                rec[name] = Exact(name, str(get(k)))
+            elif kind == "f_":
+                rec[name] = _unpack_floats(get(k), get("n_" + name))
+        for k in keys:
+            if k.startswith("d_"):
+                rec[k[2:]] = rec[str(get(k))].copy()
     return rec
+
+
+def statements(path):
+    """Logical statements of a script, comments / docstrings / formatting removed (ast round trip)."""
+    import ast
+    tree = ast.parse(Path(path).read_text())
+    out = []
+    for node in ast.walk(tree):
+        if isinstance(node, ast.stmt) and not isinstance(node, (ast.FunctionDef, ast.ClassDef, ast.If, ast.While,
+                                                                 ast.For, ast.With, ast.Try)):
+            if isinstance(node, ast.Expr) and isinstance(node.value, ast.Constant) and isinstance(node.value.value, str):
+                continue
+            out.append(ast.unparse(node))
+    return out
+
+
+def fingerprint(statement):
+    """A statement as a one-way digest: what tests/golden/ keeps of the reference's scripts instead of their text."""
+    import hashlib
+    return hashlib.sha256(statement.encode()).hexdigest()[:16]
 
 
 def run_own_example(case, workdir):
@@ -242,6 +364,4 @@ def assert_same_digest(got, want, rtol=1e-12):
 if __name__ == "__main__":
     import sys
     if len(sys.argv) == 5 and sys.argv[1] == "--child":
-        record = _exec_reference_script(sys.argv[2], sys.argv[3])
-        np.savez(sys.argv[4], **{("s_" if isinstance(v, str) else "a_") + k: (np.array(v) if isinstance(v, str) else np.asarray(v))
-                                  for k, v in record.items()})
+        save_record(sys.argv[4], _exec_reference_script(sys.argv[2], sys.argv[3]))

@@ -294,7 +294,7 @@ def test_bench_multi_rank_path_end_to_end():
     import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--mesh", "64", "--rehearse-on-one-gpu",
+           "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--mesh", "64", "--rehearse-on-one-gpu",
            "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -20,12 +20,12 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 # GPU-initialised processes (bench.py refuses to compile under a profiler for the same reason).
 python3 -c 'import __graft_entry__ as g; g.build()' || exit 9
 ONLY="--no-cpu-baseline --late-start 0 --second-mesh off --big-mesh 0 --no-glow-discharge"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.err" || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.err" || exit 1
 rm -f "$OUT"/trace/t_kernel_trace.csv "$OUT"/trace/*/t_kernel_trace.csv      # tens of MB; the stats are what is kept
 SQ1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA"
 SQ2="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS"
 for W in unstructured tensor; do
-  SHORT="bench.py --steps 2 --warmup 0 --repeats 1 --preroll 0 --family $W $ONLY"
+  SHORT="bench.py --full --steps 2 --warmup 0 --repeats 1 --preroll 0 --family $W $ONLY"
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/$W/fetch" -o f -- python3 $SHORT > /dev/null 2> "$OUT/$W.fetch.err" || exit 2
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/$W/write" -o w -- python3 $SHORT > /dev/null 2> "$OUT/$W.write.err" || exit 3
   rocprofv3 --pmc $SQ1 --output-format csv -d "$OUT/$W/sq1" -o s -- python3 $SHORT > /dev/null 2> "$OUT/$W.sq1.err" || exit 4
@@ -38,7 +38,7 @@ find "$OUT" -name "*counter_collection.csv" | head -20
 python3 tools/copy_profiles.py "$TAG" "$OUT"
 find "$OUT" -name "*counter_collection.csv" -size +4M -delete         # (gpurun_out/ travels back: 64 MiB)
 # kernel-by-kernel listing of one time step (step 6 of the run): a short traced run of its own
-SEQ="bench.py --steps 6 --warmup 3 --repeats 1 --preroll 0 $ONLY"
+SEQ="bench.py --full --steps 6 --warmup 3 --repeats 1 --preroll 0 $ONLY"
 rocprofv3 --kernel-trace --output-format csv -d "$OUT/seq" -o q -- python3 $SEQ > /dev/null 2> "$OUT/seq.err" || exit 8
 TRACE=$(find "$OUT/seq" -name "q_kernel_trace.csv" | head -1)
 { echo "One accepted time step of the headline case (refined unstructured mesh, step 6 of the run, Krylov steps replayed as graphs), kernel by kernel:";

@@ -45,7 +45,7 @@ def load(path, counter):
 short = lambda name: re.sub(r"^void ", "", name).split("(")[0]
 import bench
 res = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes, per launch, MI355X, one block per workload "
-               "(unstructured / tensor: python3 bench.py --steps 2 --warmup 0 --repeats 1 --preroll 0 --family <workload> "
+               "(unstructured / tensor: python3 bench.py --full --steps 2 --warmup 0 --repeats 1 --preroll 0 --family <workload> "
                "--no-cpu-baseline --late-start 0 --second-mesh off --big-mesh 0 --no-glow-discharge; glow_discharge: "
                "python3 tools/gd_steps.py 4).  Both counters are in KiB.  gfx950 correction (MI355X_MICROARCH.md, HBM): "
                "FETCH_SIZE counts half the bytes of a coalesced stream -> read bytes = 2*FETCH_SIZE; WRITE_SIZE is exact.",
@@ -70,7 +70,7 @@ for W in ("unstructured", "tensor", "glow_discharge"):
     res["workloads"][W] = block
 (prof / f"{tag}_pmc_traffic.json").write_text(json.dumps(res, indent=1) + "\n")
 
-text = [f"rocprofv3 --pmc (two passes, 8 SQ counters each) on `python3 bench.py --steps 2 --warmup 0 --repeats 1 --preroll 0 "
+text = [f"rocprofv3 --pmc (two passes, 8 SQ counters each) on `python3 bench.py --full --steps 2 --warmup 0 --repeats 1 --preroll 0 "
         f"--family <mesh> --no-cpu-baseline --late-start 0 --second-mesh off --big-mesh 0 --no-glow-discharge`, averages per "
         f"launch; SQ_WAVE_CYCLES, SQ_WAIT_*, SQ_ACTIVE_INST_* count quad-cycles (MI355X_MICROARCH.md).  kernel sources "
         f"{bench.kernel_source_sha()}", ""]

@@ -8,7 +8,7 @@ python3 -c 'import __graft_entry__ as g; g.build()' || exit 9
 for N in $RANKS; do
     OUT=gpurun_out/rehearsal_${FAMILY}_${N}ranks
     timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500+N*10)) \
-        bench.py --gpus $N --steps 5 --warmup 2 --repeats 1 --preroll 0 --family $FAMILY --rehearse-on-one-gpu --late-start 0 --no-cpu-baseline --configs4 ${CONFIGS4:-auto} > $OUT.json 2> $OUT.err
+        bench.py --full --gpus $N --steps 5 --warmup 2 --repeats 1 --preroll 0 --family $FAMILY --rehearse-on-one-gpu --late-start 0 --no-cpu-baseline --configs4 ${CONFIGS4:-auto} > $OUT.json 2> $OUT.err
     rc=$?
     echo "family=$FAMILY N=$N rc=$rc"
     if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi
