@@ -182,6 +182,8 @@ _SIGNATURES = {
     "fedm_fieldsplit_tiles_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "fedm_fieldsplit_tiles_stats": (C.c_int, [C.POINTER(MeshDesc), C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "fedm_debug_fieldsplit_apply": (C.c_int, [_P, _D, _D]),
+    "fedm_debug_fieldsplit_apply_operator": (C.c_int, [_P, _D, _D, _D]),
+    "fedm_debug_fieldsplit_apply_produced": (C.c_int, [_P, _D, C.c_int, _D, _D, _D]),
     "fedm_debug_fieldsplit_tiles": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "fedm_debug_species_planes_check": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "fedm_profile": (C.c_int, [_P, C.c_int]),
@@ -203,7 +205,7 @@ EXPR_OPS = {"const": 0, "x": 1, "param": 2, "add": 3, "sub": 4, "mul": 5, "div":
 EXPR_MAX_OPS, EXPR_MAX_PARAMS, EXPR_STACK = 256, 16, 24
 
 
-ABI_VERSION = 5          # include/fedm_hip.h FEDM_ABI_VERSION
+ABI_VERSION = 6          # include/fedm_hip.h FEDM_ABI_VERSION
 
 
 def exported_symbols():

@@ -2119,6 +2119,65 @@ int fedm_debug_fieldsplit_apply(fedm_ctx *h, const double *t, double *z) {
     return get_vec(c, z, c.d_w);
 }
 
+int fedm_debug_fieldsplit_apply_operator(fedm_ctx *h, const double *v, double *t, double *z) {
+    Ctx &c = h->c;
+    if (!v || !t || !z || !(c.amg && c.poisson)) {
+        set_error("the field split needs a model with a Poisson row and a multigrid hierarchy (fedm_amg_setup)");
+        return -2;
+    }
+    if (fieldsplit_upper(c)) {
+        set_error("fedm_debug_fieldsplit_apply_operator: the fused operator is the lower-triangular order's");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipMemsetAsync(c.d_rhs, 0, sizeof(double) * c.np, c.stream));   // (padding rows: as fedm_spmv)
+    if (put_vec(c, c.d_rhs, v)) return -1;
+    fieldsplit_setup(c);
+    fieldsplit_apply_operator(c, *c.amg, c.d_rhs, c.d_tmp, c.d_w, true);
+    FEDM_HIP_CHECK(hipGetLastError());
+    if (get_vec(c, t, c.d_tmp)) return -1;
+    return get_vec(c, z, c.d_w);
+}
+
+int fedm_debug_fieldsplit_apply_produced(fedm_ctx *h, const double *t, int k, const double *coef, double *y,
+                                          double *z) {
+    Ctx &c = h->c;
+    if (!t || !coef || !y || !z || !(c.amg && c.poisson) || k < 0 || k > 8) {
+        set_error("fedm_debug_fieldsplit_apply_produced: bad arguments, or no field split (fedm_amg_setup)");
+        return -2;
+    }
+    // the condition under which gmres lets the producers form the first stage (FEDM_FS_FIRST_BY_PRODUCER), the
+    // preconditioner's side aside
+    if (c.comm || fieldsplit_upper(c) || c.fs_sweeps < 2 || !c.d_fs_g) {
+        set_error("fedm_debug_fieldsplit_apply_produced: the producers form no first stage here (one GPU, lower-"
+                  "triangular order, species sweeps)");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipMemsetAsync(c.d_rhs, 0, sizeof(double) * c.np, c.stream));
+    FEDM_HIP_CHECK(hipMemsetAsync(c.d_tmp, 0, sizeof(double) * c.np, c.stream));
+    if (put_vec(c, c.d_rhs, t)) return -1;
+    fieldsplit_setup(c);
+    c.fs_first_by_producer = true;
+    if (k == 0) {
+        krylov_vector_scale(c, coef[0], c.d_rhs, c.d_tmp);
+    } else {
+        // the Gram-Schmidt coefficients where gmres's reduction leaves them: h_i in d_red[i], 1/|.| in d_red[RED_K-1]
+        std::vector<double> red(RED_K, 0.0);
+        for (int i = 0; i < k; ++i) red[i] = coef[i];
+        red[RED_K - 1] = coef[k];
+        FEDM_HIP_CHECK(hipMemcpyAsync(c.d_red, red.data(), sizeof(double) * RED_K, hipMemcpyHostToDevice, c.stream));
+        FEDM_HIP_CHECK(hipMemcpyAsync(c.d_tmp, c.d_rhs, sizeof(double) * c.np, hipMemcpyDeviceToDevice, c.stream));
+        std::vector<const double *> vp((size_t)k, c.d_rhs);
+        krylov_vector_update(c, k, vp.data(), c.d_tmp);
+    }
+    fieldsplit_apply(c, *c.amg, c.d_tmp, c.d_w, 1.0);
+    c.fs_first_by_producer = false;
+    FEDM_HIP_CHECK(hipGetLastError());
+    if (get_vec(c, y, c.d_tmp)) return -1;
+    return get_vec(c, z, c.d_w);
+}
+
 int fedm_pattern_stats(const fedm_mesh_desc *mesh, int64_t out[12]) {
     if (!mesh || !out || mesh->n_vertices < 3 || mesh->n_cells < 1) {
         set_error("null or empty mesh");

@@ -580,7 +580,9 @@ class DeviceProblem:
     def jacobian(self):
         self._check(self.lib.fedm_jacobian(self._h), "fedm_jacobian")
 
-    def jacobian_csr(self):
+    def jacobian_csr(self, device_order=False):
+        """The assembled Jacobian as a scipy CSR matrix in the caller's dof numbering; ``device_order=True``: in the
+        device's own (that of :meth:`fieldsplit_apply` and of the multigrid hierarchy)."""
         import scipy.sparse as sp
         nnz = self.lib.fedm_jacobian_nnz(self._h)
         indptr = np.empty(self.n + 1, dtype=np.int64)
@@ -590,6 +592,8 @@ class DeviceProblem:
             self._h, indptr.ctypes.data_as(C.POINTER(C.c_int64)),
             indices.ctypes.data_as(C.POINTER(C.c_int32)), _dp(values)), "fedm_jacobian_csr")
         J = sp.csr_matrix((values, indices, indptr), shape=(self.n, self.n))
+        if device_order:
+            return J
         m = self._dof_new_of_old
         return J[m][:, m].tocsr()
 
@@ -957,12 +961,38 @@ class DeviceProblem:
         return self.sizes()["assembly_variant"]
 
     def fieldsplit_apply(self, t):
-        """z = Minv t with the field split of the current Jacobian (test hook; call jacobian() first)."""
+        """z = Minv t with the field split of the current Jacobian (test hook; call jacobian() first).  t and z are in
+        the device's vertex numbering (:meth:`jacobian_csr` with ``device_order=True``), not the caller's."""
         t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
         assert t.size == self.n
         z = np.empty(self.n)
         self._check(self.lib.fedm_debug_fieldsplit_apply(self._h, _dp(t), _dp(z)), "fedm_debug_fieldsplit_apply")
         return z
+
+    def fieldsplit_apply_operator(self, v):
+        """(t, z) = (J v, Minv J v) as a Krylov step of the left-preconditioned GMRES forms them (the operator Minv J):
+        the Jacobian product with the field split's first stage in its epilogue, then the rest of the preconditioner
+        (test hook; call jacobian() first; lower-triangular order).  Like :meth:`fieldsplit_apply`, vectors in the
+        device's numbering."""
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        assert v.size == self.n
+        t, z = np.empty(self.n), np.empty(self.n)
+        self._check(self.lib.fedm_debug_fieldsplit_apply_operator(self._h, _dp(v), _dp(t), _dp(z)),
+                    "fedm_debug_fieldsplit_apply_operator")
+        return t, z
+
+    def fieldsplit_apply_produced(self, t, coef):
+        """(y, z = Minv y) as a Krylov step of the right-preconditioned GMRES forms them on one GPU with species sweeps:
+        the kernel that completes the Krylov vector y forms the preconditioner's first stage as well.  ``coef`` of
+        length 1: y = coef[0] t (the vector scaling); of length k + 1: y = (t - sum_i coef[i] t) coef[k] (the
+        Gram-Schmidt update over k basis vectors).  Test hook; vectors in the device's numbering."""
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+        cf = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        assert t.size == self.n and 1 <= cf.size <= 9
+        y, z = np.empty(self.n), np.empty(self.n)
+        self._check(self.lib.fedm_debug_fieldsplit_apply_produced(self._h, _dp(t), int(cf.size - 1), _dp(cf), _dp(y),
+                                                                  _dp(z)), "fedm_debug_fieldsplit_apply_produced")
+        return y, z
 
     def configure_fieldsplit_tiles(self, on, slices_per_tile=0, layers=0, threads=0, multigrid=True):
         """Test hook: species sweeps on tiles (several per launch) or one launch each; multigrid=False keeps the

@@ -212,8 +212,9 @@ const char *fedm_last_error(void);
  * 3: fedm_fieldsplit_tiles_info, fedm_fieldsplit_tiles_stats, fedm_debug_fieldsplit_apply, fedm_debug_fieldsplit_tiles.
  * 4: fedm_state_snapshot, fedm_state_restore; fedm_fieldsplit_tiles_stats out[10]; fedm_comm_stats out[10]; fedm_fieldsplit_policy.
  * 5: fedm_gd_desc.energy_Ei, .mean_energy_form (the sentinel energy losses on the device); fedm_debug_species_planes_check;
- *    fedm_time_kernel kinds 4, 5; fedm_pattern_info out[9]. */
-#define FEDM_ABI_VERSION 5
+ *    fedm_time_kernel kinds 4, 5; fedm_pattern_info out[9].
+ * 6: fedm_debug_fieldsplit_apply_operator, fedm_debug_fieldsplit_apply_produced. */
+#define FEDM_ABI_VERSION 6
 int fedm_abi_version(void);
 
 /* mesh + model -> device: colouring, sliced block-ELL pattern, buffers.
@@ -433,6 +434,18 @@ int fedm_fieldsplit_tiles_stats(const fedm_mesh_desc *mesh, int tile_slices, int
  * species planes are formed here), host vectors of n_vertices * n_eq doubles -- the operator a Krylov step of
  * fedm_newton_solve applies, alone. */
 int fedm_debug_fieldsplit_apply(fedm_ctx *ctx, const double *t, double *z);
+/* Test hook: t = J v and z = Minv t as a Krylov step of the LEFT-preconditioned GMRES forms them (the operator
+ * Minv J, fedm_set_preconditioner_side "left") -- the Jacobian product with the field split's first stage in its
+ * epilogue, then the rest of the preconditioner (lower-triangular order only); host vectors as in
+ * fedm_debug_fieldsplit_apply. */
+int fedm_debug_fieldsplit_apply_operator(fedm_ctx *ctx, const double *v, double *t, double *z);
+/* Test hook: z = Minv y as a Krylov step of the RIGHT-preconditioned GMRES forms it on one GPU with species sweeps
+ * (FEDM_FS_FIRST_BY_PRODUCER): the kernel that completes the Krylov vector y also forms the preconditioner's first
+ * stage, the preconditioner skips its own.  k = 0: y = coef[0] t (the vector scaling); k = 1..8: y = (t - sum_i
+ * coef[i] t) coef[k] (the Gram-Schmidt update over k basis vectors, all of them t).  y and z are returned (host
+ * vectors as in fedm_debug_fieldsplit_apply). */
+int fedm_debug_fieldsplit_apply_produced(fedm_ctx *ctx, const double *t, int k, const double *coef, double *y,
+                                         double *z);
 /* Test hook: mode 0 = species sweeps one launch each from now on (and the multigrid's finest-level sweeps kernels of
  * their own); 3 = species sweeps on tiles, the multigrid's not; 1 = tiles, rebuilt with `tile_slices` slices
  * per tile, `depth` vertex layers and `threads` threads per tile (0: defaults, FEDM_FS_TILE_SLICES /

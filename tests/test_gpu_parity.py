@@ -930,42 +930,12 @@ def test_four_species_and_poisson_against_the_oracle(monkeypatch, lean):
     coefficients; three reactions with field-dependent, constant and quadratic rates.  Residual, Jacobian, product and
     a Newton step of the device path (row-phase kernels / unrolled element routine) against the numpy oracle
     (oracle/forms.py restates fedm/functions.py:240-401 for any number of species)."""
-    from oracle import streamer as ost
-    from oracle.forms import LFAModel, TermSum as OTermSum
-    from oracle.mesh import Mesh as OMesh, mark_boundaries
     from fedm_amd.cases import streamer
-    from fedm_amd.device import DeviceProblem, Model, Reaction
-    from fedm_amd.mesh import Marking_boundaries, Mesh
-    from fedm_amd.termsum import TermSum, parse
+    from lfa_models import four_species_problem
     monkeypatch.setenv("FEDM_ASSEMBLY_LEAN", lean)
-    msh = streamer.mesh(20, 2.0)
-    m = Mesh(msh.coords, msh.cells)
-    tags = Marking_boundaries(m, streamer.BOUNDARIES)
+    m, prob, om, ddofs, dvals = four_species_problem()
     nv = m.coords.shape[0]
-    eq = ["diffusion-reaction", "drift-diffusion-reaction", "drift-diffusion-reaction", "drift-diffusion-reaction"]
-    Z = [0.0, 1.0, -1.0, -1.0]
-    bc = [[kind[0]] * 3 + [kind[1]] for kind in streamer.BC_TYPE]        # the electrons keep the deck's wall types
-    mu_e = parse(streamer.MU_E)
-    ionisation = parse(streamer.ALPHA) * mu_e * TermSum.field()
-    model = Model(n_species=4, poisson=True, eq_type=eq, Z=Z,
-                  mu=[TermSum.const(0.0), TermSum.const(2e-4), TermSum.const(0.0), mu_e],
-                  D=[TermSum.const(5e-4), TermSum.const(3e-6), TermSum.const(2e-3), parse(streamer.D_E)],
-                  reactions=[Reaction(ionisation, power=[0, 0, 0, 1], net=[0, 1, 0, 1]),
-                             Reaction(TermSum.const(3e-17), power=[1, 0, 0, 1], net=[-1, 1, 0, 1]),
-                             Reaction(TermSum.const(1e-19), power=[0, 1, 1, 0], net=[1, -1, -1, 0])],
-                  drift_w=[None, None, (1.0e3, -2.0e3), None], bc_kind=bc, quadrature_degree=2)
-    ddofs, dvals = streamer.dirichlet(m.coords)
-    ddofs = (ddofs // 3) * 5 + 4
-    prob = DeviceProblem(m.coords, m.cells, model, facet_tags=tags, dirichlet_dofs=ddofs.astype(np.int32), dirichlet_vals=dvals)
     assert prob.assembly_variant() == ("lds-patches" if lean == "2" else "lds-patches/unrolled")
-    omesh = OMesh(msh.coords, msh.cells)
-    om = LFAModel(omesh, 4, True, eq, Z,
-                  mu=[0.0, 2e-4, 0.0, ost.MU_E], D=[5e-4, 3e-6, 2e-3, ost.D_E],
-                  drift_w=[None, None, (1.0e3, -2.0e3), None],
-                  reactions=[(ost.K_ION, [0, 0, 0, 1], [0, 1, 0, 1]), (3e-17, [1, 0, 0, 1], [-1, 1, 0, 1]),
-                             (1e-19, [0, 1, 1, 0], [1, -1, -1, 0])],
-                  facet_tags=mark_boundaries(omesh, ost.BOUNDARIES), bc_type=bc, qdeg=2)
-    om.dirichlet_dofs, om.dirichlet_vals = ddofs.astype(np.int64), dvals
     rng = np.random.default_rng(4)
     x, y = m.coords[:, 0] / streamer.BOX, m.coords[:, 1] / streamer.BOX
     U = np.zeros((nv, 5))
