@@ -1258,10 +1258,12 @@ static bool lean3_launch_one(Ctx &c, bool jacobian, const int *list, int n, int 
             static size_t granted = 0;
             const int g = grid_for(reinterpret_cast<const void *>(&assemble_lean3p_kernel<NS, NR, T, CMASK, SIG>), granted);
             lean3_dispatch(c, whole, assemble_lean3p_kernel<NS, NR, T, CMASK, SIG>, g, T, lds, plan, p.val, p.F, p);
+            note_assembly_launch(c, true, 3, T, g);
         } else {
             static size_t granted = 0;
             const int g = grid_for(reinterpret_cast<const void *>(&residual_lean3p_kernel<NS, NR, T, SIG>), granted);
             lean3_dispatch(c, whole, residual_lean3p_kernel<NS, NR, T, SIG>, g, T, lds, plan, p.val, p.F, p);
+            note_assembly_launch(c, false, 3, T, g);
         }
         return true;
     }
@@ -1289,6 +1291,7 @@ static bool lean3_launch_one(Ctx &c, bool jacobian, const int *list, int n, int 
     } else {
         lean3_dispatch(c, whole, residual_lean3_kernel<NS, NR, T, SIG>, n, T, lds, plan, p);
     }
+    note_assembly_launch(c, jacobian, 3, T, n);
     return true;
 }
 
@@ -1334,8 +1337,28 @@ int lean3_signature(const Ctx &c) {
     return (!(e && e[0] == '0') && lean3_sig_matches<Lean3SigBenchmark>(plan)) ? 1 : 0;
 }
 
+// The planes launch_assemble_lean3 keeps in LDS for the kept planes `cmask` (the instantiation it takes for them)
+static int lean3_live_planes(uint32_t cmask) {
+    constexpr uint32_t PHIPHI = 1u << 8;
+    switch (cmask) {
+        case 0u: return LivePlanes<2, 0u>::N;
+        case PHIPHI: return LivePlanes<2, PHIPHI>::N;
+        case PHIPHI | (1u << 3): return LivePlanes<2, PHIPHI | (1u << 3)>::N;
+        case PHIPHI | (1u << 1): return LivePlanes<2, PHIPHI | (1u << 1)>::N;
+        default: return (cmask & PHIPHI) ? LivePlanes<2, PHIPHI>::N : LivePlanes<2, 0u>::N;
+    }
+}
+
+// The launch for the whole mesh (sized for the widest slice and the most staged vertices) fits the 160 KiB of LDS a
+// workgroup may have.  The caller decides with it before it launches: on a context's first Jacobian (all nine
+// planes) the answer can be no where it is yes for the later ones (the potential plane kept).
+bool lean3_fits(const Ctx &c, bool jacobian, uint32_t cmask) {
+    const int planes = jacobian ? lean3_live_planes(cmask) : 0;
+    return lean3_lds_bytes(c.neq, c.ns, c.pat.max_patch_width, c.pat.max_patch_verts, planes, jacobian) <= 160 * 1024;
+}
+
 // cmask: the planes that are kept for this launch (0 on a context's first full assembly: everything is written).
-// false: the launch does not fit (LDS beyond the device's limit: the caller takes the second generation).
+// false: the launch does not fit or its plan could not be uploaded (the caller takes another kernel).
 bool launch_assemble_lean3(Ctx &c, bool jacobian, const int *list, int n, uint32_t cmask) {
     if (n <= 0) return true;
     if (!jacobian) return lean3_launch<2, 1, 0u>(c, false, list, n);

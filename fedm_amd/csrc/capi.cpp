@@ -1594,9 +1594,16 @@ int fedm_residual(fedm_ctx *h, double *F_out, double *fnorm) {
     double fn = 0.0;
     eval_residual(c, 0, &fn);
     if (fnorm) *fnorm = fn;
+    FEDM_HIP_CHECK(hipGetLastError());   // (a refused launch: before F is copied out)
     if (F_out) return get_vec(c, F_out, c.d_F);
-    FEDM_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+int fedm_get_residual(fedm_ctx *h, double *F_out) {
+    if (!h || !F_out) return -2;
+    Ctx &c = h->c;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    return get_vec(c, F_out, c.d_F);
 }
 
 int fedm_jacobian(fedm_ctx *h) {
@@ -2405,19 +2412,23 @@ int fedm_pattern_info(fedm_ctx *h, int64_t out[9]) {
     out[3] = c.pat.max_patch_verts;
     out[4] = (int64_t)c.pat.patch_cells.size();
     out[5] = (int64_t)c.pat.patch_halo.size();
-    // the volume assembly a fedm_jacobian call runs: 0 global colouring, 1 LDS patches with the
-    // unrolled element routine, 2 LDS patches one equation row at a time (lean2 kernels)
-    bool ext = false;
-    for (int s = 0; s < c.ns; ++s) ext = ext || (c.model_kind == 0 && c.model.ext_nodes[s] > 0);
-    const bool lean_model = c.assembly_kind == 1 && c.assembly_lean >= 2 && c.poisson && c.model_kind == 0 && !ext &&
-                            c.model.n_qp == 3 && !c.model.linear_representation;
-    const bool lean3 = lean_model && c.assembly_lean >= 3 && lean3_applies(c);
-    const bool lean2 = lean_model && c.pat.max_patch_cells <= 256;
-    // 3: LDS patches, one pass over the cells (lean3 kernels, assemble3.hip)
-    out[6] = c.assembly_kind == 0 ? 0 : (lean3 ? 3 : lean2 ? 2 : 1);
-    out[7] = c.assembly_kind == 0 ? 0 : (c.pat.max_patch_cells <= 192 || out[6] == 3 ? 192 : (lean2 ? 256 : 320));
+    // the volume assembly the next fedm_jacobian call runs (kernels.hip, assembly_prediction: the dispatch's own
+    // conditions): 0 global colouring, 1 LDS patches with the unrolled element routine, 2 LDS patches one equation
+    // row at a time (lean2 kernels), 3 LDS patches, one pass over the cells (lean3 kernels, assemble3.hip)
+    int threads = 0;
+    const int variant = assembly_prediction(c, true, &threads);
+    out[6] = variant < 0 ? 0 : variant;
+    out[7] = threads;
     // the one-pass kernels with the model's structure compiled in (assemble3.hip, Lean3SigBenchmark)
-    out[8] = lean3 ? lean3_signature(c) : 0;
+    out[8] = variant == 3 ? lean3_signature(c) : 0;
+    return 0;
+}
+
+int fedm_launched_assembly(fedm_ctx *h, int64_t out[8]) {
+    if (!h || !out) return -2;
+    const Ctx &c = h->c;
+    for (int j = 0; j < 2; ++j)
+        for (int k = 0; k < 4; ++k) out[4 * j + k] = c.launched[j][k];
     return 0;
 }
 

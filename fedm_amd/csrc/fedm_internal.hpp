@@ -255,7 +255,18 @@ struct Ctx {
     int lean3_sig = 0;              // the precompiled structure signature the plan selects (assemble3.hip; 0: none)
     void *lean3_classes = nullptr; // assemble3.hip: patch lists by LDS need (Lean3Classes), built at first use
     double *d_snapshot = nullptr;  // fedm_state_snapshot: u, u_old, u_old1 (3 np doubles, allocated on first use)
+    // the volume assembly the last residual [0] and Jacobian [1] launched (fedm_launched_assembly): variant
+    // (fedm_pattern_info's numbering, -1 before the first), threads per workgroup, launches, workgroups of all launches
+    int launched[2][4] = {{-1, 0, 0, 0}, {-1, 0, 0, 0}};
 };
+
+inline void note_assembly_launch(Ctx &c, bool jacobian, int variant, int threads, int workgroups) {
+    int *r = c.launched[jacobian ? 1 : 0];
+    r[0] = variant;
+    r[1] = threads;
+    r[2] += 1;
+    r[3] += workgroups;
+}
 
 constexpr int RED_BLOCKS = 512;
 constexpr int RED_K = 40;
@@ -273,6 +284,10 @@ void launch_assemble_gd(Ctx &c, bool jacobian, int mode);
 bool lean3_applies(const Ctx &c);                                   // assemble3.hip
 void lean3_release(Ctx &c);
 bool launch_assemble_lean3(Ctx &c, bool jacobian, const int *patch_list, int n, uint32_t cmask);
+bool lean3_fits(const Ctx &c, bool jacobian, uint32_t cmask);       // its LDS for these kept planes fits the device
+// the volume assembly of the next full-model residual (jacobian = false) or Jacobian: variant as fedm_pattern_info's,
+// threads per workgroup (kernels.hip; assemble_patch_t dispatches with the same conditions)
+int assembly_prediction(const Ctx &c, bool jacobian, int *threads);
 int lean3_signature(const Ctx &c);   // the precompiled model structure the one-pass kernels run with (0: run-time structure)
 int gd_prep_setup(Ctx &c, const fedm_csr *mass, int n_tables, const int32_t *tab_ptr,
                   const double *tab_x, const double *tab_y, const fedm_gd_field_prog *progs);

@@ -107,6 +107,7 @@ static void assemble_colour_t(Ctx &c, bool jacobian, int mode) {
                            c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_uold, c.d_uold1, sc,
                            c.d_ext[0], c.d_ext[1], c.d_ext[2], c.d_ext[3], c.d_val, c.d_F,
                            jacobian ? 1 : 0, mode);
+        note_assembly_launch(c, jacobian, 0, 256, (n + 255) / 256);
     }
 }
 
@@ -371,6 +372,7 @@ __device__ __forceinline__ void assemble_lean2_body(FEDM_PATCH_PARAMS, int xcd, 
                 FEDM_ROW_CASE(1)
                 FEDM_ROW_CASE(2)
                 FEDM_ROW_CASE(3)
+                FEDM_ROW_CASE(4)
             }
 #undef FEDM_ROW_CASE
 #else
@@ -466,10 +468,15 @@ static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
     if constexpr (PO && CACHE == 2 && NS >= 1 && !LIN) {
         bool ext = false;
         for (int s_ = 0; s_ < NS; ++s_) ext = ext || c.model.ext_nodes[s_] > 0;
-        // (the third generation takes patches of up to 384 cells -- a second cell for some threads --, the second
-        // one cell per thread of at most 256)
-        const bool gen3_ok = c.assembly_lean >= 3 && lean3_applies(c);
-        if (mode == 0 && !ext && c.assembly_lean >= 2 && (c.pat.max_patch_cells <= 256 || gen3_ok)) {
+        // the constant potential-potential plane: written by the first full assembly, kept afterwards
+        const uint32_t cmask = (jacobian && c.skip_const_planes && c.const_planes_valid) ? c.const_plane_mask : 0u;
+        // The third generation takes patches of up to 384 cells (a second cell for some threads) where its LDS fits
+        // (the first Jacobian keeps all nine planes there: it may not fit where the later ones do); the second one
+        // takes one cell per thread, so patches of at most 256 cells.  Anything else goes to the generic kernel
+        // below, which loops over the cells.
+        const bool gen3 = c.assembly_lean >= 3 && lean3_applies(c) && lean3_fits(c, jacobian, cmask);
+        const bool gen2 = c.pat.max_patch_cells <= 256;
+        if (mode == 0 && !ext && c.assembly_lean >= 2 && (gen2 || gen3)) {
             // one cell per thread: 192 threads where every patch has at most 192 cells (tensor-product
             // meshes: 160; compact patches of an unstructured mesh: 170-190), else 256
             const int T = c.pat.max_patch_cells <= 192 ? 192 : 256;
@@ -478,11 +485,14 @@ static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
                                                        (size_t)(NEQ + 2 * NS) * c.pat.max_patch_verts +
                                                        (size_t)LeanStash<NR>::N * T);
 #define FEDM_LEAN2_LAUNCH_T(KERNEL, LIST, N, TT)                                                            \
-    hipLaunchKernelGGL((KERNEL<NS, NR, TT>), dim3(N), dim3(TT), lds_bytes, c.stream, c.d_model,             \
-                       c.nv, c.d_slice_boff, c.d_patch_cell_ptr, c.d_patch_cells, c.d_patch_halo_ptr,       \
-                       c.d_patch_halo, c.d_coords, c.d_u, c.d_uold, c.d_uold1, sc, c.d_ext[0], c.d_ext[1],  \
-                       c.d_ext[2], c.d_ext[3], c.d_val, c.d_F, mode, acc_row, c.pat.max_patch_verts,        \
-                       c.xcd_remap ? 1 : 0, LIST, cmask)
+    do {                                                                                                    \
+        hipLaunchKernelGGL((KERNEL<NS, NR, TT>), dim3(N), dim3(TT), lds_bytes, c.stream, c.d_model,         \
+                           c.nv, c.d_slice_boff, c.d_patch_cell_ptr, c.d_patch_cells, c.d_patch_halo_ptr,   \
+                           c.d_patch_halo, c.d_coords, c.d_u, c.d_uold, c.d_uold1, sc, c.d_ext[0],          \
+                           c.d_ext[1], c.d_ext[2], c.d_ext[3], c.d_val, c.d_F, mode, acc_row,               \
+                           c.pat.max_patch_verts, c.xcd_remap ? 1 : 0, LIST, cmask);                        \
+        note_assembly_launch(c, jacobian, 2, TT, N);                                                        \
+    } while (0)
 #define FEDM_LEAN2_LAUNCH(KERNEL, LIST, N)                                                                  \
     do {                                                                                                    \
         if (T == 192) FEDM_LEAN2_LAUNCH_T(KERNEL, LIST, N, 192);                                            \
@@ -497,46 +507,91 @@ static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
             FEDM_LEAN2_LAUNCH(residual_lean2_kernel, LIST, N);                                              \
         }                                                                                                   \
     } while (0)
-            // the constant potential-potential plane: written by the first full assembly, kept afterwards
-            const uint32_t cmask = (jacobian && c.skip_const_planes && c.const_planes_valid) ? c.const_plane_mask : 0u;
             // third generation (assemble3.hip: one pass over the cells, compile-time plane mask) where it is
-            // instantiated; FEDM_ASSEMBLY_LEAN=2 keeps the row-phase kernels below
-            const bool gen3 = gen3_ok;
-#define FEDM_LEAN3_OR(LIST, N) (gen3 && launch_assemble_lean3(c, jacobian, LIST, N, cmask))
+            // instantiated; FEDM_ASSEMBLY_LEAN=2 keeps the row-phase kernels below.  A third-generation launch that
+            // fails all the same (its plan not uploaded) falls back to the second generation only where that takes
+            // every cell; otherwise `done` turns false and the generic kernel assembles the whole mesh.
+            bool done = true;
+#define FEDM_LEAN3_OR_LEAN2(LIST, N)                                                                        \
+    do {                                                                                                    \
+        if (gen3 && launch_assemble_lean3(c, jacobian, LIST, N, cmask)) break;                              \
+        if (gen2) FEDM_LEAN2_BOTH(LIST, N);                                                                 \
+        else done = false;                                                                                  \
+    } while (0)
             if (c.halo_pending && c.comm && c.comm->d_patch_interior) {
                 // the ghost values of the new state travel on the communication stream while the
                 // patches that stage no ghost vertex are assembled (north_star: "ghost exchange
                 // overlapped with interior assembly"); the patches that do follow the exchange
                 Comm &cm = *c.comm;
                 comm_halo_begin(c);
-                if (!FEDM_LEAN3_OR(cm.d_patch_interior, cm.n_patch_interior))
-                    FEDM_LEAN2_BOTH(cm.d_patch_interior, cm.n_patch_interior);
+                FEDM_LEAN3_OR_LEAN2(cm.d_patch_interior, cm.n_patch_interior);
                 comm_halo_exchange(c, c.d_u);
-                if (!FEDM_LEAN3_OR(cm.d_patch_boundary, cm.n_patch_boundary))
-                    FEDM_LEAN2_BOTH(cm.d_patch_boundary, cm.n_patch_boundary);
+                if (done) FEDM_LEAN3_OR_LEAN2(cm.d_patch_boundary, cm.n_patch_boundary);
                 c.halo_pending = false;
             } else {
                 flush_pending_halo(c);
-                if (!FEDM_LEAN3_OR((const int *)nullptr, c.pat.n_slices))
-                    FEDM_LEAN2_BOTH((const int *)nullptr, c.pat.n_slices);
+                FEDM_LEAN3_OR_LEAN2((const int *)nullptr, c.pat.n_slices);
             }
-#undef FEDM_LEAN3_OR
+#undef FEDM_LEAN3_OR_LEAN2
 #undef FEDM_LEAN2_BOTH
 #undef FEDM_LEAN2_LAUNCH
 #undef FEDM_LEAN2_LAUNCH_T
-            if (jacobian) c.const_planes_valid = true;
-            return;
+            if (done) {
+                if (jacobian) c.const_planes_valid = true;
+                return;
+            }
         }
     }
     flush_pending_halo(c);
+    const int T = c.pat.max_patch_cells <= 192 ? 192 : 320;
     if (jacobian) {
-        if (c.pat.max_patch_cells <= 192) FEDM_PATCH_LAUNCH(assemble_patch_kernel, 192);
+        if (T == 192) FEDM_PATCH_LAUNCH(assemble_patch_kernel, 192);
         else FEDM_PATCH_LAUNCH(assemble_patch_kernel, 320);
     } else {
-        if (c.pat.max_patch_cells <= 192) FEDM_PATCH_LAUNCH(residual_patch_kernel, 192);
+        if (T == 192) FEDM_PATCH_LAUNCH(residual_patch_kernel, 192);
         else FEDM_PATCH_LAUNCH(residual_patch_kernel, 320);
     }
 #undef FEDM_PATCH_LAUNCH
+    note_assembly_launch(c, jacobian, 1, T, c.pat.n_slices);
+    // every plane written, the constant ones included (the lean kernels may keep them from here on)
+    if (jacobian && mode == 0) c.const_planes_valid = true;
+}
+
+// What assemble_patch_t / assemble_colour_t launch for a full-model assembly (mode 0) of this context as it stands:
+// the same conditions, evaluated on the host (fedm_pattern_info).  The one-pass and row-phase kernels need a
+// template instance assemble_dispatch takes for the LFA family with Poisson, FIAT's degree-2 rule and the
+// logarithmic representation, and no external source (the one-pass kernels besides: lean3_applies).
+int assembly_prediction(const Ctx &c, bool jacobian, int *threads) {
+    if (c.model_kind != 0) {
+        *threads = 0;
+        return -1;
+    }
+    if (c.assembly_kind == 0) {
+        *threads = 256;
+        return 0;
+    }
+    const fedm_model_desc &m = c.model;
+    bool ext = false;
+    for (int s = 0; s < c.ns; ++s) ext = ext || m.ext_nodes[s] > 0;
+    const double sixth = 1.0 / 6.0, two3 = 2.0 / 3.0;
+    const bool stdq = m.n_qp == 3 && m.qp_x[0] == sixth && m.qp_x[1] == sixth && m.qp_x[2] == two3 &&
+                      m.qp_y[0] == sixth && m.qp_y[1] == two3 && m.qp_y[2] == sixth && m.qp_w[0] == sixth &&
+                      m.qp_w[1] == sixth && m.qp_w[2] == sixth;
+    const bool lean_model = c.poisson && c.ns >= 1 && c.ns <= 4 && !m.linear_representation && stdq && !ext &&
+                            c.assembly_lean >= 2;
+    const uint32_t cmask = (jacobian && c.skip_const_planes && c.const_planes_valid) ? c.const_plane_mask : 0u;
+    const bool gen3 = lean_model && c.assembly_lean >= 3 && lean3_applies(c) && lean3_fits(c, jacobian, cmask);
+    const bool gen2 = lean_model && c.pat.max_patch_cells <= 256;
+    if (gen3) {
+        *threads = 192;
+        return 3;
+    }
+    if (gen2) {
+        *threads = c.pat.max_patch_cells <= 192 ? 192 : 256;
+        return 2;
+    }
+    *threads = c.pat.max_patch_cells <= 192 ? 192 : 320;
+    return 1;
 }
 
 // =============================================================================================
@@ -625,6 +680,9 @@ static void assemble_dispatch(Ctx &c, bool jacobian, int mode) {
     // the non-logarithmic representation runs on the generic (uncached, any reaction count) element only
     if (m.linear_representation) assemble_variant<NS, PO, FEDM_MAX_REACTIONS, 0, true>(c, jacobian, mode);
     else if (few && stdq) assemble_variant<NS, PO, 1, (NEQ > 1) ? 2 : 0>(c, jacobian, mode);
+    // (the row-phase kernels take any number of reactions: element_lean.hpp stashes the rate coefficients of one
+    // reaction beside the cell constants and evaluates several in each species row)
+    else if (stdq) assemble_variant<NS, PO, FEDM_MAX_REACTIONS, (NEQ > 1) ? 2 : 0>(c, jacobian, mode);
     else if (few && cache) assemble_variant<NS, PO, 1, (NEQ > 1) ? 1 : 0>(c, jacobian, mode);
     else if (few) assemble_variant<NS, PO, 1, 0>(c, jacobian, mode);
     else if (cache) assemble_variant<NS, PO, FEDM_MAX_REACTIONS, (NEQ > 1) ? 1 : 0>(c, jacobian, mode);
@@ -640,6 +698,9 @@ void launch_assemble(Ctx &c, bool jacobian, int mode) {
         return;
     }
     if (jacobian) c.planes_fused = false;   // (set by the one-pass kernel when it forms the field split's planes itself)
+    int *rec = c.launched[jacobian ? 1 : 0];   // what this assembly launches (note_assembly_launch)
+    rec[0] = -1;
+    rec[1] = rec[2] = rec[3] = 0;
     prof_begin(c, jacobian ? 0 : 2);  // the volume kernel only (all colours in variant 0)
     if (c.ns == 1 && !c.poisson) assemble_dispatch<1, false>(c, jacobian, mode);
     else if (c.ns == 1 && c.poisson) assemble_dispatch<1, true>(c, jacobian, mode);

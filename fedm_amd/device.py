@@ -356,6 +356,10 @@ def fieldsplit_tiles_stats(coords, cells, slices_per_tile=8, layers=3, reorder=T
     return dict(zip(keys, (int(v) for v in out)))
 
 
+# fedm_pattern_info's / fedm_launched_assembly's numbering of the volume-assembly kernels
+_VARIANTS = ("global colouring", "lds-patches/unrolled", "lds-patches", "lds-patches/one-pass")
+
+
 class DeviceProblem:
     """Mesh + model + state resident on one MI355X."""
 
@@ -579,6 +583,13 @@ class DeviceProblem:
 
     def jacobian(self):
         self._check(self.lib.fedm_jacobian(self._h), "fedm_jacobian")
+
+    def residual_vector(self):
+        """F as the last assembly left it (that of :meth:`residual` or the F + J of :meth:`jacobian`), not evaluated
+        again."""
+        F = np.empty(self.n)
+        self._check(self.lib.fedm_get_residual(self._h, _dp(F)), "fedm_get_residual")
+        return self._back(F)
 
     def jacobian_csr(self, device_order=False):
         """The assembled Jacobian as a scipy CSR matrix in the caller's dof numbering; ``device_order=True``: in the
@@ -952,13 +963,26 @@ class DeviceProblem:
         self._check(self.lib.fedm_pattern_info(self._h, info), "fedm_pattern_info")
         out.update(zip(("n_slices", "max_patch_cells", "max_patch_width", "max_patch_verts", "cell_visits",
                         "halo_vertices"), (int(v) for v in info[:6])))
-        out["assembly_variant"] = ("global colouring", "lds-patches/unrolled", "lds-patches", "lds-patches/one-pass")[int(info[6])]
+        out["assembly_variant"] = _VARIANTS[int(info[6])]
         out["patch_threads"] = int(info[7])
         out["model_structure"] = "compiled in" if info[8] else "run time"
         return out
 
     def assembly_variant(self):
         return self.sizes()["assembly_variant"]
+
+    def launched_assembly(self):
+        """The volume-assembly kernels the last residual-only assembly ("residual") and the last Jacobian assembly
+        ("jacobian") launched (``fedm_launched_assembly``): variant (as :meth:`assembly_variant` names it; None before
+        the first), threads per workgroup, launches and workgroups of all launches."""
+        out = (C.c_int64 * 8)()
+        self._check(self.lib.fedm_launched_assembly(self._h, out), "fedm_launched_assembly")
+        rec = {}
+        for k, what in enumerate(("residual", "jacobian")):
+            v, threads, launches, wgs = (int(x) for x in out[4 * k:4 * k + 4])
+            rec[what] = dict(variant=_VARIANTS[v] if v >= 0 else None, threads=threads, launches=launches,
+                             workgroups=wgs)
+        return rec
 
     def fieldsplit_apply(self, t):
         """z = Minv t with the field split of the current Jacobian (test hook; call jacobian() first).  t and z are in

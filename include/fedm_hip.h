@@ -213,8 +213,10 @@ const char *fedm_last_error(void);
  * 4: fedm_state_snapshot, fedm_state_restore; fedm_fieldsplit_tiles_stats out[10]; fedm_comm_stats out[10]; fedm_fieldsplit_policy.
  * 5: fedm_gd_desc.energy_Ei, .mean_energy_form (the sentinel energy losses on the device); fedm_debug_species_planes_check;
  *    fedm_time_kernel kinds 4, 5; fedm_pattern_info out[9].
- * 6: fedm_debug_fieldsplit_apply_operator, fedm_debug_fieldsplit_apply_produced. */
-#define FEDM_ABI_VERSION 6
+ * 6: fedm_debug_fieldsplit_apply_operator, fedm_debug_fieldsplit_apply_produced.
+ * 7: fedm_launched_assembly, fedm_get_residual; fedm_pattern_info out[6..7] predict what the next fedm_jacobian
+ *    launches. */
+#define FEDM_ABI_VERSION 7
 int fedm_abi_version(void);
 
 /* mesh + model -> device: colouring, sliced block-ELL pattern, buffers.
@@ -408,13 +410,21 @@ int fedm_debug_comm_roundtrip(fedm_ctx *ctx, double *vec, double *red, int k);
  * patches, colours of the global cell colouring, (wave of 64 patch cells, local row) pairs in which some
  * cell owns that vertex: what the assembly kernels emit; the others are skipped}. */
 int fedm_pattern_stats(const fedm_mesh_desc *mesh, int64_t out[12]);
-/* The same for a live context, and which volume-assembly kernels it runs: out = {slices, max cells per
- * patch, max block columns per slice, max staged vertices per patch, cell visits, halo vertices,
+/* The same for a live context, and which volume-assembly kernels its next fedm_jacobian call runs: out = {slices,
+ * max cells per patch, max block columns per slice, max staged vertices per patch, cell visits, halo vertices,
  * assembly variant (0 global colouring, 1 LDS patches / unrolled element routine, 2 LDS patches / one
- * equation row at a time, 3 LDS patches / one pass over the cells), threads per patch workgroup, 1 when the one-pass
+ * equation row at a time, 3 LDS patches / one pass over the cells), threads per workgroup, 1 when the one-pass
  * kernels run with the model's STRUCTURE compiled in (a precompiled signature matches it: csrc/assemble3.hip) and only
- * its numbers read at run time}. */
+ * its numbers read at run time}.  The variant can change after the first Jacobian: that one writes all planes, the
+ * later ones keep the constant planes and need less LDS. */
 int fedm_pattern_info(fedm_ctx *ctx, int64_t out[9]);
+/* The volume-assembly kernels the last residual-only assembly and the last Jacobian assembly of the LFA family
+ * actually launched: out = {residual: variant (fedm_pattern_info's numbering; -1: none yet), threads per workgroup,
+ * launches, workgroups of all launches; Jacobian: the same four}.  With several launches (the halo-overlap halves,
+ * the colouring's colours, FEDM_LEAN3_CLASSES) variant and threads are the last one's. */
+int fedm_launched_assembly(fedm_ctx *ctx, int64_t out[8]);
+/* F as the last assembly left it (residual-only or F + J: no evaluation), caller-side layout as fedm_residual's. */
+int fedm_get_residual(fedm_ctx *ctx, double *F_out);
 /* The species sweeps of the field split (the Chebyshev polynomial in Duu^-1 Juu that stands for PETSc's
  * sub-solver of the species block; no counterpart in the scripts): on one GPU they run several per launch on
  * tiles of matrix slices whose vertex layers sit in LDS (csrc/fs_tiles.hip).  Returns 1 when this context

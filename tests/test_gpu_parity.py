@@ -956,6 +956,7 @@ def test_four_species_and_poisson_against_the_oracle(monkeypatch, lean):
     assert (np.abs(F_gpu - F_cpu).reshape(-1, 5) / scale).max() < 1e-11
     assert fnorm == pytest.approx(np.linalg.norm(F_cpu), rel=1e-11)
     prob.jacobian()
+    assert prob.launched_assembly()["jacobian"]["variant"] == ("lds-patches" if lean == "2" else "lds-patches/unrolled")
     J_gpu = prob.jacobian_csr()
     assert _rel_rows(J_gpu, J_cpu) < 1e-10
     xv = rng.normal(size=prob.n)

@@ -64,6 +64,9 @@ CASES = {
     "refined-head-poly2-upper": dict(mesh="refined", state="head", order="upper",
                                      mg=dict(nu=1, omega=0.85, poly_degree=2)),
     "glow-discharge": dict(model="glow"),
+    # limit meshes (tests/limit_meshes.py): width 12, the widest tile instances; width 15, no tiles (sweeps one by one)
+    "width12-head": dict(mesh="width12", state="head"),
+    "width13+-head": dict(mesh="width13+", state="head"),
 }
 
 # Measured on an MI355X (first run of this file): (emulated restatement, float64 restatement) per case and right-hand
@@ -100,6 +103,8 @@ MEASURED = {
     "refined-head-poly2-upper": {"random": (4.0e-07, 2.1e-04), "potential": (1.4e-06, 2.0e-04)},
     "glow-discharge": {"random": (6.3e-05, 4.8e-03), "potential": (2.6e-08, 5.9e-08)},
     "operator": {"random": (3.0e-04, 6.0e-02)},
+    "width12-head": {"random": (3.9e-05, 2.3e-02), "potential": (2.8e-08, 2.1e-08)},
+    "width13+-head": {"random": (4.9e-05, 2.8e-02), "potential": (4.5e-08, 3.0e-08)},
 }
 
 
@@ -115,6 +120,9 @@ def _mesh(kind):
         from oracle.mesh import graded_axis, rectangle_right
         m = rectangle_right(0.0, 0.0, ost.BOX, ost.BOX, 20, 20, xs=graded_axis(ost.BOX, 20, 6.0))
         return m.coords, m.cells
+    if kind in ("width12", "width13+"):
+        import limit_meshes
+        return limit_meshes.build(kind)
     if kind == "tensor":
         m = streamer.mesh(63)                            # 64 x 64 = 4096 vertices: full slices only
     else:
