@@ -181,6 +181,8 @@ _SIGNATURES = {
     "fedm_pattern_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "fedm_launched_assembly": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "fedm_get_residual": (C.c_int, [_P, _D]),
+    "fedm_solver_path_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
+    "fedm_debug_linear_solve": (C.c_int, [_P, _D, C.POINTER(NewtonOpts), _D, C.POINTER(C.c_int), _D]),
     "fedm_fieldsplit_tiles_info": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "fedm_fieldsplit_tiles_stats": (C.c_int, [C.POINTER(MeshDesc), C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "fedm_debug_fieldsplit_apply": (C.c_int, [_P, _D, _D]),
@@ -207,7 +209,7 @@ EXPR_OPS = {"const": 0, "x": 1, "param": 2, "add": 3, "sub": 4, "mul": 5, "div":
 EXPR_MAX_OPS, EXPR_MAX_PARAMS, EXPR_STACK = 256, 16, 24
 
 
-ABI_VERSION = 7          # include/fedm_hip.h FEDM_ABI_VERSION
+ABI_VERSION = 8          # include/fedm_hip.h FEDM_ABI_VERSION
 
 
 def exported_symbols():

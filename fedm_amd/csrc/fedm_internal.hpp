@@ -258,6 +258,36 @@ struct Ctx {
     // the volume assembly the last residual [0] and Jacobian [1] launched (fedm_launched_assembly): variant
     // (fedm_pattern_info's numbering, -1 before the first), threads per workgroup, launches, workgroups of all launches
     int launched[2][4] = {{-1, 0, 0, 0}, {-1, 0, 0, 0}};
+    // which branches of gmres() and fedm_newton_solve ran (fedm_solver_path_stats; indices PS_*): host counters only
+    int64_t path_stats[24] = {};
+};
+
+// Indices of Ctx::path_stats, in the order fedm_solver_path_stats documents (include/fedm_hip.h)
+enum PathStat {
+    PS_CYCLES = 0,          // GMRES cycles that ran at least one Krylov step
+    PS_STEPS_SINGLE,        // Krylov steps launched one by one, with their orthonormalising update
+    PS_STEPS_PAIR,          // ... as part of a two-step graph (a second step that went in as 'the last one' excluded)
+    PS_STEPS_LAST,          // ... 'as the last one': without their update (singly or as the second step of a pair)
+    PS_STEPS_DROPPED,       // steps launched ahead whose results were never used
+    PS_UPDATES_MADE_UP,     // skipped updates launched afterwards because the solve went on
+    PS_SECOND_PASSES,       // second Gram-Schmidt passes
+    PS_FUSED_UPDATES,       // u += Z y and the stol norms formed by launch_newton_update
+    PS_GENERIC_UPDATES,     // delta += Z y by launch_multi_axpy (one per cycle that ends with k > 0 otherwise)
+    PS_DEFERRED_NORM,       // solves whose |rhs| rode on the first step's publication
+    PS_NOTHING_TO_SOLVE,    // |rhs| <= tol exits
+    PS_RESIDUAL_ONLY_RIGHT, // residual-only final checks of the Newton loop that did end the solve
+    PS_RESIDUAL_ONLY_WRONG, // ... that did not: a Jacobian was assembled after all
+    PS_ERR_CACHE_SERVED,    // fedm_field_error calls answered from the cache
+    PS_STEPS_USED,          // Krylov steps counted by the solves (the sum of their iteration counts)
+    PS_STEPS_AHEAD,         // steps launched before the step in front of them had been read
+    PS_STEPS_AHEAD_LATER,   // ... in a cycle after the first
+    PS_SOLVES,              // gmres() calls
+    PS_BREAKDOWNS,          // happy breakdowns (h_{j+1,j} == 0)
+    PS_EXHAUSTED,           // solves that stopped at ksp_max_it
+    PS_NEWTON_MAX_IT,       // Newton solves that stopped at max_it
+    PS_VERIFIED,            // true residuals formed at the start of a cycle (restarts, and before a success is reported)
+    PS_VERIFY_FAILED,       // ... that contradicted the recurrence's 'converged': another cycle ran (or the solve gave up)
+    PS_COUNT
 };
 
 inline void note_assembly_launch(Ctx &c, bool jacobian, int variant, int threads, int workgroups) {

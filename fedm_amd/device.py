@@ -356,6 +356,13 @@ def fieldsplit_tiles_stats(coords, cells, slices_per_tile=8, layers=3, reorder=T
     return dict(zip(keys, (int(v) for v in out)))
 
 
+# the counters of fedm_solver_path_stats, in its order (include/fedm_hip.h)
+SOLVER_PATH_STATS = ("cycles", "steps_single", "steps_pair", "steps_last", "steps_dropped", "updates_made_up",
+                     "second_passes", "fused_updates", "generic_updates", "deferred_norm", "nothing_to_solve",
+                     "residual_only_right", "residual_only_wrong", "err_cache_served", "steps_used", "steps_ahead",
+                     "steps_ahead_later", "solves", "breakdowns", "exhausted", "newton_max_it", "verified",
+                     "verify_failed")
+
 # fedm_pattern_info's / fedm_launched_assembly's numbering of the volume-assembly kernels
 _VARIANTS = ("global colouring", "lds-patches/unrolled", "lds-patches", "lds-patches/one-pass")
 
@@ -983,6 +990,28 @@ class DeviceProblem:
             rec[what] = dict(variant=_VARIANTS[v] if v >= 0 else None, threads=threads, launches=launches,
                              workgroups=wgs)
         return rec
+
+    def solver_path_stats(self, reset=False):
+        """Which branches of the GMRES driver and of the Newton loop have run on this context
+        (``fedm_solver_path_stats``; host counters, named as :data:`SOLVER_PATH_STATS`); ``reset=True`` zeroes them
+        after reading."""
+        out = (C.c_int64 * 24)()
+        self._check(self.lib.fedm_solver_path_stats(self._h, out, int(bool(reset))), "fedm_solver_path_stats")
+        return {name: int(out[k]) for k, name in enumerate(SOLVER_PATH_STATS)}
+
+    def linear_solve(self, b, ksp_restart=30, ksp_rtol=1e-5, ksp_atol=1e-50, ksp_max_it=10000):
+        """Test hook: GMRES on ``J x = b`` with the Jacobian of the last :meth:`jacobian` / :meth:`newton_solve`, through
+        the call the Newton loop makes (``fedm_debug_linear_solve``).  Returns ``(x, its, rnorm, code)`` with the
+        solver's own return code (0, or a key of ``_lib.DIVERGED``) instead of raising on a numerical failure; b and x
+        in the caller's dof order.  The state is untouched; :meth:`residual_vector` is -b afterwards."""
+        b = self._vec(b)
+        x = np.empty(self.n)
+        o = _lib.NewtonOpts(0.0, 0.0, 0.0, 0, ksp_restart, ksp_rtol, ksp_atol, ksp_max_it, 0)
+        its, rn = C.c_int(), C.c_double()
+        rc = self.lib.fedm_debug_linear_solve(self._h, _dp(b), C.byref(o), _dp(x), C.byref(its), C.byref(rn))
+        if rc < 0:
+            self._check(rc, "fedm_debug_linear_solve")
+        return self._back(x), its.value, rn.value, rc
 
     def fieldsplit_apply(self, t):
         """z = Minv t with the field split of the current Jacobian (test hook; call jacobian() first).  t and z are in

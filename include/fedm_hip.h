@@ -215,8 +215,9 @@ const char *fedm_last_error(void);
  *    fedm_time_kernel kinds 4, 5; fedm_pattern_info out[9].
  * 6: fedm_debug_fieldsplit_apply_operator, fedm_debug_fieldsplit_apply_produced.
  * 7: fedm_launched_assembly, fedm_get_residual; fedm_pattern_info out[6..7] predict what the next fedm_jacobian
- *    launches. */
-#define FEDM_ABI_VERSION 7
+ *    launches.
+ * 8: fedm_solver_path_stats, fedm_debug_linear_solve. */
+#define FEDM_ABI_VERSION 8
 int fedm_abi_version(void);
 
 /* mesh + model -> device: colouring, sliced block-ELL pattern, buffers.
@@ -423,6 +424,33 @@ int fedm_pattern_info(fedm_ctx *ctx, int64_t out[9]);
  * launches, workgroups of all launches; Jacobian: the same four}.  With several launches (the halo-overlap halves,
  * the colouring's colours, FEDM_LEAN3_CLASSES) variant and threads are the last one's. */
 int fedm_launched_assembly(fedm_ctx *ctx, int64_t out[8]);
+/* Which branches of the GMRES driver and of the Newton loop have run on this context since it was created (or since
+ * the last call with reset != 0): host counters, nothing is added on the device.  out (may be NULL with reset) =
+ *  [0] GMRES cycles that ran a Krylov step        [1] steps launched one by one, with their orthonormalising update
+ *  [2] steps launched as part of a two-step graph  [3] steps launched 'as the last one' (without their update; singly
+ *      or as the second step of a pair, which [2] then does not count)
+ *  [4] steps launched ahead whose results were dropped (the solve ended before them, or a second Gram-Schmidt pass
+ *      or a non-finite number made them void)       [5] skipped updates made up afterwards
+ *  [6] second Gram-Schmidt passes                  [7] Newton updates fused with the GMRES update (<= 8 steps, one cycle)
+ *  [8] generic updates delta += Z y (one per cycle otherwise)
+ *  [9] solves with a deferred right-hand-side norm  [10] 'nothing to solve' exits
+ *  [11] residual-only final checks of the Newton loop that were right   [12] ... that were wrong
+ *  [13] fedm_field_error calls served from the cache
+ *  [14] Krylov steps counted by the solves: [1] + [2] + [3] - [4]
+ *  [15] steps launched before the step in front of them had been read   [16] ... in a cycle after the first
+ *  [17] GMRES solves   [18] happy breakdowns   [19] solves stopped by ksp_max_it   [20] Newton solves stopped by max_it
+ *  [21] true residuals formed at the start of a cycle: at every restart, and before a solve that ended on the generic
+ *       update reports success   [22] ... that contradicted the recurrence's 'converged' (another cycle ran, or the
+ *       solve gave up with FEDM_DIVERGED_LINEAR because such a cycle had not halved the residual)   [23] reserved. */
+int fedm_solver_path_stats(fedm_ctx *ctx, int64_t out[24], int reset);
+/* Test hook: x = the GMRES solution of J x = b with the Jacobian and the preconditioner as the last fedm_jacobian /
+ * fedm_newton_solve left them, through the very call fedm_newton_solve makes (same preparation of the preconditioner
+ * and of the right-hand side for the side in use; opts' ksp_* fields are read).  The state is not touched; F of the
+ * last assembly is overwritten with -b.  b and x in the caller-side layout of fedm_residual.  Returns what the solver
+ * returns (0, FEDM_DIVERGED_LINEAR, FEDM_DIVERGED_NAN); its / rnorm: its step count and the residual norm it reports
+ * (on the left: of the preconditioned residual). */
+int fedm_debug_linear_solve(fedm_ctx *ctx, const double *b, const fedm_newton_opts *opts, double *x, int *its,
+                            double *rnorm);
 /* F as the last assembly left it (residual-only or F + J: no evaluation), caller-side layout as fedm_residual's. */
 int fedm_get_residual(fedm_ctx *ctx, double *F_out);
 /* The species sweeps of the field split (the Chebyshev polynomial in Duu^-1 Juu that stands for PETSc's
