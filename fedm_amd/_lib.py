@@ -196,6 +196,8 @@ _SIGNATURES = {
     "fedm_set_preconditioner_side": (C.c_int, [_P, C.c_int]),
     "fedm_plane_masks": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "fedm_set_fieldsplit_order": (C.c_int, [_P, C.c_int]),
+    "fedm_set_krylov_scaling": (C.c_int, [_P, C.c_int]),
+    "fedm_get_krylov_scaling": (C.c_int, [_P, C.POINTER(C.c_int), _D]),
     "fedm_sizes": (C.c_int, [_P] + [C.POINTER(C.c_int64)] * 6),
 }
 
@@ -209,7 +211,7 @@ EXPR_OPS = {"const": 0, "x": 1, "param": 2, "add": 3, "sub": 4, "mul": 5, "div":
 EXPR_MAX_OPS, EXPR_MAX_PARAMS, EXPR_STACK = 256, 16, 24
 
 
-ABI_VERSION = 8          # include/fedm_hip.h FEDM_ABI_VERSION
+ABI_VERSION = 9          # include/fedm_hip.h FEDM_ABI_VERSION
 
 
 def exported_symbols():

@@ -604,7 +604,8 @@ static const bool skip_last_ok = [] {
 // ---- GMRES(m) ---------------------------------------------------------------------------------
 // Preconditioner on the left (point-block Jacobi; field split across GPUs): solves
 // Minv J delta = Minv rhs (rhs in c.d_rhs, already scaled), convergence on the preconditioned
-// residual norm |r| <= max(rtol*|r0|, atol).  Field split (one GPU by default, several always): on the right, flexible
+// residual norm |r| <= max(rtol*|r0|, atol).  (With fedm_set_krylov_scaling "rows" every norm below -- the right-hand
+// side's, the recurrence's, the true residual's at the start of a cycle and in the reports -- is |D .|.)  Field split (one GPU by default, several always): on the right, flexible
 // (z_j = Minv v_j kept, delta = Z y): rhs is -F itself, one preconditioner application less per
 // solve, and the norm tested is that of the true residual.  delta starts at 0; classical
 // Gram-Schmidt (PETSc's KSPGMRES default).
@@ -629,9 +630,23 @@ static int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int 
         const char *e = std::getenv("FEDM_FS_FIRST_BY_PRODUCER");
         return !(e && e[0] == '0');
     }();
+    // Row-equilibrated test (fedm_set_krylov_scaling): the same vectors, product and preconditioner, GMRES in the inner
+    // product <x, y> = sum_i d_i^2 x_i y_i -- the iterates of GMRES on D J M^-1 D^-1 with the basis D^-1 V, so M^-1
+    // receives D^-1 times a unit vector, not a scaled one.  Only the reductions change: for the duration of this solve
+    // every launch_dots / launch_dots_fused / launch_spmv_dots / launch_norm2 takes the weights c.red_w.  Defined for
+    // the field split on the right; on the left the tested residual M^-1 r is equilibrated already.
+    const bool scaled = c.krylov_scaling != 0;
+    if (scaled && !right) {
+        set_error("krylov scaling 'rows' is defined for the field-split preconditioner on the right only (this solve "
+                  "runs point-block Jacobi or the field split on the left): set the krylov scaling to 'none'");
+        return -2;
+    }
     struct ProducerMode {
         Ctx &c;
-        ~ProducerMode() { c.fs_first_by_producer = false; }
+        ~ProducerMode() {
+            c.fs_first_by_producer = false;
+            c.red_w = nullptr;
+        }
     } producer_mode{c};
     c.fs_first_by_producer = first_by_producer_ok && right && !c.comm && !fieldsplit_upper(c) && c.fs_sweeps > 1 &&
                              c.d_fs_g != nullptr;
@@ -655,6 +670,19 @@ static int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int 
     if (u_updated) *u_updated = false;
     int64_t *ps = c.path_stats;
     ++ps[PS_SOLVES];
+    if (scaled) {
+        // the weights of the Jacobian as it stands, and |D b|: the norm the caller knows is the unscaled one
+        launch_row_scale(c, c.d_kscale2, nullptr);
+        c.red_w = c.d_kscale2;
+        launch_norm2(c, bvec, 0);
+        read_red(c, 1);
+        bnorm_known = std::sqrt(c.h_red[0]);
+        if (!std::isfinite(bnorm_known)) {
+            *its_out = 0;
+            *rnorm_out = bnorm_known;
+            return FEDM_DIVERGED_NAN;
+        }
+    }
     if (bnorm_known < 0.0) ++ps[PS_DEFERRED_NORM];
     int its = 0, cycle = 0;
     double r0 = -1.0, rnorm = 0.0;
@@ -1454,6 +1482,7 @@ void fedm_ctx_destroy(fedm_ctx *h) {
     if (c.d_s16) hipFree(c.d_s16);
     if (c.d_planes_rows) hipFree(c.d_planes_rows);
     if (c.d_Z) hipFree(c.d_Z);
+    if (c.d_kscale2) hipFree(c.d_kscale2);
     if (c.h_stage) hipHostFree(c.h_stage);
     if (c.d_snapshot) hipFree(c.d_snapshot);
     lean3_release(c);
@@ -2453,6 +2482,35 @@ int fedm_set_fieldsplit_order(fedm_ctx *h, int upper) {
         c.fs_upper = upper == 1;
     }
     return 0;
+}
+
+int fedm_set_krylov_scaling(fedm_ctx *h, int mode) {
+    if (!h) return -2;
+    Ctx &c = h->c;
+    if (mode != 0 && mode != 1) {
+        set_error("krylov scaling mode must be 0 (none) or 1 (rows)");
+        return -2;
+    }
+    if (c.krylov_scaling != mode) {
+        FEDM_HIP_CHECK(hipSetDevice(c.device));
+        hipStreamSynchronize(c.stream);
+        iter_graphs_clear(c);  // captured with the other instantiations of the reduction kernels
+        if (mode == 1 && !c.d_kscale2) FEDM_HIP_CHECK(hipMalloc((void **)&c.d_kscale2, sizeof(double) * c.np));
+        c.krylov_scaling = mode;
+    }
+    return 0;
+}
+
+int fedm_get_krylov_scaling(fedm_ctx *h, int *mode, double *d_out) {
+    if (!h) return -2;
+    Ctx &c = h->c;
+    if (mode) *mode = c.krylov_scaling;
+    if (!d_out) return 0;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    // from the Jacobian as it stands: what a scaled solve started now would use (d^2 goes to scratch when no scaled
+    // solve has run on this context)
+    launch_row_scale(c, c.d_kscale2 ? c.d_kscale2 : c.d_tmp, c.d_w);
+    return get_vec(c, d_out, c.d_w);
 }
 
 int fedm_plane_masks(fedm_ctx *h, uint32_t *kept_planes, uint32_t *zero_planes) {

@@ -224,6 +224,12 @@ struct Ctx {
     // Z y and no preconditioner application is spent on the right-hand side.
     double *d_Z = nullptr;
     bool right_precond = true;
+    // Row-equilibrated residual test (fedm_set_krylov_scaling; 0 none, 1 rows): d_kscale2 = d^2 per DOF (np doubles,
+    // row_scale_kernel, refreshed at the start of every scaled solve); red_w points at it for the duration of such a
+    // solve and is null otherwise -- the reduction launchers take their weighted instantiations when it is set.
+    int krylov_scaling = 0;
+    double *d_kscale2 = nullptr;
+    const double *red_w = nullptr;
     // reductions
     double *d_partials = nullptr;  // [RED_BLOCKS][RED_K]
     double *d_partials_wide = nullptr;  // [8][workgroups of the Jacobian product]: spmv_dots_kernel
@@ -327,6 +333,7 @@ void gd_prep_release(Ctx &c);
 size_t patch_lds_bytes(const Ctx &c, bool jacobian = true);
 void launch_finalize(Ctx &c, bool jacobian, int mode);          // Dirichlet + padding rows
 void launch_block_inverse(Ctx &c);                              // d_dinv from diagonal blocks
+void launch_row_scale(Ctx &c, double *d2, double *d_out);       // d^2 (and d, unless null) of the rows' equilibration
 void launch_spmv(Ctx &c, const double *x, double *y, bool scale_dinv, const int *slice_list = nullptr,
                  int n_list = 0);
 void launch_ext_source_eval(Ctx &c, int species, const double *params);   // gdprep.hip
@@ -347,7 +354,7 @@ void launch_cgs_update(Ctx &c, int k, const double *const *xs, double *y);
 // u += delta = sum_i coef_i zs[i] (k <= 8), d_red[1] = |delta|^2, d_red[2] = |u|^2 (owned entries)
 void launch_newton_update(Ctx &c, const double *coef_host, int k, const double *const *zs, double *u,
                           double *delta);
-void launch_norm2(Ctx &c, const double *x, int slot);                       // d_red[slot] = x.x
+void launch_norm2(Ctx &c, const double *x, int slot);                       // d_red[slot] = x.x  (Ctx::red_w set: sum w x x)
 void launch_axpy(Ctx &c, double a, const double *x, double *y);             // y += a x
 void launch_scale_copy(Ctx &c, double a, const double *x, double *y);       // y = a x
 void launch_normalise_copy(Ctx &c, int slot, const double *x, double *y);   // y = x / sqrt(d_red[slot])

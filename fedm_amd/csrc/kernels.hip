@@ -993,6 +993,45 @@ void launch_block_inverse(Ctx &c) {
     }
 }
 
+// Row equilibration of the Krylov residual test (fedm_set_krylov_scaling): for the DOF (vertex v, component r)
+// s = sqrt(sum_c J[(v,r),(v,c)]^2) over row r of the vertex's diagonal block, d = 1 / s (1 where s is zero or not
+// finite: identity rows get exactly 1).  A thread per vertex, the planes block_inverse_kernel reads; d2 = d^2 is what
+// the weighted reductions multiply by, d itself is written only for whoever asks (fedm_get_krylov_scaling).
+template <int NEQ>
+__global__ void row_scale_kernel(int nvp, const double *__restrict__ val, const uint32_t *__restrict__ diag_slot,
+                                 double *__restrict__ d2, double *__restrict__ d_out) {
+    constexpr int NEQ2 = NEQ * NEQ;
+    const int vtx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (vtx >= nvp) return;
+    const uint32_t ds = diag_slot[vtx];
+    const double *blk = val + (size_t)(ds >> 6) * NEQ2 * SLICE + (ds & 63);
+#pragma unroll
+    for (int r = 0; r < NEQ; ++r) {
+        double s2 = 0.0;
+#pragma unroll
+        for (int cidx = 0; cidx < NEQ; ++cidx) {
+            const double a = blk[(size_t)(r * NEQ + cidx) * SLICE];
+            s2 += a * a;
+        }
+        const double s = sqrt(s2);
+        const double d = (s > 0.0 && s < 1.7e308) ? 1.0 / s : 1.0;   // (NaN fails both comparisons)
+        d2[(size_t)vtx * NEQ + r] = d * d;
+        if (d_out) d_out[(size_t)vtx * NEQ + r] = d;
+    }
+}
+
+void launch_row_scale(Ctx &c, double *d2, double *d_out) {
+    const dim3 g((c.nvp + 255) / 256), b(256);
+    switch (c.neq) {
+        case 1: hipLaunchKernelGGL(row_scale_kernel<1>, g, b, 0, c.stream, c.nvp, c.d_val, c.d_diag_slot, d2, d_out); break;
+        case 2: hipLaunchKernelGGL(row_scale_kernel<2>, g, b, 0, c.stream, c.nvp, c.d_val, c.d_diag_slot, d2, d_out); break;
+        case 3: hipLaunchKernelGGL(row_scale_kernel<3>, g, b, 0, c.stream, c.nvp, c.d_val, c.d_diag_slot, d2, d_out); break;
+        case 4: hipLaunchKernelGGL(row_scale_kernel<4>, g, b, 0, c.stream, c.nvp, c.d_val, c.d_diag_slot, d2, d_out); break;
+        case 5: hipLaunchKernelGGL(row_scale_kernel<5>, g, b, 0, c.stream, c.nvp, c.d_val, c.d_diag_slot, d2, d_out); break;
+        case 6: hipLaunchKernelGGL(row_scale_kernel<6>, g, b, 0, c.stream, c.nvp, c.d_val, c.d_diag_slot, d2, d_out); break;
+    }
+}
+
 // =============================================================================================
 // SpMV on the sliced block-ELL matrix: one wavefront per slice, one lane per vertex.
 // Matrix values and column indices stream in coalesced (lanes contiguous); x is gathered per
@@ -1227,15 +1266,18 @@ struct PtrPack8 {
 };
 
 // partials[block][kbase + i] = sum over the block's grid-stride range of xs[i] * y
-template <int K>
+// W (row-equilibrated GMRES, fedm_set_krylov_scaling): the sums run in the inner product <x, y> = sum_i wgt_i x_i y_i,
+// wgt = d^2 of row_scale_kernel.  A template flag: the unweighted instantiation is the code it was.
+template <int K, bool W = false>
 __global__ __launch_bounds__(256) void dots_kernel(PtrPack8 xs, const double *__restrict__ y,
-                                                   size_t n, double *__restrict__ partials, int kbase) {
+                                                   size_t n, double *__restrict__ partials, int kbase,
+                                                   const double *__restrict__ wgt = nullptr) {
     double acc[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) acc[i] = 0.0;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n;
          idx += (size_t)gridDim.x * blockDim.x) {
-        const double yv = y[idx];
+        const double yv = W ? y[idx] * wgt[idx] : y[idx];
 #pragma unroll
         for (int i = 0; i < K; ++i) acc[i] += xs.p[i][idx] * yv;
     }
@@ -1307,11 +1349,11 @@ __global__ __launch_bounds__(64) void cgs_finish_kernel(int k, double *__restric
 // Every kernel boundary costs ~4-5 us on this GPU, more than the work of these small kernels.
 // (A single kernel with a last-block-done ticket was tried: the agent-scope fences it needs
 // across the 8 XCDs' L2s cost 60 us.)
-template <int K>
+template <int K, bool W = false>
 __global__ __launch_bounds__(256) void dots_scatter_kernel(PtrPack8 xs, double *__restrict__ y, size_t n,
                                                            double *__restrict__ partials, int kbase,
                                                            int self_index, const double *__restrict__ x0,
-                                                           int neq) {
+                                                           int neq, const double *__restrict__ wgt = nullptr) {
     double acc[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) acc[i] = 0.0;
@@ -1325,16 +1367,18 @@ __global__ __launch_bounds__(256) void dots_scatter_kernel(PtrPack8 xs, double *
             y[base + neq - 1] = phi;
             for (int cidx = 0; cidx < neq; ++cidx) {
                 const double yv = (cidx == neq - 1) ? phi : y[base + cidx];
+                const double yw = W ? yv * wgt[base + cidx] : yv;
 #pragma unroll
-                for (int i = 0; i < K; ++i) acc[i] += (i == self_index ? yv : xs.p[i][base + cidx]) * yv;
+                for (int i = 0; i < K; ++i) acc[i] += (i == self_index ? yv : xs.p[i][base + cidx]) * yw;
             }
         }
     } else {
         for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n;
              idx += (size_t)gridDim.x * blockDim.x) {
             const double yv = y[idx];
+            const double yw = W ? yv * wgt[idx] : yv;
 #pragma unroll
-            for (int i = 0; i < K; ++i) acc[i] += (i == self_index ? yv : xs.p[i][idx]) * yv;
+            for (int i = 0; i < K; ++i) acc[i] += (i == self_index ? yv : xs.p[i][idx]) * yw;
         }
     }
     block_reduce_store<K>(acc, partials, kbase);
@@ -1386,12 +1430,14 @@ __global__ __launch_bounds__(1024) void reduce_finish_kernel(const double *__res
 // that has formed a slice's rows of w multiplies them with the same rows of the basis vectors before it stores them
 // (w is not read back: 8 MB and a 9 us kernel less per step).  One partial per workgroup and slot,
 // partials[slot * n_blocks + block]; spmv_dots_finish_kernel reduces them in a fixed order.
-template <int NEQ, unsigned ZMASK, int K>
+// W: the dot products in the weighted inner product (dots_kernel); the rows' weights are read once the rows are formed.
+template <int NEQ, unsigned ZMASK, int K, bool W = false>
 __global__ __launch_bounds__(256) void spmv_dots_kernel(int n_slices, int n_owned, const int *__restrict__ boff,
                                                         const int *__restrict__ colidx,
                                                         const double *__restrict__ val,
                                                         const double *__restrict__ x, double *__restrict__ y,
-                                                        PtrPack8 xs, double *__restrict__ partials, int xcd) {
+                                                        PtrPack8 xs, double *__restrict__ partials, int xcd,
+                                                        const double *__restrict__ wgt = nullptr) {
     constexpr int NEQ2 = NEQ * NEQ;
     const int blk = (xcd & 1) ? xcd_contiguous(blockIdx.x, gridDim.x) : blockIdx.x;
     const int wave_id = blk * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -1432,17 +1478,40 @@ __global__ __launch_bounds__(256) void spmv_dots_kernel(int n_slices, int n_owne
     double d[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) d[i] = 0.0;
-    if (owned) {
+    if constexpr (W) {
+        // the rows are stored first and then weighted in place: no registers beyond the unweighted kernel's
+        if (live) {
 #pragma unroll
-        for (int i = 0; i < K - 1; ++i)
+            for (int r = 0; r < NEQ; ++r) y[vtx * NEQ + r] = owned ? acc[r] : 0.0;
+        }
+        if (owned) {
 #pragma unroll
-            for (int r = 0; r < NEQ; ++r) d[i] += xs.p[i][vtx * NEQ + r] * acc[r];
+            for (int r = 0; r < NEQ; ++r) {
+                const double a = acc[r];
+                acc[r] = a * wgt[vtx * NEQ + r];
+                d[K - 1] += a * acc[r];
+            }
+            // (the weights' registers are free before the basis vectors' loads are issued: without this the scheduler
+            // hoists those loads above the scaling and the K = 7 instantiation loses a wave per SIMD)
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int r = 0; r < NEQ; ++r) d[K - 1] += acc[r] * acc[r];
-    }
-    if (live) {
+            for (int i = 0; i < K - 1; ++i)
 #pragma unroll
-        for (int r = 0; r < NEQ; ++r) y[vtx * NEQ + r] = owned ? acc[r] : 0.0;
+                for (int r = 0; r < NEQ; ++r) d[i] += xs.p[i][vtx * NEQ + r] * acc[r];
+        }
+    } else {
+        if (owned) {
+#pragma unroll
+            for (int i = 0; i < K - 1; ++i)
+#pragma unroll
+                for (int r = 0; r < NEQ; ++r) d[i] += xs.p[i][vtx * NEQ + r] * acc[r];
+#pragma unroll
+            for (int r = 0; r < NEQ; ++r) d[K - 1] += acc[r] * acc[r];
+        }
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < NEQ; ++r) y[vtx * NEQ + r] = owned ? acc[r] : 0.0;
+        }
     }
     __shared__ double sm[4][K];
     const int wave = threadIdx.x >> 6;
@@ -1537,16 +1606,21 @@ void launch_dots(Ctx &c, const double *const *xs, const double *y, int k, bool f
         const int kk = (k - done) >= 8 ? 8 : (k - done);
         PtrPack8 pk;
         for (int i = 0; i < 8; ++i) pk.p[i] = xs[done + (i < kk ? i : 0)];
+#define FEDM_D(K)                                                                                              \
+    if (c.red_w) hipLaunchKernelGGL((dots_kernel<K, true>), dim3(grid), dim3(256), 0, c.stream, pk, y,             \
+                                    (size_t)c.n_dot, c.d_partials, done, c.red_w);                                 \
+    else hipLaunchKernelGGL(dots_kernel<K>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, c.d_partials, done)
         switch (kk) {
-            case 1: hipLaunchKernelGGL(dots_kernel<1>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, c.d_partials, done); break;
-            case 2: hipLaunchKernelGGL(dots_kernel<2>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, c.d_partials, done); break;
-            case 3: hipLaunchKernelGGL(dots_kernel<3>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, c.d_partials, done); break;
-            case 4: hipLaunchKernelGGL(dots_kernel<4>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, c.d_partials, done); break;
-            case 5: hipLaunchKernelGGL(dots_kernel<5>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, c.d_partials, done); break;
-            case 6: hipLaunchKernelGGL(dots_kernel<6>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, c.d_partials, done); break;
-            case 7: hipLaunchKernelGGL(dots_kernel<7>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, c.d_partials, done); break;
-            default: hipLaunchKernelGGL(dots_kernel<8>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, c.d_partials, done); break;
+            case 1: FEDM_D(1); break;
+            case 2: FEDM_D(2); break;
+            case 3: FEDM_D(3); break;
+            case 4: FEDM_D(4); break;
+            case 5: FEDM_D(5); break;
+            case 6: FEDM_D(6); break;
+            case 7: FEDM_D(7); break;
+            default: FEDM_D(8); break;
         }
+#undef FEDM_D
         done += kk;
     }
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(k), dim3(64), 0, c.stream, c.d_partials, grid, k, c.d_red);
@@ -1579,8 +1653,10 @@ void launch_dots_fused(Ctx &c, const double *const *xs, double *y, int k, const 
         }
         const double *sc = (done == 0) ? x0 : nullptr;
 #define FEDM_DF(K)                                                                                     \
-    hipLaunchKernelGGL(dots_scatter_kernel<K>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, \
-                       c.d_partials, done, self, sc, c.neq)
+    if (c.red_w) hipLaunchKernelGGL((dots_scatter_kernel<K, true>), dim3(grid), dim3(256), 0, c.stream, pk, y, \
+                                    (size_t)c.n_dot, c.d_partials, done, self, sc, c.neq, c.red_w);        \
+    else hipLaunchKernelGGL(dots_scatter_kernel<K>, dim3(grid), dim3(256), 0, c.stream, pk, y, (size_t)c.n_dot, \
+                            c.d_partials, done, self, sc, c.neq)
         switch (kk) {
             case 1: FEDM_DF(1); break;
             case 2: FEDM_DF(2); break;
@@ -1623,8 +1699,10 @@ bool launch_spmv_dots(Ctx &c, const double *x, double *y, const double *const *x
     for (int i = 0; i < 8; ++i) pk.p[i] = xs[i < k - 1 ? i : 0];
     const int xcd = (c.xcd_remap ? 1 : 0) | spmv_nontemporal(c);
 #define FEDM_SD(Z, K)                                                                                       \
-    hipLaunchKernelGGL((spmv_dots_kernel<3, Z, K>), g, b, 0, c.stream, n, c.n_owned, c.d_slice_boff, c.d_colidx, \
-                       c.d_val, x, y, pk, c.d_partials_wide, xcd)
+    if (c.red_w) hipLaunchKernelGGL((spmv_dots_kernel<3, Z, K, true>), g, b, 0, c.stream, n, c.n_owned,       \
+                                    c.d_slice_boff, c.d_colidx, c.d_val, x, y, pk, c.d_partials_wide, xcd, c.red_w); \
+    else hipLaunchKernelGGL((spmv_dots_kernel<3, Z, K>), g, b, 0, c.stream, n, c.n_owned, c.d_slice_boff, c.d_colidx, \
+                            c.d_val, x, y, pk, c.d_partials_wide, xcd)
 #define FEDM_SD_K(Z)                                                                                        \
     do {                                                                                                    \
         if (k == 2) FEDM_SD(Z, 2);                                                                          \
@@ -1785,7 +1863,10 @@ void launch_norm2(Ctx &c, const double *x, int slot) {
     const int grid = red_grid(c);
     PtrPack8 pk;
     for (int i = 0; i < 8; ++i) pk.p[i] = x;
-    hipLaunchKernelGGL(dots_kernel<1>, dim3(grid), dim3(256), 0, c.stream, pk, x, (size_t)c.n_dot, c.d_partials, RED_K - 1);
+    if (c.red_w)   // inside a row-equilibrated GMRES solve: |D x|^2
+        hipLaunchKernelGGL((dots_kernel<1, true>), dim3(grid), dim3(256), 0, c.stream, pk, x, (size_t)c.n_dot, c.d_partials, RED_K - 1, c.red_w);
+    else
+        hipLaunchKernelGGL(dots_kernel<1>, dim3(grid), dim3(256), 0, c.stream, pk, x, (size_t)c.n_dot, c.d_partials, RED_K - 1);
     hipLaunchKernelGGL(reduce_partials_slot_kernel, dim3(1), dim3(64), 0, c.stream, c.d_partials, grid, RED_K - 1, c.d_red, slot);
     comm_allreduce(c, c.d_red + slot, 1);
 }

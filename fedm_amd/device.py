@@ -918,9 +918,34 @@ class DeviceProblem:
         J_u,phi z_phi: the residual test passes in half the Krylov steps late in a streamer run, but
         the potential is left at V-cycle accuracy -- include/fedm_hip.h); order of the
         block-triangular split when it is on the right of the operator.  Takes effect with the next
-        Jacobian assembly."""
+        Jacobian assembly.  With ``set_krylov_scaling("rows")`` that caveat no longer holds: the
+        equilibrated residual norm sees the Poisson rows, and a converged solve means the same accuracy
+        in either order."""
         code = {"lower": 0, "upper": 1}[order]
         self._check(self.lib.fedm_set_fieldsplit_order(self._h, code), "fedm_set_fieldsplit_order")
+
+    def set_krylov_scaling(self, mode):
+        """'none' (default: GMRES tests ``|b - J x|``, which the species rows dominate) or 'rows': GMRES minimises
+        and tests ``|D (b - J x)|`` against ``max(ksp_rtol |D b|, ksp_atol)`` with ``d_i`` one over the 2-norm of row
+        ``i`` of its vertex's diagonal block (1 for identity rows), so that every equation is held on its own scale
+        (``fedm_set_krylov_scaling``).  Field split on the right only: a solve under point-block Jacobi or with the
+        split on the left raises.  The Newton loop's own test stays on the unscaled ``|F|``."""
+        code = {"none": 0, "rows": 1}[mode]
+        self._check(self.lib.fedm_set_krylov_scaling(self._h, code), "fedm_set_krylov_scaling")
+
+    def krylov_scaling_mode(self):
+        """0 (none) or 1 (rows): the mode alone, without the vector."""
+        mode = C.c_int()
+        self._check(self.lib.fedm_get_krylov_scaling(self._h, C.byref(mode), None), "fedm_get_krylov_scaling")
+        return mode.value
+
+    def krylov_scaling(self):
+        """``(mode, d)``: 0 or 1, and the row scaling ``d`` of the Jacobian as it stands (what a scaled solve started now
+        uses; caller's dof order) -- ``fedm_get_krylov_scaling``."""
+        mode = C.c_int()
+        d = np.empty(self.n)
+        self._check(self.lib.fedm_get_krylov_scaling(self._h, C.byref(mode), _dp(d)), "fedm_get_krylov_scaling")
+        return mode.value, self._back(d)
 
     # -- measurement ----------------------------------------------------------
     def species_planes_check(self):

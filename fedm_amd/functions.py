@@ -482,20 +482,30 @@ class PETScSNESSolver:
     accepted for compatibility: the device path always solves the Newton systems with restarted
     (flexible) GMRES -- preconditioned by the field split (Chebyshev sweeps on the species block
     + one multigrid V-cycle on the potential block) once ``setup_multigrid`` has installed a
-    hierarchy, by point-block Jacobi otherwise -- to ``krylov_relative_tolerance``."""
+    hierarchy, by point-block Jacobi otherwise -- to ``krylov_relative_tolerance``.
+    ``krylov_residual_scaling``: "none" (the test is on ``|b - J x|``) or "rows" (on the row-equilibrated
+    ``|D (b - J x)|``, ``DeviceProblem.set_krylov_scaling``; field split on the right only)."""
 
     def __init__(self):
         self.parameters = {"relative_tolerance": 1e-9, "absolute_tolerance": 1e-10,
                            "solution_tolerance": 1e-16, "maximum_iterations": 50,
                            "linear_solver": "gmres", "preconditioner": "default",
                            "krylov_restart": 30, "krylov_relative_tolerance": 1e-5,
-                           "krylov_maximum_iterations": 10000}
+                           "krylov_maximum_iterations": 10000, "krylov_residual_scaling": "none"}
 
     def solve(self, problem, x=None):
         p = self.parameters
         dev = problem.device
         if getattr(problem, "before_solve", None) is not None:
             problem.before_solve()      # e.g. time-dependent Dirichlet values (functions.py:1042-1044)
+        scaling = p.get("krylov_residual_scaling", "none")
+        if scaling not in ("none", "rows"):
+            raise ValueError(f"krylov_residual_scaling must be 'none' or 'rows', got {scaling!r}")
+        if hasattr(dev, "krylov_scaling_mode"):
+            if dev.krylov_scaling_mode() != ("none", "rows").index(scaling):
+                dev.set_krylov_scaling(scaling)
+        elif scaling != "none":
+            raise NotImplementedError("krylov_residual_scaling needs a device problem with set_krylov_scaling")
         return dev.newton_solve(rtol=p["relative_tolerance"], max_it=p["maximum_iterations"],
                                 atol=p["absolute_tolerance"], stol=p["solution_tolerance"],
                                 ksp_restart=p["krylov_restart"],

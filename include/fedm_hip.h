@@ -216,8 +216,9 @@ const char *fedm_last_error(void);
  * 6: fedm_debug_fieldsplit_apply_operator, fedm_debug_fieldsplit_apply_produced.
  * 7: fedm_launched_assembly, fedm_get_residual; fedm_pattern_info out[6..7] predict what the next fedm_jacobian
  *    launches.
- * 8: fedm_solver_path_stats, fedm_debug_linear_solve. */
-#define FEDM_ABI_VERSION 8
+ * 8: fedm_solver_path_stats, fedm_debug_linear_solve.
+ * 9: fedm_set_krylov_scaling, fedm_get_krylov_scaling. */
+#define FEDM_ABI_VERSION 9
 int fedm_abi_version(void);
 
 /* mesh + model -> device: colouring, sliced block-ELL pattern, buffers.
@@ -448,7 +449,8 @@ int fedm_solver_path_stats(fedm_ctx *ctx, int64_t out[24], int reset);
  * and of the right-hand side for the side in use; opts' ksp_* fields are read).  The state is not touched; F of the
  * last assembly is overwritten with -b.  b and x in the caller-side layout of fedm_residual.  Returns what the solver
  * returns (0, FEDM_DIVERGED_LINEAR, FEDM_DIVERGED_NAN); its / rnorm: its step count and the residual norm it reports
- * (on the left: of the preconditioned residual). */
+ * (on the left: of the preconditioned residual M^-1 r; on the right: of the true residual, |b - J x|_2 -- and with
+ * fedm_set_krylov_scaling "rows" the row-equilibrated |D (b - J x)|_2, tested against max(ksp_rtol |D b|_2, ksp_atol)). */
 int fedm_debug_linear_solve(fedm_ctx *ctx, const double *b, const fedm_newton_opts *opts, double *x, int *its,
                             double *rnorm);
 /* F as the last assembly left it (residual-only or F + J: no evaluation), caller-side layout as fedm_residual's. */
@@ -533,8 +535,28 @@ int fedm_set_preconditioner_side(fedm_ctx *ctx, int right);
  *       library's test) is dominated by the species rows and does not see the Poisson row.  2x
  *       faster late in a run, 4e-3 instead of 6e-6 deviation from a tightly solved run after 220
  *       steps of the bench case (tools/fs_order_accuracy.py): an explicit trade, not the default.
+ *       With fedm_set_krylov_scaling "rows" this caveat no longer holds: the equilibrated norm sees the
+ *       Poisson rows, and return code 0 means the same accuracy whatever the order.
  * Takes effect with the next Jacobian assembly.  Environment: FEDM_FS_ORDER=lower|upper. */
 int fedm_set_fieldsplit_order(fedm_ctx *ctx, int upper);
+/* Row-equilibrated residual test of the Newton linear solves (PETSc: KSPSetDiagonalScale).  The systems couple species
+ * rows of size ~1e15 with a Poisson row of size ~0.1, so |b - J x|_2 sees the species rows only.
+ *   mode 0 = none (default): the test is on |b - J x|_2, as before, bit for bit.
+ *   mode 1 = rows: for the DOF i = (vertex v, component r), s_i = sqrt(sum_c J[(v,r),(v,c)]^2) over row r of the
+ *       vertex's n_eq x n_eq diagonal block, d_i = 1 / s_i, and d_i = 1 where s_i is zero or not finite (identity
+ *       rows -- Dirichlet, outermost ghost layer -- get exactly 1).  Flexible GMRES then minimises and tests
+ *       |D (b - J x)|_2 against max(ksp_rtol |D b|_2, ksp_atol); the preconditioner is unchanged.  It runs in the inner
+ *       product <x, y> = sum_i d_i^2 x_i y_i (the iterates of GMRES on D J M^-1 D^-1): only the reductions change.
+ *       d is not normalised (ksp_atol is compared with |D r|_2 for this d) and is recomputed from the Jacobian at the
+ *       start of every scaled solve.  The residual norms a solve reports (fedm_debug_linear_solve's rnorm) are the
+ *       scaled ones; the Newton loop's own test stays on the unscaled |F| (fedm_newton_report.fnorm0 / fnorm).
+ * Other values are refused.  Defined for the field split on the right (one GPU and several): a solve started with
+ * mode 1 under point-block Jacobi or with the field split on the left returns a hard error (< 0), it does not
+ * ignore the setting -- there the tested residual M^-1 r is equilibrated already. */
+int fedm_set_krylov_scaling(fedm_ctx *ctx, int mode);
+/* mode (unless NULL) and, unless NULL, d_out[n_vertices * n_eq] in the caller-side layout of fedm_residual: the d of
+ * the Jacobian as it stands, i.e. what a scaled solve started now uses (whatever the mode). */
+int fedm_get_krylov_scaling(fedm_ctx *ctx, int *mode, double *d_out);
 /* value planes of the Jacobian blocks (bit r * n_eq + c = d(row r)/d(unknown c)) that the assembly
  * keeps between assemblies (constant or structurally zero: not recomputed, not written again) and
  * that the Jacobian SpMV skips (structurally zero: no reaction couples the two species): the bytes
