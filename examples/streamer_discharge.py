@@ -188,7 +188,7 @@ def quiet_stdout(quiet):
 
 
 def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_dir=None, output_dir=None,
-         quiet=False, stop_before_device=None):
+         quiet=False, stop_before_device=None, coupling="coupled"):
     """Runs the case; returns (state as (n_vertices, 3) array of ln n_i, ln n_e, Phi; error-log path)."""
     case = Case() if end_time is None else Case(end_time=end_time)
     fem.parameters["form_compiler"]["quadrature_degree"] = 2
@@ -228,6 +228,7 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
     newton.parameters["relative_tolerance"] = case.newton_rtol
     newton.parameters["maximum_iterations"] = case.newton_max_it
     newton.parameters["linear_solver"] = "gmres"
+    newton.parameters["coupling"] = coupling             # "uncoupled": Poisson solve, then Newton on the species alone
 
     # what file_output interpolates between: potential first, then the species
     order = [deck["n_equations"] - 1] + list(range(deck["n_species"]))
@@ -264,7 +265,9 @@ if __name__ == "__main__":
     ap.add_argument("--mesh", help="DOLFIN XML mesh to load instead of generating one")
     ap.add_argument("--end", type=float, default=1e-10, help="end time [s] (the reference script: 1.4e-8)")
     ap.add_argument("--out", default="streamer_output")
+    ap.add_argument("--coupling", choices=["coupled", "uncoupled"], default="coupled",
+                    help="one Newton solve on the mixed space, or the segregated step")
     a = ap.parse_args()
     state, log_path = main(cells=a.cells, mesh_spacing=a.mesh_spacing, mesh_file=a.mesh, end_time=a.end,
-                           output_dir=a.out)
+                           output_dir=a.out, coupling=a.coupling)
     print(open(log_path).read())

@@ -148,6 +148,12 @@ _SIGNATURES = {
     "fedm_spmv": (C.c_int, [_P, _D, _D]),
     "fedm_newton_solve": (C.c_int, [_P, C.POINTER(NewtonOpts), C.POINTER(NewtonReport)]),
     "fedm_poisson_solve": (C.c_int, [_P, C.c_double, C.c_int, C.POINTER(C.c_int)]),
+    "fedm_poisson_update": (C.c_int, [_P, C.c_double, C.c_int, C.POINTER(C.c_int)]),
+    "fedm_newton_solve_species": (C.c_int, [_P, C.POINTER(NewtonOpts), C.POINTER(NewtonReport)]),
+    "fedm_segregated_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
+    "fedm_debug_species_assembly": (C.c_int, [_P, C.c_int]),
+    "fedm_debug_block_product": (C.c_int, [_P, C.c_int, _D, _D]),
+    "fedm_debug_species_linear_solve": (C.c_int, [_P, _D, C.POINTER(NewtonOpts), _D, C.POINTER(C.c_int), _D]),
     "fedm_block_nnz": (C.c_int64, [_P]),
     "fedm_block_csr": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _D]),
     "fedm_jacobian_poisson_only": (C.c_int, [_P]),

@@ -166,7 +166,8 @@ class Stepper:
         return getattr(self.prob, "multigrid_levels", None)
 
     def __init__(self, prob, dt_init=5e-12, dt_max=5e-12, dt_min=1e-15, ttol=1e-3,
-                 relative_tolerance=1e-4, maximum_iterations=20, error_file=None, quiet=True):
+                 relative_tolerance=1e-4, maximum_iterations=20, error_file=None, quiet=True,
+                 coupling="coupled"):
         import tempfile
         from .. import functions as ff
         from ..forms import DeviceState, Expression, FunctionAssigner
@@ -174,6 +175,7 @@ class Stepper:
         self.solver = ff.PETScSNESSolver()
         self.solver.parameters["relative_tolerance"] = relative_tolerance
         self.solver.parameters["maximum_iterations"] = maximum_iterations
+        self.solver.parameters["coupling"] = coupling      # "uncoupled": the segregated step (PETScSNESSolver)
         self.problem = ff.Problem(None, None, [], device_problem=prob)
         self.dt = Expression("time_step", time_step=dt_init, degree=0)
         self.dt_old = Expression("time_step", time_step=1e30, degree=0)

@@ -50,6 +50,19 @@ namespace fedm {
 #define LEAN3_ADD(ptr, v) unsafeAtomicAdd(ptr, v)
 #endif
 
+// Bit 31 of a CMASK: the species-only instantiation (fedm_newton_solve_species, the segregated step).  The Poisson row is
+// not evaluated at all -- its residual stays the 0 the accumulator was set to -- and the mask's low bits name every plane
+// of the potential row and of the potential column besides, so none of them is accumulated, kept in LDS or streamed
+// out: the accumulators are the species-species planes alone.  LivePlanes reads the low bits only.
+constexpr uint32_t LEAN3_SPECIES_ONLY = 1u << 31;
+template <int NS>
+constexpr uint32_t lean3_species_mask() {
+    constexpr int NEQ = NS + 1;
+    uint32_t m = LEAN3_SPECIES_ONLY;
+    for (int k = 0; k < NEQ; ++k) m |= (1u << (NS * NEQ + k)) | (1u << (k * NEQ + NS));
+    return m;
+}
+
 // Planes of the (row, col) block that are accumulated and streamed out: those NOT in CMASK, numbered in
 // row-major order.
 template <int NS, uint32_t CMASK>
@@ -559,7 +572,7 @@ __device__ __forceinline__ void lean3_cell(const Lean3Plan<NS, NR> *__restrict__
         return;
     }
     lean3_species_rows<NS, NR, CMASK, JAC, 0, SIG>(md, c, Ul, Hl, sc, dst, Fl, lds_base);
-    lean3_poisson_row<NS, NR, CMASK, JAC>(md, c, dst, Fl, lds_base);
+    if constexpr (!(CMASK & LEAN3_SPECIES_ONLY)) lean3_poisson_row<NS, NR, CMASK, JAC>(md, c, dst, Fl, lds_base);
 }
 
 // The field split's set-up (amg.hip, species_planes_kernel) from the patch's accumulators instead of from the matrix
@@ -951,6 +964,26 @@ template <int NS, int NR, int THREADS, class SIG>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(FEDM_RES3_WAVES, FEDM_RES3_WAVES))) void residual_lean3_kernel(
     const Lean3Plan<NS, NR> *__restrict__ plan, const Lean3Params p) {
     assemble_lean3_body<NS, NR, THREADS, 0u, false, SIG>(plan, p);
+}
+
+// The species-only pair (LEAN3_SPECIES_ONLY).  Four live planes of nine and no Poisson row: LDS and registers for four
+// waves per SIMD in the Jacobian kernel too (five workgroups a CU where the LDS allows, against three) with the
+// model's structure compiled in; with the run-time structure four waves would spill two registers, so that one stays
+// at the coupled kernel's three.
+#ifndef FEDM_LEAN3S_WAVES
+#define FEDM_LEAN3S_WAVES 4
+#endif
+template <int NS, int NR, int THREADS, uint32_t CMASK, class SIG>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(SIG::fixed ? FEDM_LEAN3S_WAVES : FEDM_LEAN3_WAVES, SIG::fixed ? FEDM_LEAN3S_WAVES : FEDM_LEAN3_WAVES))) void assemble_lean3s_kernel(
+    const Lean3Plan<NS, NR> *__restrict__ plan, const Lean3Params p) {
+    static_assert((CMASK & LEAN3_SPECIES_ONLY) != 0u, "the species-only kernel");
+    assemble_lean3_body<NS, NR, THREADS, CMASK, true, SIG>(plan, p);
+}
+
+template <int NS, int NR, int THREADS, class SIG>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(FEDM_RES3_WAVES, FEDM_RES3_WAVES))) void residual_lean3s_kernel(
+    const Lean3Plan<NS, NR> *__restrict__ plan, const Lean3Params p) {
+    assemble_lean3_body<NS, NR, THREADS, LEAN3_SPECIES_ONLY, false, SIG>(plan, p);
 }
 
 // fedm_model_desc -> Lean3Plan.  false: the model's coefficient functions do not fit the plan's form.
@@ -1355,6 +1388,66 @@ static int lean3_live_planes(uint32_t cmask) {
 bool lean3_fits(const Ctx &c, bool jacobian, uint32_t cmask) {
     const int planes = jacobian ? lean3_live_planes(cmask) : 0;
     return lean3_lds_bytes(c.neq, c.ns, c.pat.max_patch_width, c.pat.max_patch_verts, planes, jacobian) <= 160 * 1024;
+}
+
+// The species-only assembly of the whole mesh in one launch (one GPU).  The planes it does not write stay as they are
+// in the matrix: the potential-potential plane stays valid for later coupled assemblies, and Ctx::const_planes_valid is
+// not touched, so a context's first coupled Jacobian still writes all nine planes.
+template <class SIG>
+static bool lean3_launch_species(Ctx &c, bool jacobian) {
+    constexpr int NS = 2, NR = 1, T = 192;
+    constexpr uint32_t CMASK = lean3_species_mask<NS>();
+    using PL = LivePlanes<NS, CMASK>;
+    static_assert(PL::N == NS * NS, "the species-species planes");
+    const Lean3Plan<NS, NR> *plan = static_cast<const Lean3Plan<NS, NR> *>(c.d_lean3_plan);
+    const int width = c.pat.max_patch_width, verts = c.pat.max_patch_verts, n = c.pat.n_slices;
+    Lean3Params p;
+    p.nv = c.nv;
+    p.boff = c.d_slice_boff;
+    p.cell_ptr = c.d_patch_cell_ptr;
+    p.pcells = c.d_patch_cells;
+    p.halo_ptr = c.d_patch_halo_ptr;
+    p.halo = c.d_patch_halo;
+    p.coords = c.d_coords;
+    p.u = c.d_u;
+    p.uold = c.d_uold;
+    p.uold1 = c.d_uold1;
+    p.sc = step_coef(c.dt, c.dt_old);
+    p.val = c.d_val;
+    p.F = c.d_F;
+    p.acc_doubles = jacobian ? width * PL::N * SLICE : 0;
+    p.max_verts = verts;
+    p.xcd = c.xcd_remap ? 1 : 0;
+    p.patch_list = nullptr;
+    p.n_patches = n;
+    p.s16 = nullptr;
+    p.val32 = nullptr;
+    p.dinv = nullptr;
+    p.diag_slot = nullptr;
+    p.planes_upper = 0;
+    p.planes_zs = 0u;
+    const size_t lds = lean3_lds_bytes(c.neq, c.ns, width, verts, PL::N, jacobian);
+    if (lds > 160 * 1024) return false;
+    if (jacobian) {
+        static size_t granted = 0;
+        if (lds > 64 * 1024 && lds > granted) {
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&assemble_lean3s_kernel<NS, NR, T, CMASK, SIG>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            granted = lds;
+        }
+        lean3_dispatch(c, true, assemble_lean3s_kernel<NS, NR, T, CMASK, SIG>, n, T, lds, plan, p);
+    } else {
+        lean3_dispatch(c, true, residual_lean3s_kernel<NS, NR, T, SIG>, n, T, lds, plan, p);
+    }
+    note_assembly_launch(c, jacobian, 3, T, n);
+    return true;
+}
+
+bool launch_assemble_lean3_species(Ctx &c, bool jacobian) {
+    if (c.comm || c.n_owned != c.nv || c.pat.n_slices <= 0 || !lean3_applies(c)) return false;
+    if (!lean3_ensure_plan<2, 1>(c)) return false;
+    if (c.lean3_sig == 1) return lean3_launch_species<Lean3SigBenchmark>(c, jacobian);
+    return lean3_launch_species<Lean3SigRuntime>(c, jacobian);
 }
 
 // cmask: the planes that are kept for this launch (0 on a context's first full assembly: everything is written).

@@ -1485,6 +1485,7 @@ void fedm_ctx_destroy(fedm_ctx *h) {
     if (c.d_kscale2) hipFree(c.d_kscale2);
     if (c.h_stage) hipHostFree(c.h_stage);
     if (c.d_snapshot) hipFree(c.d_snapshot);
+    if (c.d_seg_dinv) hipFree(c.d_seg_dinv);
     lean3_release(c);
     for (int s_ = 0; s_ < FEDM_MAX_SPECIES; ++s_) {
         if (c.d_expr_ops[s_]) hipFree(c.d_expr_ops[s_]);
@@ -1975,6 +1976,388 @@ int fedm_poisson_solve(fedm_ctx *h, double rtol, int max_it, int *iterations) {
     return rn <= rtol * r0 || r0 == 0.0 ? 0 : FEDM_DIVERGED_LINEAR;
 }
 
+// ---- segregated (uncoupled) step ---------------------------------------------------------------
+// Refusals shared by the two stages: nothing is launched.
+static int segregated_refusal(Ctx &c, const char *who, bool species) {
+    if (c.model_kind != 0) {
+        set_error(std::string(who) + ": the LMEA family has no segregated step (LFA models with a Poisson row only)");
+        return -2;
+    }
+    if (!c.poisson) {
+        set_error("model has no Poisson row");
+        return -2;
+    }
+    if (c.comm || c.n_owned != c.nv) {
+        set_error(std::string(who) + ": the segregated step runs on one GPU (this context has a transport or ghost vertices)");
+        return -2;
+    }
+    if (species && c.krylov_scaling != 0) {
+        set_error(std::string(who) + ": krylov scaling 'rows' is not defined for the species block (its own equilibration "
+                  "is not implemented): set the krylov scaling to 'none'");
+        return -2;
+    }
+    if (species && c.amg && !c.right_precond) {
+        set_error(std::string(who) + ": the species solve is flexible GMRES with its preconditioner on the right; this "
+                  "context has the field split on the left: set the preconditioner side to 'right'");
+        return -2;
+    }
+    return 0;
+}
+
+enum SegStat { SG_UPDATES = 0, SG_CG_ITS, SG_SOLVES, SG_ONE_PASS, SG_FALLBACK, SG_NEWTON_ITS, SG_KRYLOV_STEPS };
+
+static int ensure_seg_dinv(Ctx &c) {
+    if (c.d_seg_dinv) return 0;
+    FEDM_HIP_CHECK(hipMalloc((void **)&c.d_seg_dinv, sizeof(double) * (size_t)c.nvp * c.ns * c.ns));
+    return 0;
+}
+
+// z = M^-1 v on the species block: the Richardson sweeps z += w_k Duu^-1 (v - J_uu z) from z = 0 with the weights of
+// fedm_set_fieldsplit (one sweep of weight 1 when none is installed: point-block Jacobi).  c.d_tmp is scratch.
+static void species_precondition(Ctx &c, const double *v, double *z) {
+    launch_species_sweep(c, c.fs_main_w[0], v, nullptr, z, true);
+    for (int k = 1; k < c.fs_main_sweeps; ++k) {
+        launch_block_product(c, 0, z, c.d_tmp);
+        launch_species_sweep(c, c.fs_main_w[k], v, c.d_tmp, z, false);
+    }
+}
+
+// Flexible GMRES(restart) on J_uu delta_u = -F_u (F in c.d_F with zeros on the potential entries; delta in c.d_delta,
+// zeros there too).  Classical Gram-Schmidt, two passes.  The recurrence's norm ends a cycle; success is reported only
+// for a true residual |F_u + J_uu delta_u| <= max(rtol |F_u|, atol), formed in double precision at the top of the
+// next cycle.  A cycle entered on such a check that does not halve the true residual gives up.
+static int species_gmres(Ctx &c, int restart, double rtol, double atol, int max_it, double bnorm, int *its_out,
+                         double *rnorm_out) {
+    if (restart < 1 || restart > RED_K - 10) {
+        set_error("GMRES restart must be between 1 and 30");
+        return -2;
+    }
+    if (ensure_krylov(c, restart)) return -1;
+    const int m = restart;
+    std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), gvec(m + 1), yv(m), hcol(m + 1);
+    std::vector<const double *> vp(m + 1), zp(m);
+    for (int i = 0; i <= m; ++i) vp[i] = c.d_V + (size_t)i * c.np;
+    for (int i = 0; i < m; ++i) zp[i] = c.d_Z + (size_t)i * c.np;
+    hipMemsetAsync(c.d_delta, 0, sizeof(double) * c.np, c.stream);
+    const double tol = std::max(rtol * bnorm, atol);
+    int its = 0;
+    double rnorm = bnorm, verified_prev = -1.0;
+    *its_out = 0;
+    *rnorm_out = bnorm;
+    if (bnorm <= tol) return 0;
+    bool first = true, checking = false;
+    while (true) {
+        double *v0 = c.d_V;
+        double beta = bnorm;
+        if (first) {
+            launch_scale_copy(c, -1.0 / beta, c.d_F, v0);
+            first = false;
+        } else {
+            launch_block_product(c, 0, c.d_delta, c.d_w);
+            launch_scale_copy(c, -1.0, c.d_F, v0);
+            launch_axpy(c, -1.0, c.d_w, v0);
+            launch_norm2(c, v0, 0);
+            read_red(c, 1);
+            beta = std::sqrt(c.h_red[0]);
+            rnorm = beta;
+            if (!std::isfinite(beta)) {
+                c.seg_stats[SG_KRYLOV_STEPS] += its;
+                *its_out = its;
+                *rnorm_out = beta;
+                return FEDM_DIVERGED_NAN;
+            }
+            if (beta <= tol) break;
+            if (checking) {
+                checking = false;
+                if (verified_prev >= 0.0 && beta > 0.5 * verified_prev) break;   // the arithmetic's floor is above tol
+                verified_prev = beta;
+            }
+            if (its >= max_it) break;
+            launch_scale_copy(c, 1.0 / beta, v0, v0);
+        }
+        std::fill(gvec.begin(), gvec.end(), 0.0);
+        gvec[0] = beta;
+        int j = 0;
+        bool done = false;
+        for (; j < m && its < max_it; ++j) {
+            double *z = c.d_Z + (size_t)j * c.np, *w = c.d_V + (size_t)(j + 1) * c.np;
+            species_precondition(c, vp[j], z);
+            launch_block_product(c, 0, z, w);
+            for (int i = 0; i <= j; ++i) hcol[i] = 0.0;
+            for (int pass = 0; pass < 2; ++pass) {
+                launch_dots(c, vp.data(), w, j + 1, false);
+                read_red(c, j + 1);
+                for (int i = 0; i <= j; ++i) hcol[i] += c.h_red[i];
+                launch_multi_axpy(c, c.h_red, j + 1, vp.data(), w, -1.0);
+            }
+            launch_norm2(c, w, 0);
+            read_red(c, 1);
+            const double hn = std::sqrt(c.h_red[0]);
+            if (!std::isfinite(hn)) {
+                c.seg_stats[SG_KRYLOV_STEPS] += its + 1;
+                *its_out = its;
+                *rnorm_out = hn;
+                return FEDM_DIVERGED_NAN;
+            }
+            if (hn > 0.0) launch_scale_copy(c, 1.0 / hn, w, w);
+            for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] = hcol[i];
+            H[(size_t)(j + 1) * m + j] = hn;
+            for (int i = 0; i < j; ++i) {
+                const double t = cs[i] * H[(size_t)i * m + j] + sn[i] * H[(size_t)(i + 1) * m + j];
+                H[(size_t)(i + 1) * m + j] = -sn[i] * H[(size_t)i * m + j] + cs[i] * H[(size_t)(i + 1) * m + j];
+                H[(size_t)i * m + j] = t;
+            }
+            const double a = H[(size_t)j * m + j], b = H[(size_t)(j + 1) * m + j];
+            const double d = std::hypot(a, b);
+            cs[j] = d > 0.0 ? a / d : 1.0;
+            sn[j] = d > 0.0 ? b / d : 0.0;
+            H[(size_t)j * m + j] = d;
+            H[(size_t)(j + 1) * m + j] = 0.0;
+            gvec[j + 1] = -sn[j] * gvec[j];
+            gvec[j] = cs[j] * gvec[j];
+            ++its;
+            rnorm = std::fabs(gvec[j + 1]);
+            if (rnorm <= tol || hn == 0.0) {
+                ++j;
+                done = true;
+                break;
+            }
+        }
+        const int k = j;
+        for (int i = k - 1; i >= 0; --i) {
+            double s = gvec[i];
+            for (int l = i + 1; l < k; ++l) s -= H[(size_t)i * m + l] * yv[l];
+            yv[i] = s / H[(size_t)i * m + i];
+        }
+        if (k > 0) launch_multi_axpy(c, yv.data(), k, zp.data(), c.d_delta, 1.0);
+        checking = done;   // the recurrence says converged: the loop's top looks at the true residual
+    }
+    c.seg_stats[SG_KRYLOV_STEPS] += its;
+    *its_out = its;
+    *rnorm_out = rnorm;
+    return rnorm <= tol ? 0 : FEDM_DIVERGED_LINEAR;
+}
+
+int fedm_newton_solve_species(fedm_ctx *h, const fedm_newton_opts *o, fedm_newton_report *rep) {
+    if (!h || !o) {
+        set_error("fedm_newton_solve_species: null argument");
+        return -2;
+    }
+    Ctx &c = h->c;
+    if (const int refused = segregated_refusal(c, "fedm_newton_solve_species", true)) return refused;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    if (ensure_seg_dinv(c)) return -1;
+    c.err_cache_comp = -1;
+    ++c.seg_stats[SG_SOLVES];
+    fedm_newton_report r{};
+    int it = 0, lin_total = 0, rc = 0;
+    double fnorm = 0.0, fnorm0 = 0.0, snorm = 0.0, xnorm = 0.0;
+    while (true) {
+        // F_u and J_uu in one pass; |F_u| decides (the potential entries of F are zeros).  The iteration at which the
+        // previous solve converged is expected to be the final check again: the residual-only twin there (a wrong
+        // guess costs the F + J assembly after all), as the coupled loop does.
+        const bool residual_only = it > 0 && it == c.seg_newton_its_hint;
+        const bool one_pass = launch_assemble_species(c, !residual_only);
+        ++c.seg_stats[one_pass ? SG_ONE_PASS : SG_FALLBACK];
+        launch_norm2(c, c.d_F, 0);
+        read_red(c, 1);
+        fnorm = std::sqrt(c.h_red[0]);
+        if (!std::isfinite(fnorm)) {
+            rc = FEDM_DIVERGED_NAN;
+            break;
+        }
+        const bool done = it == 0 ? fnorm < o->atol
+                                  : (fnorm < o->atol || fnorm <= o->rtol * fnorm0 || snorm < o->stol * xnorm);
+        if (it == 0) fnorm0 = fnorm;
+        if (done) break;
+        if (it >= o->max_it) {
+            rc = FEDM_DIVERGED_MAX_IT;
+            break;
+        }
+        if (residual_only) {   // not converged after all: the Jacobian is needed
+            const bool again = launch_assemble_species(c, true);
+            ++c.seg_stats[again ? SG_ONE_PASS : SG_FALLBACK];
+        }
+        launch_species_block_inverse(c);
+        int lits = 0;
+        double lres = 0.0;
+        const int lrc = species_gmres(c, o->ksp_restart, o->ksp_rtol, o->ksp_atol, o->ksp_max_it, fnorm, &lits, &lres);
+        lin_total += lits;
+        if (lrc != 0) {
+            rc = lrc < 0 ? lrc : (lrc == FEDM_DIVERGED_NAN ? FEDM_DIVERGED_NAN : FEDM_DIVERGED_LINEAR);
+            break;
+        }
+        // u_u += delta_u (delta's potential entries are exact zeros: u_phi keeps its bits); |delta_u|, |u_u| for stol
+        launch_axpy(c, 1.0, c.d_delta, c.d_u);
+        launch_pick_entries(c, 0, 1.0, c.d_u, c.d_w);
+        launch_norm2(c, c.d_delta, 1);
+        launch_norm2(c, c.d_w, 2);
+        read_red(c, 3);
+        snorm = std::sqrt(c.h_red[1]);
+        xnorm = std::sqrt(c.h_red[2]);
+        ++it;
+    }
+    c.seg_stats[SG_NEWTON_ITS] += it;
+    if (rc == 0) c.seg_newton_its_hint = it;
+    r.iterations = it;
+    r.linear_iterations = lin_total;
+    r.fnorm0 = fnorm0;
+    r.fnorm = fnorm;
+    r.reason = rc > 0 ? rc : 0;
+    r.converged = rc == 0 ? 1 : 0;
+    if (rep) *rep = r;
+    if (hipStreamSynchronize(c.stream) != hipSuccess || hipGetLastError() != hipSuccess) {
+        set_error("HIP error during the species Newton solve");
+        return -1;
+    }
+    return rc;
+}
+
+// The potential stage of the segregated step.  The Poisson rows are linear in the potential, F_phi(u_u, phi) =
+// A phi - b(u_u), so one correction A dphi = -F_phi solves them; A = the potential-potential planes as they stand.
+// Dirichlet rows: the state takes the boundary values first, their residual is then zero and every CG vector is zero
+// there, so the iteration runs on the symmetric positive definite remainder (as fedm_poisson_solve's does).
+int fedm_poisson_update(fedm_ctx *h, double rtol, int max_it, int *iterations) {
+    if (!h) {
+        set_error("fedm_poisson_update: null argument");
+        return -2;
+    }
+    Ctx &c = h->c;
+    if (iterations) *iterations = 0;
+    if (const int refused = segregated_refusal(c, "fedm_poisson_update", false)) return refused;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    c.err_cache_comp = -1;
+    ++c.seg_stats[SG_UPDATES];
+    launch_set_dirichlet_state(c);
+    if (!c.const_planes_valid && !c.seg_jacobian_done) {
+        eval_jacobian(c, 0);   // the context's first Jacobian: writes every plane, the potential-potential one included
+        c.seg_jacobian_done = true;
+    } else {
+        launch_assemble(c, false, 0);
+        launch_finalize(c, false, 0);
+    }
+    double *r = c.d_rhs, *z = c.d_tmp, *p = c.d_delta, *q = c.d_w;
+    launch_pick_entries(c, 1, -1.0, c.d_F, r);   // r = -F_phi, zeros on the species entries
+    auto precondition = [&](const double *rr, double *zz) {
+        if (c.amg) poisson_precondition(c, *c.amg, rr, zz);
+        else launch_potential_jacobi(c, rr, zz);
+    };
+    precondition(r, z);
+    launch_scale_copy(c, 1.0, z, p);
+    const double *rz_ptr[1] = {r};
+    launch_dots(c, rz_ptr, z, 1);
+    launch_norm2(c, r, 1);
+    read_red(c, 2);
+    double rz = c.h_red[0];
+    const double r0 = std::sqrt(c.h_red[1]);
+    double rn = r0;
+    int it = 0;
+    if (ensure_krylov(c, 1)) return -1;
+    double *x = c.d_V;
+    hipMemsetAsync(x, 0, sizeof(double) * c.np, c.stream);
+    while (std::isfinite(rn) && rn > rtol * r0 && it < max_it) {
+        launch_block_product(c, 1, p, q);
+        const double *pp[1] = {p};
+        launch_dots(c, pp, q, 1);
+        read_red(c, 1);
+        const double alpha = rz / c.h_red[0];
+        launch_axpy(c, alpha, p, x);
+        launch_axpy(c, -alpha, q, r);
+        precondition(r, z);
+        launch_dots(c, rz_ptr, z, 1);
+        launch_norm2(c, r, 1);
+        read_red(c, 2);
+        const double rz_new = c.h_red[0];
+        rn = std::sqrt(c.h_red[1]);
+        if (!std::isfinite(rn)) break;
+        const double beta = rz_new / rz;
+        rz = rz_new;
+        launch_scale_copy(c, beta, p, p);
+        launch_axpy(c, 1.0, z, p);
+        ++it;
+    }
+    // x has exact zeros on the species entries: they keep their bits
+    if (std::isfinite(rn)) launch_axpy(c, 1.0, x, c.d_u);
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    FEDM_HIP_CHECK(hipGetLastError());
+    c.seg_stats[SG_CG_ITS] += it;
+    if (iterations) *iterations = it;
+    if (!std::isfinite(rn)) return FEDM_DIVERGED_NAN;
+    return rn <= rtol * r0 ? 0 : FEDM_DIVERGED_LINEAR;
+}
+
+int fedm_debug_species_linear_solve(fedm_ctx *h, const double *b, const fedm_newton_opts *o, double *x, int *its,
+                                    double *rnorm) {
+    if (!h || !b || !o || !x) {
+        set_error("fedm_debug_species_linear_solve: null argument");
+        return -2;
+    }
+    Ctx &c = h->c;
+    if (const int refused = segregated_refusal(c, "fedm_debug_species_linear_solve", true)) return refused;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    if (ensure_seg_dinv(c)) return -1;
+    FEDM_HIP_CHECK(hipMemsetAsync(c.d_w, 0, sizeof(double) * c.np, c.stream));
+    if (put_vec(c, c.d_w, b)) return -1;
+    launch_pick_entries(c, 0, -1.0, c.d_w, c.d_F);   // species_gmres solves J_uu delta = -F
+    launch_norm2(c, c.d_F, 0);
+    read_red(c, 1);
+    const double bnorm = std::sqrt(c.h_red[0]);
+    int lits = 0;
+    double lres = bnorm;
+    int rc = FEDM_DIVERGED_NAN;
+    if (std::isfinite(bnorm)) {
+        launch_species_block_inverse(c);
+        rc = species_gmres(c, o->ksp_restart, o->ksp_rtol, o->ksp_atol, o->ksp_max_it, bnorm, &lits, &lres);
+    }
+    if (its) *its = lits;
+    if (rnorm) *rnorm = lres;
+    if (rc < 0) return rc;
+    if (get_vec(c, x, c.d_delta)) return -1;
+    return rc;
+}
+
+int fedm_debug_species_assembly(fedm_ctx *h, int jacobian) {
+    if (!h) {
+        set_error("fedm_debug_species_assembly: null argument");
+        return -2;
+    }
+    Ctx &c = h->c;
+    if (const int refused = segregated_refusal(c, "fedm_debug_species_assembly", false)) return refused;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    const bool one_pass = launch_assemble_species(c, jacobian != 0);
+    ++c.seg_stats[one_pass ? SG_ONE_PASS : SG_FALLBACK];
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    FEDM_HIP_CHECK(hipGetLastError());
+    return one_pass ? 1 : 0;
+}
+
+int fedm_debug_block_product(fedm_ctx *h, int which, const double *x, double *y) {
+    if (!h || !x || !y || (which != 0 && which != 1)) {
+        set_error("fedm_debug_block_product: null argument, or a block other than 0 (species) and 1 (potential)");
+        return -2;
+    }
+    Ctx &c = h->c;
+    if (const int refused = segregated_refusal(c, "fedm_debug_block_product", false)) return refused;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipMemsetAsync(c.d_tmp, 0, sizeof(double) * c.np, c.stream));
+    if (put_vec(c, c.d_tmp, x)) return -1;
+    launch_block_product(c, which, c.d_tmp, c.d_w);
+    return get_vec(c, y, c.d_w);
+}
+
+int fedm_segregated_stats(fedm_ctx *h, int64_t out[8], int reset) {
+    if (!h || (!out && !reset)) {
+        set_error("fedm_segregated_stats: null argument");
+        return -2;
+    }
+    Ctx &c = h->c;
+    if (out)
+        for (int i = 0; i < 8; ++i) out[i] = c.seg_stats[i];
+    if (reset)
+        for (int i = 0; i < 8; ++i) c.seg_stats[i] = 0;
+    return 0;
+}
+
 int fedm_field_error(fedm_ctx *h, int component, double *rel_err) {
     Ctx &c = h->c;
     if (component < 0 || component >= c.neq) {
@@ -2009,6 +2392,7 @@ int fedm_debug_species_planes_check(fedm_ctx *h, double *out) {
 
 int fedm_time_kernel(fedm_ctx *h, int kind, int repeats, double *ms_per_launch) {
     Ctx &c = h->c;
+    if (kind == 6 && segregated_refusal(c, "fedm_time_kernel", false)) return -2;
     FEDM_HIP_CHECK(hipSetDevice(c.device));
     hipEvent_t e0, e1;
     FEDM_HIP_CHECK(hipEventCreate(&e0));
@@ -2026,8 +2410,10 @@ int fedm_time_kernel(fedm_ctx *h, int kind, int repeats, double *ms_per_launch) 
             launch_assemble(c, true, 0);                   // ... behind the assembly, as in a Newton iteration
             c.boundary_pending = 0;
             if (c.amg && c.poisson) fieldsplit_setup(c);
+        } else if (kind == 6) {
+            launch_assemble_species(c, true, true);        // the volume kernel alone, as kind 0 times the coupled one
         } else {
-            launch_assemble(c, false, 0);
+            launch_assemble(c, false, 0);                  // (kinds 2 and 7: fedm_poisson_update's right-hand side is this assembly)
         }
     };
     run();  // warm-up

@@ -266,6 +266,12 @@ struct Ctx {
     int launched[2][4] = {{-1, 0, 0, 0}, {-1, 0, 0, 0}};
     // which branches of gmres() and fedm_newton_solve ran (fedm_solver_path_stats; indices PS_*): host counters only
     int64_t path_stats[24] = {};
+    // segregated step (fedm_poisson_update, fedm_newton_solve_species): counters in fedm_segregated_stats' order and the
+    // inverses of the n_species x n_species diagonal blocks, sliced like d_dinv (allocated on first use)
+    int64_t seg_stats[8] = {};
+    double *d_seg_dinv = nullptr;
+    int seg_newton_its_hint = -1;     // Newton iterations of the previous converged species solve (its final check is residual-only)
+    bool seg_jacobian_done = false;   // fedm_poisson_update has assembled a Jacobian itself (contexts whose assembly never sets const_planes_valid)
 };
 
 // Indices of Ctx::path_stats, in the order fedm_solver_path_stats documents (include/fedm_hip.h)
@@ -321,6 +327,21 @@ bool lean3_applies(const Ctx &c);                                   // assemble3
 void lean3_release(Ctx &c);
 bool launch_assemble_lean3(Ctx &c, bool jacobian, const int *patch_list, int n, uint32_t cmask);
 bool lean3_fits(const Ctx &c, bool jacobian, uint32_t cmask);       // its LDS for these kept planes fits the device
+// species-only one-pass assembly of the whole mesh (no Poisson row, no plane of the potential row or column); false:
+// it does not apply here or does not fit, nothing was launched
+bool launch_assemble_lean3_species(Ctx &c, bool jacobian);
+// volume + boundary + Dirichlet / padding rows of the species equations, F of the potential rows zeroed (kernels.hip).
+// Returns true when the species-only one-pass kernel ran, false when the full assembly did.  volume_only: the volume
+// kernel alone (fedm_time_kernel; the caller clears Ctx::boundary_pending).
+bool launch_assemble_species(Ctx &c, bool jacobian, bool volume_only = false);
+// segregated.hip.  which = 0: y_u = J_uu x_u, y_phi = 0; which = 1: y_phi = J_phiphi x_phi, y_u = 0
+void launch_block_product(Ctx &c, int which, const double *x, double *y);
+void launch_species_block_inverse(Ctx &c);                          // c.d_seg_dinv from the diagonal blocks
+// z_u = (first ? 0 : z_u) + w Duu^-1 (r_u - (first ? 0 : t_u)), z_phi = 0
+void launch_species_sweep(Ctx &c, double w, const double *r, const double *t, double *z, bool first);
+void launch_potential_jacobi(Ctx &c, const double *r, double *z);   // z_phi = r_phi / diag(J_phiphi), z_u = 0
+// y = a x on the species entries (which = 0) or the potential entries (which = 1), 0 on the others
+void launch_pick_entries(Ctx &c, int which, double a, const double *x, double *y);
 // the volume assembly of the next full-model residual (jacobian = false) or Jacobian: variant as fedm_pattern_info's,
 // threads per workgroup (kernels.hip; assemble_patch_t dispatches with the same conditions)
 int assembly_prediction(const Ctx &c, bool jacobian, int *threads);

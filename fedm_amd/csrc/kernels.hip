@@ -561,6 +561,19 @@ static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
 // the same conditions, evaluated on the host (fedm_pattern_info).  The one-pass and row-phase kernels need a
 // template instance assemble_dispatch takes for the LFA family with Poisson, FIAT's degree-2 rule and the
 // logarithmic representation, and no external source (the one-pass kernels besides: lean3_applies).
+// (one predicate for assembly_prediction and launch_assemble_species)
+static bool lean_model_applies(const Ctx &c) {
+    const fedm_model_desc &m = c.model;
+    bool ext = false;
+    for (int s = 0; s < c.ns; ++s) ext = ext || m.ext_nodes[s] > 0;
+    const double sixth = 1.0 / 6.0, two3 = 2.0 / 3.0;
+    const bool stdq = m.n_qp == 3 && m.qp_x[0] == sixth && m.qp_x[1] == sixth && m.qp_x[2] == two3 &&
+                      m.qp_y[0] == sixth && m.qp_y[1] == two3 && m.qp_y[2] == sixth && m.qp_w[0] == sixth &&
+                      m.qp_w[1] == sixth && m.qp_w[2] == sixth;
+    return c.model_kind == 0 && c.poisson && c.ns >= 1 && c.ns <= 4 && !m.linear_representation && stdq && !ext &&
+           c.assembly_lean >= 2;
+}
+
 int assembly_prediction(const Ctx &c, bool jacobian, int *threads) {
     if (c.model_kind != 0) {
         *threads = 0;
@@ -570,15 +583,7 @@ int assembly_prediction(const Ctx &c, bool jacobian, int *threads) {
         *threads = 256;
         return 0;
     }
-    const fedm_model_desc &m = c.model;
-    bool ext = false;
-    for (int s = 0; s < c.ns; ++s) ext = ext || m.ext_nodes[s] > 0;
-    const double sixth = 1.0 / 6.0, two3 = 2.0 / 3.0;
-    const bool stdq = m.n_qp == 3 && m.qp_x[0] == sixth && m.qp_x[1] == sixth && m.qp_x[2] == two3 &&
-                      m.qp_y[0] == sixth && m.qp_y[1] == two3 && m.qp_y[2] == sixth && m.qp_w[0] == sixth &&
-                      m.qp_w[1] == sixth && m.qp_w[2] == sixth;
-    const bool lean_model = c.poisson && c.ns >= 1 && c.ns <= 4 && !m.linear_representation && stdq && !ext &&
-                            c.assembly_lean >= 2;
+    const bool lean_model = lean_model_applies(c);
     const uint32_t cmask = (jacobian && c.skip_const_planes && c.const_planes_valid) ? c.const_plane_mask : 0u;
     const bool gen3 = lean_model && c.assembly_lean >= 3 && lean3_applies(c) && lean3_fits(c, jacobian, cmask);
     const bool gen2 = lean_model && c.pat.max_patch_cells <= 256;
@@ -599,7 +604,9 @@ int assembly_prediction(const Ctx &c, bool jacobian, int *threads) {
 // per facet colour (facets of a colour share no vertex), plain adds on top of the volume
 // assembly -> fixed summation order.
 // =============================================================================================
-template <int NS, bool ATOMIC>
+// SPECIES_COLS: the species columns only (the segregated step's species assembly: the planes of the potential column
+// are not touched)
+template <int NS, bool ATOMIC, bool SPECIES_COLS = false>
 __global__ void boundary_kernel(const fedm_model_desc *__restrict__ md, int n_facets,
                                 const int *__restrict__ facets /* [n][3] = cell, local facet, tag */,
                                 const int *__restrict__ cells, const double *__restrict__ coords,
@@ -624,6 +631,7 @@ __global__ void boundary_kernel(const fedm_model_desc *__restrict__ md, int n_fa
         else *p += value;
     };
     auto addJ = [&](int a, int b, int sr, int scol, double value) {
+        if (SPECIES_COLS && scol == NEQ - 1) return;
         const uint32_t slot = cell_slots[(size_t)c * 9 + a * 3 + b];
         double *p = &val[((size_t)(slot >> 6) * NEQ2 + sr * NEQ + scol) * SLICE + (slot & 63)];
         if (ATOMIC) unsafeAtomicAdd(p, value);
@@ -722,6 +730,41 @@ void launch_assemble(Ctx &c, bool jacobian, int mode) {
         else
             launch_boundary(c, jacobian);
     }
+}
+
+// The species equations alone (fedm_newton_solve_species): the species-only one-pass kernel where it applies, with the
+// boundary facets' species columns behind it; otherwise the full assembly as it is (the solve ignores the potential
+// row and column).  launch_finalize follows in both cases (Dirichlet and padding rows), then F of the potential rows
+// is set to 0.
+bool launch_assemble_species(Ctx &c, bool jacobian, bool volume_only) {
+    bool one_pass = false;
+    if (c.assembly_kind == 1 && c.ns == 2 && lean_model_applies(c)) {
+        int *rec = c.launched[jacobian ? 1 : 0];
+        const int saved[4] = {rec[0], rec[1], rec[2], rec[3]};
+        rec[0] = -1;
+        rec[1] = rec[2] = rec[3] = 0;
+        prof_begin(c, jacobian ? 0 : 2);
+        one_pass = launch_assemble_lean3_species(c, jacobian);
+        prof_end(c);
+        if (!one_pass)
+            for (int i = 0; i < 4; ++i) rec[i] = saved[i];
+    }
+    if (jacobian && one_pass) c.planes_fused = false;
+    if (one_pass && volume_only) return true;
+    if (one_pass) {
+        c.boundary_pending = 0;
+        if (c.n_bfacets > 0) {
+            const dim3 g((c.n_bfacets + 127) / 128), b(128);
+            hipLaunchKernelGGL((boundary_kernel<2, true, true>), g, b, 0, c.stream, c.d_model, c.n_bfacets, c.d_bfacets,
+                               c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0);
+        }
+    } else {
+        launch_assemble(c, jacobian, 0);
+        if (volume_only) return false;
+    }
+    launch_finalize(c, jacobian, 0);
+    launch_pick_entries(c, 0, 1.0, c.d_F, c.d_F);   // (in place: the kernel's pointers are not restrict-qualified)
+    return one_pass;
 }
 
 // =============================================================================================

@@ -889,6 +889,79 @@ class DeviceProblem:
                     "fedm_poisson_solve")
         return its.value
 
+    # -- segregated (uncoupled) step: the potential with the densities frozen, then the species with the field frozen
+    def poisson_update(self, rtol=1e-10, max_it=20000):
+        """The potential entries of ``u_new`` from the Poisson rows with its species entries frozen
+        (``fedm_poisson_update``; the reference's ``Poisson_solver``).  Returns the CG iterations, kept in
+        ``last_poisson_iterations`` too."""
+        its = C.c_int()
+        rc = self.lib.fedm_poisson_update(self._h, float(rtol), int(max_it), C.byref(its))
+        self.last_poisson_iterations = its.value
+        self._check(rc, "fedm_poisson_update")
+        return its.value
+
+    def newton_solve_species(self, rtol=1e-9, max_it=50, atol=1e-10, stol=1e-16,
+                             ksp_restart=30, ksp_rtol=1e-5, ksp_atol=1e-50, ksp_max_it=10000):
+        """Newton on the species rows with the potential entries frozen (``fedm_newton_solve_species``).
+        ``last_report`` carries its counts and its norms over the species entries."""
+        o = _lib.NewtonOpts(rtol, atol, stol, max_it, ksp_restart, ksp_rtol, ksp_atol, ksp_max_it, 0)
+        r = _lib.NewtonReport()
+        rc = self.lib.fedm_newton_solve_species(self._h, C.byref(o), C.byref(r))
+        self.last_report = NewtonReport(r.iterations, bool(r.converged), r.linear_iterations,
+                                        r.fnorm0, r.fnorm)
+        self._check(rc, "fedm_newton_solve_species")
+        return r.iterations, True
+
+    def species_assembly(self, jacobian=True):
+        """Test hook: the assembly of one species Newton iteration alone (``fedm_debug_species_assembly``): F_u and
+        J_uu, or with ``jacobian=False`` F_u by the residual-only twin.  True when the species-only one-pass kernel
+        ran, False when the full assembly did."""
+        rc = self.lib.fedm_debug_species_assembly(self._h, 1 if jacobian else 0)
+        if rc < 0:
+            self._check(rc, "fedm_debug_species_assembly")
+        return bool(rc)
+
+    def block_product(self, which, x):
+        """Test hook: ``y = J_bb x_b`` with the Jacobian as it stands, ``which`` = "species" or "potential"
+        (``fedm_debug_block_product``); caller's dof order, exact zeros on the other block's entries."""
+        x = self._vec(x)
+        y = np.empty(self.n)
+        self._check(self.lib.fedm_debug_block_product(self._h, {"species": 0, "potential": 1}[which], _dp(x), _dp(y)),
+                    "fedm_debug_block_product")
+        return self._back(y)
+
+    def species_linear_solve(self, b, ksp_restart=30, ksp_rtol=1e-5, ksp_atol=1e-50, ksp_max_it=10000):
+        """Test hook: flexible GMRES on ``J_uu x_u = b_u`` with the Jacobian as the last species assembly left it,
+        through the call the species Newton makes (``fedm_debug_species_linear_solve``).  Returns
+        ``(x, its, rnorm, code)``: x with zeros on the potential entries, the step count, the true residual norm the
+        solver reports and its return code (0 or FEDM_DIVERGED_*)."""
+        o = _lib.NewtonOpts(0.0, 0.0, 0.0, 0, ksp_restart, ksp_rtol, ksp_atol, ksp_max_it, 0)
+        b = self._vec(b)
+        x = np.zeros(self.n)
+        its, rnorm = C.c_int(), C.c_double()
+        rc = self.lib.fedm_debug_species_linear_solve(self._h, _dp(b), C.byref(o), _dp(x), C.byref(its),
+                                                      C.byref(rnorm))
+        if rc < 0:
+            self._check(rc, "fedm_debug_species_linear_solve")
+        return self._back(x), its.value, rnorm.value, rc
+
+    def segregated_solve(self, poisson_rtol=1e-10, poisson_max_it=20000, **newton):
+        """One segregated step from the state as it stands: ``poisson_update`` then ``newton_solve_species``
+        (whose arguments ``newton`` holds).  First order in dt against ``newton_solve``; explicit in the space
+        charge, so stable for ``dt < eps0 / (e mu_e n_e)``."""
+        self.poisson_update(rtol=poisson_rtol, max_it=poisson_max_it)
+        return self.newton_solve_species(**newton)
+
+    SEGREGATED_STATS = ("poisson_updates", "cg_iterations", "species_solves", "one_pass_assemblies",
+                        "fallback_assemblies", "newton_iterations", "krylov_steps", "reserved")
+
+    def segregated_stats(self, reset=False):
+        """Counters of the segregated step since the context was created or they were last reset
+        (``fedm_segregated_stats``), by name."""
+        out = (C.c_int64 * 8)()
+        self._check(self.lib.fedm_segregated_stats(self._h, out, 1 if reset else 0), "fedm_segregated_stats")
+        return dict(zip(self.SEGREGATED_STATS, (int(v) for v in out)))
+
     def field_error(self, component):
         e = C.c_double()
         self._check(self.lib.fedm_field_error(self._h, int(component), C.byref(e)), "fedm_field_error")

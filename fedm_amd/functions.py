@@ -484,14 +484,19 @@ class PETScSNESSolver:
     + one multigrid V-cycle on the potential block) once ``setup_multigrid`` has installed a
     hierarchy, by point-block Jacobi otherwise -- to ``krylov_relative_tolerance``.
     ``krylov_residual_scaling``: "none" (the test is on ``|b - J x|``) or "rows" (on the row-equilibrated
-    ``|D (b - J x)|``, ``DeviceProblem.set_krylov_scaling``; field split on the right only)."""
+    ``|D (b - J x)|``, ``DeviceProblem.set_krylov_scaling``; field split on the right only).
+    ``coupling``: "coupled" (one Newton solve on the mixed space) or "uncoupled" (the reference's segregated
+    strategy, fedm/functions.py:777-843, 1154-1161: the potential from the Poisson rows with the densities frozen,
+    to ``poisson_relative_tolerance``, then Newton on the species rows with the field frozen --
+    ``DeviceProblem.segregated_solve``).  "uncoupled" does not go with ``krylov_residual_scaling`` "rows"."""
 
     def __init__(self):
         self.parameters = {"relative_tolerance": 1e-9, "absolute_tolerance": 1e-10,
                            "solution_tolerance": 1e-16, "maximum_iterations": 50,
                            "linear_solver": "gmres", "preconditioner": "default",
                            "krylov_restart": 30, "krylov_relative_tolerance": 1e-5,
-                           "krylov_maximum_iterations": 10000, "krylov_residual_scaling": "none"}
+                           "krylov_maximum_iterations": 10000, "krylov_residual_scaling": "none",
+                           "coupling": "coupled", "poisson_relative_tolerance": 1e-10}
 
     def solve(self, problem, x=None):
         p = self.parameters
@@ -501,11 +506,26 @@ class PETScSNESSolver:
         scaling = p.get("krylov_residual_scaling", "none")
         if scaling not in ("none", "rows"):
             raise ValueError(f"krylov_residual_scaling must be 'none' or 'rows', got {scaling!r}")
+        coupling = p.get("coupling", "coupled")
+        if coupling not in ("coupled", "uncoupled"):
+            raise ValueError(f"coupling must be 'coupled' or 'uncoupled', got {coupling!r}")
+        if coupling == "uncoupled" and scaling == "rows":
+            raise ValueError("coupling 'uncoupled' does not go with krylov_residual_scaling 'rows': the species "
+                             "block's own equilibration is not implemented")
         if hasattr(dev, "krylov_scaling_mode"):
             if dev.krylov_scaling_mode() != ("none", "rows").index(scaling):
                 dev.set_krylov_scaling(scaling)
         elif scaling != "none":
             raise NotImplementedError("krylov_residual_scaling needs a device problem with set_krylov_scaling")
+        if coupling == "uncoupled":
+            if not hasattr(dev, "segregated_solve"):
+                raise NotImplementedError("coupling 'uncoupled' needs a device problem with segregated_solve")
+            return dev.segregated_solve(poisson_rtol=p.get("poisson_relative_tolerance", 1e-10),
+                                        rtol=p["relative_tolerance"], max_it=p["maximum_iterations"],
+                                        atol=p["absolute_tolerance"], stol=p["solution_tolerance"],
+                                        ksp_restart=p["krylov_restart"],
+                                        ksp_rtol=p["krylov_relative_tolerance"],
+                                        ksp_max_it=p["krylov_maximum_iterations"])
         return dev.newton_solve(rtol=p["relative_tolerance"], max_it=p["maximum_iterations"],
                                 atol=p["absolute_tolerance"], stol=p["solution_tolerance"],
                                 ksp_restart=p["krylov_restart"],
@@ -517,8 +537,14 @@ def Poisson_solver(A, L, b, bcs, u, solver_type="mumps", preconditioner="hypre_a
     """fedm/functions.py:1154-1161: assemble the right-hand side ``L`` (into ``b``), apply the Dirichlet
     values and solve ``A u = b`` -- with the host-side tensors of ``fedm_amd.forms.assemble`` (``A``
     already carries the boundary rows, as in the reference).  The solver names are accepted; the solve is
-    a sparse direct one."""
+    a sparse direct one.  A right-hand side that carries a device problem in a ``device`` attribute (the
+    attribute ``Problem`` reads; the lowering does not set it on forms yet, a caller does) is not assembled on the host: the potential is solved on the device with the densities frozen
+    (``DeviceProblem.poisson_update``) and ``b`` is returned as it came."""
     from . import forms
+    dev = getattr(L, "device", None)
+    if dev is not None and hasattr(dev, "poisson_update"):
+        dev.poisson_update()
+        return b
     b = forms.assemble(L, tensor=b)
     for bc in bcs:
         bc.apply(b)

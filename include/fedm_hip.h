@@ -217,7 +217,8 @@ const char *fedm_last_error(void);
  * 7: fedm_launched_assembly, fedm_get_residual; fedm_pattern_info out[6..7] predict what the next fedm_jacobian
  *    launches.
  * 8: fedm_solver_path_stats, fedm_debug_linear_solve.
- * 9: fedm_set_krylov_scaling, fedm_get_krylov_scaling. */
+ * 9: fedm_set_krylov_scaling, fedm_get_krylov_scaling; additive: fedm_poisson_update, fedm_newton_solve_species,
+ *    fedm_segregated_stats, fedm_debug_species_linear_solve, fedm_debug_species_assembly, fedm_debug_block_product, fedm_time_kernel kinds 6, 7. */
 #define FEDM_ABI_VERSION 9
 int fedm_abi_version(void);
 
@@ -295,6 +296,52 @@ int fedm_spmv(fedm_ctx *ctx, const double *x, double *y);
 int fedm_newton_solve(fedm_ctx *ctx, const fedm_newton_opts *opts, fedm_newton_report *rep);
 /* Poisson row only, species frozen (initial potential, fedm-streamer.py:205-215) */
 int fedm_poisson_solve(fedm_ctx *ctx, double rtol, int max_it, int *iterations);
+
+/* ---- segregated (uncoupled) time step ------------------------------------------------------
+ * The reference's second solution strategy: the potential on its own with the densities frozen, then the species
+ * among themselves with the field frozen.  One step from the shifted state is fedm_poisson_update followed by
+ * fedm_newton_solve_species.  First order in dt against the coupled step; explicit in the space charge, so stable
+ * for dt below the dielectric relaxation time eps0 / (e mu_e n_e).  One GPU, LFA family with a Poisson row. */
+
+/* Poisson_solver(A, L, b, u, bcs) (fedm/functions.py:1154-1161) once per step: the potential entries of u_new are
+ * solved from the Poisson rows with the species entries of u_new frozen (bit-identical afterwards); Dirichlet rows
+ * stay as they are.  The right-hand side comes from a residual-only assembly; the operator is the potential-potential
+ * planes of the Jacobian as they stand (assembled once if this context has never assembled a Jacobian) and the
+ * preconditioner the installed multigrid hierarchy (Jacobi without one): conjugate gradients to
+ * |r| <= rtol |r0|.  iterations (unless NULL): CG steps.  Returns 0, FEDM_DIVERGED_LINEAR or FEDM_DIVERGED_NAN. */
+int fedm_poisson_update(fedm_ctx *ctx, double rtol, int max_it, int *iterations);
+/* nonlinear_solver.solve on the species equations alone, what a script gets from Source_term / Energy_Source_term
+ * with coupling='uncoupled' (fedm/functions.py:777-843, 845-912) and a problem without the Poisson equation: Newton
+ * (newtonls / basic, the rules of fedm_newton_solve) on the species rows with the potential entries frozen
+ * (bit-identical afterwards).  Each system J_uu delta_u = -F_u goes to flexible GMRES(ksp_restart) preconditioned by
+ * the species polynomial of fedm_set_fieldsplit (point-block Jacobi on the n_species x n_species blocks when none is
+ * installed), no V-cycle; ksp_rtol / ksp_atol are tested on the true species residual, which is formed before a
+ * solve reports success.  The report's norms are norms over the species entries.  Assembly: the species-only
+ * one-pass kernels where they apply (csrc/assemble3.hip: neither the Poisson row nor a plane of the potential row or
+ * column is evaluated, accumulated or written; F of the potential rows is written as 0); otherwise the full assembly,
+ * whose potential row and column the solve ignores. */
+int fedm_newton_solve_species(fedm_ctx *ctx, const fedm_newton_opts *opts, fedm_newton_report *rep);
+/* Counters of the two calls above since the context was created (or the last call with reset != 0; out may be NULL
+ * then): out = {potential updates, their CG iterations, species solves, species-only one-pass assemblies, fallback
+ * (full) assemblies run for species solves, species Newton iterations, species Krylov steps, reserved}. */
+int fedm_segregated_stats(fedm_ctx *ctx, int64_t out[8], int reset);
+/* Test hooks.  fedm_debug_species_assembly: the assembly a species Newton iteration runs, alone -- F_u and J_uu
+ * (jacobian != 0) or F_u by the residual-only twin (jacobian = 0: the matrix is not touched); F of the potential rows is
+ * 0 either way.  Returns 1 when the species-only one-pass kernel ran, 0 when the full assembly did (counted in
+ * fedm_segregated_stats like a solve's assemblies), < 0 on refusal.
+ * fedm_debug_block_product: y = J_bb x_b with the Jacobian as it stands, block 0 = species (y_u = J_uu x_u, the
+ * structurally zero species planes skipped), 1 = potential (y_phi = J_phiphi x_phi); the entries of the other block come
+ * back as exact zeros.  Host vectors in the caller-side layout of fedm_residual: the products the two stages make. */
+int fedm_debug_species_assembly(fedm_ctx *ctx, int jacobian);
+int fedm_debug_block_product(fedm_ctx *ctx, int which, const double *x, double *y);
+/* Test hook, fedm_debug_linear_solve's counterpart for the species block: x = the flexible-GMRES solution of
+ * J_uu x_u = b_u with the Jacobian as the last species assembly (or fedm_jacobian) left it, through the very call
+ * fedm_newton_solve_species makes (opts' ksp_* fields are read).  b and x in the caller-side layout of fedm_residual;
+ * the potential entries of b are ignored, those of x come back as zeros.  The state is not touched; F of the last
+ * assembly is overwritten with -b_u.  Returns what the solver returns; its / rnorm: its step count and the true
+ * residual norm |b_u - J_uu x_u|_2 it reports. */
+int fedm_debug_species_linear_solve(fedm_ctx *ctx, const double *b, const fedm_newton_opts *opts, double *x, int *its,
+                                    double *rnorm);
 
 /* ---- linear solver set-up -----------------------------------------------------------------
  * The reference hands J dx = -F to MUMPS (examples) or to PETSc GMRES + default PC (test
@@ -502,7 +549,9 @@ int fedm_field_error(fedm_ctx *ctx, int component, double *rel_err);
 
 /* timed micro-benchmarks on the resident state (HIP events on the library's stream):
  * kind 0 = residual+Jacobian assembly, 1 = SpMV, 2 = residual only, 3 = one multigrid cycle on the
- * potential block, 4 = the field split's set-up behind an assembly (species planes), 5 = assembly + that set-up.
+ * potential block, 4 = the field split's set-up behind an assembly (species planes), 5 = assembly + that set-up,
+ * 6 = species-only residual+Jacobian assembly (fedm_newton_solve_species; the full one where the one-pass kernel does
+ * not apply), 7 = the right-hand-side assembly of fedm_poisson_update (residual only).
  * ms per launch. */
 int fedm_time_kernel(fedm_ctx *ctx, int kind, int repeats, double *ms_per_launch);
 /* Copy rate of the device (GB/s, read + write bytes): a 16-byte-per-lane grid-stride copy between two
