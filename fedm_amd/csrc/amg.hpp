@@ -34,7 +34,7 @@ struct Amg {
         //   b_c = C b,            C  = R (I - w A Dinv),
         // and prolongation + second sweep is one product on the concatenated vector [b ; x_c]
         //   x   = G b + Q x_c,    G  = w Dinv (2 I - w A Dinv),   Q = (I - w Dinv A) P
-        // (built on the host at set-up, capi.cpp).  Two kernels per level instead of four.  b holds
+        // (built on the host at set-up, amg_setup.cpp).  Two kernels per level instead of four.  b holds
         // n_rows_p + (rows of the next level) entries and the next level's x is its tail.
         EllMat C, GQ;
         bool composite = false;

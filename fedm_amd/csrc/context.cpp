@@ -1,0 +1,866 @@
+// C ABI of libfedm_hip.so (include/fedm_hip.h): the context, its state and its settings.
+// Host logic only; every flop of the hot path runs in kernels.hip.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "solver.hpp"
+
+namespace fedm {
+
+static thread_local std::string g_error;
+void set_error(const std::string &msg) { g_error = msg; }
+
+void prof_collect(Ctx &c) {
+    Prof &p = c.prof;
+    if (p.used == 0) return;
+    hipStreamSynchronize(c.stream);
+    for (int i = 0; i + 1 < p.used; i += 2) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, p.ev[i], p.ev[i + 1]) == hipSuccess) {
+            p.ms[p.kind[i / 2]] += ms;
+            p.cnt[p.kind[i / 2]]++;
+        }
+    }
+    p.used = 0;
+}
+
+void prof_begin(Ctx &c, int kind) {
+    Prof &p = c.prof;
+    p.recording = false;
+    if (!p.on || c.capturing || ((kind == 1 || kind == 3) && !p.all_kinds)) return;
+    // events cost a few microseconds of stream time each: short, frequent kernels are sampled
+    p.recording = (p.seen[kind]++ % p.stride[kind]) == 0;
+    if (!p.recording) return;
+    if (p.used + 2 > (int)p.ev.size()) prof_collect(c);
+    p.kind[p.used / 2] = kind;
+    hipEventRecord(p.ev[p.used], c.stream);
+}
+
+void prof_end(Ctx &c) {
+    Prof &p = c.prof;
+    if (!p.on || !p.recording || c.capturing) return;
+    hipEventRecord(p.ev[p.used + 1], c.stream);
+    p.used += 2;
+    p.recording = false;
+}
+
+template <class T>
+static int upload(T *&dst, const T *src, size_t n) {
+    FEDM_HIP_CHECK(hipMalloc((void **)&dst, sizeof(T) * std::max<size_t>(n, 1)));
+    if (n) FEDM_HIP_CHECK(hipMemcpy(dst, src, sizeof(T) * n, hipMemcpyHostToDevice));
+    return 0;
+}
+
+static int alloc_zero(double *&p, size_t n, hipStream_t st) {
+    FEDM_HIP_CHECK(hipMalloc((void **)&p, sizeof(double) * std::max<size_t>(n, 1)));
+    FEDM_HIP_CHECK(hipMemsetAsync(p, 0, sizeof(double) * std::max<size_t>(n, 1), st));
+    return 0;
+}
+
+static int check_model(const fedm_model_desc &m) {
+    if (m.n_species < 1 || m.n_species > FEDM_MAX_SPECIES) return 1;
+    if (m.n_reactions < 0 || m.n_reactions > FEDM_MAX_REACTIONS) return 1;
+    if (m.n_qp < 1 || m.n_qp > FEDM_MAX_QP || m.n_fqp < 0 || m.n_fqp > FEDM_MAX_FQP) return 1;
+    if (m.n_tags < 0 || m.n_tags > FEDM_MAX_TAGS) return 1;
+    const int ns = m.n_species, po = m.poisson ? 1 : 0;
+    const bool ok = (ns == 1) || (ns == 2) || ((ns == 3 || ns == 4) && po);
+    if (!ok) return 1;
+    for (int s = 0; s < ns; ++s) {
+        if (m.eq_type[s] < 0 || m.eq_type[s] > 2) return 1;
+        if (m.mu[s].n_terms < 0 || m.mu[s].n_terms > FEDM_MAX_TERMS) return 1;
+        if (m.D[s].n_terms < 0 || m.D[s].n_terms > FEDM_MAX_TERMS) return 1;
+        if (m.ext_nodes[s] < 0 || m.ext_nodes[s] > FEDM_MAX_EXT_NODES) return 1;
+    }
+    for (int j = 0; j < m.n_reactions; ++j)
+        if (m.k[j].n_terms < 0 || m.k[j].n_terms > FEDM_MAX_TERMS) return 1;
+    return 0;
+}
+
+int put_vec(Ctx &c, double *dst, const double *src) {
+    if (!src) return 0;
+    std::memcpy(c.h_stage, src, sizeof(double) * c.n);
+    FEDM_HIP_CHECK(hipMemcpyAsync(dst, c.h_stage, sizeof(double) * c.n, hipMemcpyHostToDevice, c.stream));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+int get_vec(Ctx &c, double *dst, const double *src) {
+    FEDM_HIP_CHECK(hipMemcpyAsync(c.h_stage, src, sizeof(double) * c.n, hipMemcpyDeviceToHost, c.stream));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    std::memcpy(dst, c.h_stage, sizeof(double) * c.n);
+    return 0;
+}
+
+}  // namespace fedm
+
+using namespace fedm;
+
+extern "C" {
+
+const char *fedm_last_error(void) { return g_error.c_str(); }
+int fedm_abi_version(void) { return FEDM_ABI_VERSION; }
+
+static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *model,
+                           const fedm_gd_desc *gd, int device, fedm_ctx **out);
+
+// every error exit of the set-up releases what had been allocated so far (context, stream, device
+// and pinned memory): a caller that retries after an out-of-memory must not accumulate leaked HBM
+static int ctx_create_guarded(const fedm_mesh_desc *mesh, const fedm_model_desc *model,
+                              const fedm_gd_desc *gd, int device, fedm_ctx **out) {
+    *out = nullptr;
+    fedm_ctx *h = nullptr;
+    const int rc = ctx_create_impl(mesh, model, gd, device, &h);
+    if (rc != 0) {
+        const std::string msg = g_error;  // destroy may overwrite it
+        if (h) fedm_ctx_destroy(h);
+        g_error = msg;
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int fedm_ctx_create(const fedm_mesh_desc *mesh, const fedm_model_desc *model, int device,
+                    fedm_ctx **out) {
+    if (!mesh || !model || !out) {
+        set_error("null argument");
+        return -2;
+    }
+    if (check_model(*model)) {
+        // refused, never truncated: the LFA kernels are instantiated for 1-2 species without and 1-4 species
+        // with a Poisson equation (fedm_model_desc's arrays hold FEDM_MAX_SPECIES = 4 and FEDM_MAX_REACTIONS = 8)
+        set_error("unsupported LFA model: " + std::to_string(model->n_species) + " species" +
+                  (model->poisson ? " + Poisson" : "") + ", " + std::to_string(model->n_reactions) +
+                  " reactions, " + std::to_string(model->n_qp) + " quadrature points (supported: 1-2 species, or 1-4 "
+                  "with a Poisson equation; at most " + std::to_string(FEDM_MAX_REACTIONS) + " reactions, " +
+                  std::to_string(FEDM_MAX_TERMS) + " terms per coefficient, " + std::to_string(FEDM_MAX_QP) +
+                  " quadrature points)");
+        return -2;
+    }
+    return ctx_create_guarded(mesh, model, nullptr, device, out);
+}
+
+int fedm_ctx_create_gd(const fedm_mesh_desc *mesh, const fedm_gd_desc *gd, int device,
+                       fedm_ctx **out) {
+    if (!mesh || !gd || !out) {
+        set_error("null argument");
+        return -2;
+    }
+    if (gd->n_species < 2 || gd->n_species > FEDM_GD_MAX_SPECIES - 1 || gd->n_reactions < 0 ||
+        gd->n_reactions > FEDM_GD_MAX_REACTIONS || gd->n_qp < 1 || gd->n_qp > FEDM_MAX_QP ||
+        gd->n_fqp < 0 || gd->n_fqp > FEDM_MAX_FQP || gd->n_tags < 0 || gd->n_tags > FEDM_MAX_TAGS) {
+        set_error("unsupported LMEA model descriptor");
+        return -2;
+    }
+    for (int j = 0; j < gd->n_reactions; ++j)
+        for (int i = 0; i < gd->n_species; ++i)
+            if (gd->power[j][i] < 0 || gd->power[j][i] > 15) {   // the kernels pack them 4 bits each
+                set_error("LMEA reaction powers must be between 0 and 15");
+                return -2;
+            }
+    return ctx_create_guarded(mesh, nullptr, gd, device, out);
+}
+
+int fedm_gd_prep_setup(fedm_ctx *h, const fedm_csr *mass, int n_tables, const int32_t *tab_ptr,
+                       const double *tab_x, const double *tab_y, const fedm_gd_field_prog *progs) {
+    Ctx &c = h->c;
+    if (c.model_kind != 1 || !mass || !tab_ptr || !progs || n_tables < 0 || mass->n_rows != c.nv) {
+        set_error("bad LMEA field-refresh description");
+        return -2;
+    }
+    for (int r = 0; r < c.gd_n_fields; ++r)
+        if ((progs[r].kind == FEDM_GDP_TABLE && (progs[r].table < 0 || progs[r].table >= n_tables)) ||
+            (progs[r].kind == FEDM_GDP_SCALED_ROW && (progs[r].src_row < 0 || progs[r].src_row >= c.gd_n_fields))) {
+            set_error("field program refers to a missing table or row");
+            return -2;
+        }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    return gd_prep_setup(c, mass, n_tables, tab_ptr, tab_x, tab_y, progs);
+}
+
+int fedm_gd_prep_step(fedm_ctx *h) {
+    Ctx &c = h->c;
+    if (c.model_kind != 1 || !c.gd_prep) {
+        set_error("fedm_gd_prep_setup has not been called");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    const int rc = gd_prep_step(c);
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    return rc;
+}
+
+int fedm_gd_update_mean_energy(fedm_ctx *h) {
+    Ctx &c = h->c;
+    if (c.model_kind != 1) {
+        set_error("not an LMEA context");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    gd_update_mean_energy(c);
+    return 0;
+}
+
+int fedm_gd_get_fields(fedm_ctx *h, double *out) {
+    Ctx &c = h->c;
+    if (c.model_kind != 1 || !out) {
+        set_error("not an LMEA context");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    FEDM_HIP_CHECK(hipMemcpy(out, c.d_gd_fields, sizeof(double) * (size_t)c.gd_n_fields * c.nv, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int fedm_gd_set_fields(fedm_ctx *h, const double *fields) {
+    Ctx &c = h->c;
+    if (c.model_kind != 1 || !fields) {
+        set_error("not an LMEA context");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipMemcpyAsync(c.d_gd_fields, fields, sizeof(double) * (size_t)c.gd_n_fields * c.nv,
+                                  hipMemcpyHostToDevice, c.stream));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *model,
+                           const fedm_gd_desc *gd, int device, fedm_ctx **out) {
+    if (mesh->n_vertices < 3 || mesh->n_cells < 1) {
+        set_error("empty mesh");
+        return -2;
+    }
+    for (int i = 0; i < 3 * mesh->n_cells; ++i)
+        if (mesh->cells[i] < 0 || mesh->cells[i] >= mesh->n_vertices) {
+            set_error("cell vertex index out of range");
+            return -2;
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error("no HIP device available: libfedm_hip has no CPU fallback");
+        return -3;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(device));
+    fedm_ctx *h = new fedm_ctx();
+    *out = h;  // from here on the caller (ctx_create_guarded) owns it, error exits included
+    Ctx &c = h->c;
+    c.device = device;
+    const int n_tags_model = model ? model->n_tags : gd->n_tags;
+    if (model) {
+        c.model = *model;
+        c.ns = model->n_species;
+        c.poisson = model->poisson != 0;
+    } else {  // LMEA: energy + (n_species - 1) particle equations + potential
+        c.model_kind = 1;
+        c.gd = *gd;
+        c.ns = gd->n_species;
+        c.poisson = true;
+        c.assembly_kind = 0;
+    }
+    c.neq = c.ns + (c.poisson ? 1 : 0);
+    c.nv = mesh->n_vertices;
+    c.nc = mesh->n_cells;
+    {
+        // (Expression sources are tables indexed by (cell, local node): their cells keep their vertex order)
+        bool tables = false;
+        if (model)
+            for (int s_ = 0; s_ < model->n_species; ++s_) tables = tables || model->ext_nodes[s_] > 0;
+        build_pattern(*mesh, c.pat, !tables);
+    }
+    c.nvp = c.pat.nvp;
+    c.n_owned = (mesh->n_owned_vertices > 0 && mesh->n_owned_vertices <= c.nv) ? mesh->n_owned_vertices : c.nv;
+    c.n_dot = (int64_t)c.n_owned * c.neq;
+    c.halo_depth = 1;
+    if (mesh->halo_depth > 1 && (mesh->identity_vertices || mesh->n_identity_vertices == 0)) {
+        for (int i = 0; i < mesh->n_identity_vertices; ++i)
+            if (mesh->identity_vertices[i] < c.n_owned || mesh->identity_vertices[i] >= c.nv) {
+                set_error("identity_vertices must be ghost vertices");
+                return -2;
+            }
+        c.halo_depth = mesh->halo_depth;
+        c.n_identity = mesh->n_identity_vertices;
+        if (upload(c.d_identity, mesh->identity_vertices, (size_t)c.n_identity)) return -1;
+    }
+    c.n = (int64_t)c.nv * c.neq;
+    c.np = (int64_t)c.nvp * c.neq;
+    for (int i = 0; i < mesh->n_dirichlet; ++i)
+        if (mesh->dirichlet_dofs[i] < 0 || mesh->dirichlet_dofs[i] >= c.n) {
+            set_error("Dirichlet dof out of range");
+            return -2;
+        }
+    FEDM_HIP_CHECK(hipStreamCreate(&c.stream));
+    if (upload(c.d_coords, mesh->coords, (size_t)2 * c.nv)) return -1;
+    if (upload(c.d_cells, mesh->cells, (size_t)3 * c.nc)) return -1;
+    std::vector<int8_t> zero_tags;
+    const int8_t *tags = mesh->facet_tags;
+    if (!tags) {
+        zero_tags.assign((size_t)3 * c.nc, 0);
+        tags = zero_tags.data();
+    }
+    for (size_t i = 0; i < (size_t)3 * c.nc; ++i)
+        if (tags[i] < 0 || tags[i] > n_tags_model) {
+            set_error("facet tag out of range");
+            return -2;
+        }
+    if (upload(c.d_ftags, tags, (size_t)3 * c.nc)) return -1;
+    {
+        // tagged boundary facets, greedily coloured so that facets of one colour share no
+        // vertex of their cells: the boundary kernel can then add without atomics, in a
+        // fixed order (bitwise reproducible)
+        std::vector<int> fcell, floc, ftag, fcol;
+        std::vector<uint32_t> used(c.nv, 0);
+        int ncol = 0;
+        for (int cell = 0; cell < c.nc; ++cell)
+            for (int i = 0; i < 3; ++i)
+                if (tags[3 * cell + i] > 0) {
+                    const int32_t *v = mesh->cells + 3 * cell;
+                    const uint32_t m = used[v[0]] | used[v[1]] | used[v[2]];
+                    int k = 0;
+                    while (k < 31 && ((m >> k) & 1u)) ++k;
+                    for (int a = 0; a < 3; ++a) used[v[a]] |= (1u << k);
+                    ncol = std::max(ncol, k + 1);
+                    fcell.push_back(cell);
+                    floc.push_back(i);
+                    ftag.push_back(tags[3 * cell + i]);
+                    fcol.push_back(k);
+                }
+        std::vector<int> bf;
+        c.bfacet_colour_ptr.assign(ncol + 1, 0);
+        for (int k = 0; k < ncol; ++k) {
+            for (size_t f = 0; f < fcell.size(); ++f)
+                if (fcol[f] == k) {
+                    bf.push_back(fcell[f]);
+                    bf.push_back(floc[f]);
+                    bf.push_back(ftag[f]);
+                }
+            c.bfacet_colour_ptr[k + 1] = (int)bf.size() / 3;
+        }
+        c.n_bfacets = (int)bf.size() / 3;
+        if (upload(c.d_bfacets, bf.data(), bf.size())) return -1;
+        // Do the boundary facets (species rows of their cells' vertices) and the Dirichlet dofs meet in a row?  If not
+        // -- the scripts put Dirichlet values on the potential only -- the two can share a launch (launch_finalize)
+        std::vector<char> is_dirichlet((size_t)c.nv * c.neq, 0);
+        for (int k = 0; k < mesh->n_dirichlet; ++k)
+            if (mesh->dirichlet_dofs[k] >= 0 && (int64_t)mesh->dirichlet_dofs[k] < (int64_t)c.nv * c.neq)
+                is_dirichlet[mesh->dirichlet_dofs[k]] = 1;
+        c.boundary_rows_disjoint = true;
+        for (size_t f = 0; f < fcell.size() && c.boundary_rows_disjoint; ++f)
+            for (int a = 0; a < 3; ++a)
+                for (int sp = 0; sp < c.ns; ++sp)
+                    if (is_dirichlet[(size_t)mesh->cells[3 * fcell[f] + a] * c.neq + sp]) c.boundary_rows_disjoint = false;
+        // the rows that change behind the volume assembly (Ctx::planes_fused): vertices of boundary-facet cells, of
+        // Dirichlet values, and the padding of the last slice
+        {
+            std::vector<char> touched((size_t)c.nvp, 0);
+            for (size_t f = 0; f < fcell.size(); ++f)
+                for (int a = 0; a < 3; ++a) touched[mesh->cells[3 * fcell[f] + a]] = 1;
+            for (int k = 0; k < mesh->n_dirichlet; ++k)
+                if (mesh->dirichlet_dofs[k] >= 0 && (int64_t)mesh->dirichlet_dofs[k] < (int64_t)c.nv * c.neq)
+                    touched[mesh->dirichlet_dofs[k] / c.neq] = 1;
+            for (int v = c.nv; v < c.nvp; ++v) touched[v] = 1;
+            std::vector<int> rows;
+            for (int v = 0; v < c.nvp; ++v)
+                if (touched[v]) rows.push_back(v);
+            c.n_planes_rows = (int)rows.size();
+            if (c.n_planes_rows && upload(c.d_planes_rows, rows.data(), rows.size())) return -1;
+            const char *e = getenv("FEDM_PLANES_FUSED");
+            // one GPU, whole-mesh launches: no identity rows of ghost layers, no listed part launches
+            // (opt-in, FEDM_PLANES_FUSED=1: measured -9 us per assembly back to back, nothing in the bench's step, and the
+            // dominant kernel 75 -> 89 us: DESIGN.md Appendix A)
+            c.planes_fuse_ok = (e && e[0] == '1') && mesh->n_identity_vertices == 0 && c.n_owned == c.nv;
+        }
+    }
+    if (upload(c.d_cell_slots, c.pat.cell_slots.data(), c.pat.cell_slots.size())) return -1;
+    if (upload(c.d_colour_cells, c.pat.colour_cells.data(), c.pat.colour_cells.size())) return -1;
+    if (model) {
+        if (upload(c.d_model, model, 1)) return -1;
+    } else {
+        if (upload(c.d_gd, gd, 1)) return -1;
+        c.gd_n_fields = FEDM_GD_N_FIELDS(gd->n_species, gd->n_reactions);
+        if (alloc_zero(c.d_gd_fields, (size_t)c.gd_n_fields * c.nv, c.stream)) return -1;
+    }
+    if (upload(c.d_patch_cell_ptr, c.pat.patch_cell_ptr.data(), c.pat.patch_cell_ptr.size())) return -1;
+    if (upload(c.d_patch_halo_ptr, c.pat.patch_halo_ptr.data(), c.pat.patch_halo_ptr.size())) return -1;
+    if (upload(c.d_patch_halo, c.pat.patch_halo.data(), c.pat.patch_halo.size())) return -1;
+    if (upload(c.d_patch_cells, c.pat.patch_cells.data(), c.pat.patch_cells.size())) return -1;
+    {
+        // LDS patches need 8-bit local indices and <= 160 KiB of LDS per workgroup; the
+        // globally coloured kernel is the (deterministic, slower) alternative.
+        const char *env = getenv("FEDM_ASSEMBLY");
+        c.assembly_kind = (env && std::string(env) == "colour") ? 0 : 1;
+        // Side of the field split: right for the LFA systems (3 instead of 5.25 Krylov steps per
+        // Newton iteration on the streamer case); left for LMEA, whose rows (energy balance next to
+        // densities) are scaled so differently that the true residual norm is the harder target
+        // (glow discharge, 402k DOFs: 70 against 100 steps per time step).  FEDM_PRECOND_SIDE or
+        // fedm_set_preconditioner_side override.
+        c.right_precond = c.model_kind == 0;
+        if (const char *lean = getenv("FEDM_ASSEMBLY_LEAN")) c.assembly_lean = lean[0] == '0' ? 0 : (lean[0] == '3' ? 3 : 2);
+        if (const char *e = getenv("FEDM_XCD_REMAP")) c.xcd_remap = e[0] != '0';
+        if (const char *e = getenv("FEDM_ASSEMBLY_OVERLAP")) c.assembly_overlap = e[0] != '0';
+        if (const char *e = getenv("FEDM_SKIP_CONST_PLANES")) c.skip_const_planes = e[0] != '0';
+        if (model && c.poisson) {
+            // potential-potential: geometry only.  Species (s, i), i != s: zero unless a reaction that
+            // changes species s has species i among its reactants (fedm/functions.py:835-843).
+            c.const_plane_mask = 1u << (c.ns * c.neq + c.ns);
+            for (int s_ = 0; s_ < c.ns; ++s_)
+                for (int i = 0; i < c.ns; ++i) {
+                    if (i == s_) continue;
+                    bool coupled = false;
+                    for (int j = 0; j < model->n_reactions; ++j)
+                        coupled = coupled || (model->net[j][s_] != 0 && model->power[j][i] > 0);
+                    if (!coupled) c.const_plane_mask |= 1u << (s_ * c.neq + i);
+                }
+            c.zero_plane_mask = c.const_plane_mask & ~(1u << (c.ns * c.neq + c.ns));
+            if (const char *e = getenv("FEDM_SPMV_SKIP_ZERO_PLANES"))
+                if (e[0] == '0') c.zero_plane_mask = 0;
+        }
+        if (const char *e = getenv("FEDM_FS_HALO")) c.fs_halo = e[0] != '0';
+        if (const char *e = getenv("FEDM_DEEP_HALO")) c.deep_halo = e[0] != '0';
+        if (const char *e = getenv("FEDM_FS_POLICY")) c.fs_measured_policy = std::string(e) != "counts";
+        if (const char *e = getenv("FEDM_FS_LAGGED_COUPLING")) c.fs_lagged_coupling = e[0] != '0';
+        if (const char *e = getenv("FEDM_GD_HAND"))
+            if (e[0] == '0' || (e[0] >= '2' && e[0] <= '5')) c.gd_hand_mode = e[0] - '0';
+        if (const char *e = getenv("FEDM_FS_ORDER")) c.fs_upper = std::string(e) == "upper";
+        const char *side = getenv("FEDM_PRECOND_SIDE");
+        if (side && std::string(side) == "left") c.right_precond = false;
+        if (side && std::string(side) == "right") c.right_precond = true;
+        if (!c.pat.patch_ok || patch_lds_bytes(c) > 160 * 1024 || c.model_kind == 1) c.assembly_kind = 0;
+    }
+    if (upload(c.d_slice_boff, c.pat.slice_boff.data(), c.pat.slice_boff.size())) return -1;
+    if (upload(c.d_colidx, c.pat.colidx.data(), c.pat.colidx.size())) return -1;
+    if (upload(c.d_diag_slot, c.pat.diag_slot.data(), c.pat.diag_slot.size())) return -1;
+    c.n_dir = mesh->n_dirichlet;
+    if (upload(c.d_dir_dofs, mesh->dirichlet_dofs, (size_t)c.n_dir)) return -1;
+    if (upload(c.d_dir_vals, mesh->dirichlet_vals, (size_t)c.n_dir)) return -1;
+    const size_t nval = (size_t)c.pat.total_bc * SLICE * c.neq * c.neq;
+    if (alloc_zero(c.d_val, nval, c.stream)) return -1;
+    if (alloc_zero(c.d_dinv, (size_t)c.nvp * c.neq * c.neq, c.stream)) return -1;
+    double **vecs[] = {&c.d_u, &c.d_uold, &c.d_uold1, &c.d_F, &c.d_delta, &c.d_w, &c.d_rhs, &c.d_tmp, &c.d_fs, &c.d_fs_g};
+    for (auto v : vecs)
+        if (alloc_zero(*v, (size_t)c.np, c.stream)) return -1;
+    if (alloc_zero(c.d_partials, (size_t)RED_BLOCKS * RED_K, c.stream)) return -1;
+    if (alloc_zero(c.d_red, RED_K, c.stream)) return -1;
+    FEDM_HIP_CHECK(hipHostMalloc((void **)&c.h_mail, sizeof(double) * MAIL_SLOTS * (RED_K + 1), hipHostMallocDefault));
+    std::memset(c.h_mail, 0, sizeof(double) * MAIL_SLOTS * (RED_K + 1));
+    c.h_red = c.h_mail;
+    FEDM_HIP_CHECK(hipMalloc((void **)&c.d_mail_seq, sizeof(unsigned long long)));
+    FEDM_HIP_CHECK(hipMemset(c.d_mail_seq, 0, sizeof(unsigned long long)));
+
+    FEDM_HIP_CHECK(hipHostMalloc((void **)&c.h_stage, sizeof(double) * (size_t)c.np));
+    for (int s = 0; model && s < c.ns; ++s)
+        if (model->ext_nodes[s] > 0)
+            if (alloc_zero(c.d_ext[s], (size_t)c.nc * model->ext_nodes[s], c.stream)) return -1;
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+void fedm_ctx_destroy(fedm_ctx *h) {
+    if (!h) return;
+    Ctx &c = h->c;
+    hipSetDevice(c.device);
+    // a failed transport first: its communicator is aborted before anything below waits for the device
+    // (comm.hip, Comm::release_communicator); the error stays readable through fedm_last_error
+    if (c.comm) {
+        comm_poll_async_error(c);
+        if (c.comm->failed && c.comm->release_communicator())
+            set_error(c.comm->error + " -- communicator aborted at teardown");
+    }
+    if (c.stream) hipStreamSynchronize(c.stream);
+    void *ptrs[] = {c.d_coords, c.d_cells, c.d_ftags, c.d_cell_slots, c.d_colour_cells, c.d_model,
+                    c.d_slice_boff, c.d_colidx, c.d_diag_slot, c.d_val, c.d_dinv, c.d_dir_dofs,
+                    c.d_dir_vals, c.d_identity, c.d_u, c.d_uold, c.d_uold1, c.d_F, c.d_delta, c.d_w, c.d_rhs,
+                    c.d_tmp, c.d_fs, c.d_fs_g, c.d_V, c.d_partials, c.d_partials_wide, c.d_red, c.d_ext[0], c.d_ext[1], c.d_ext[2],
+                    c.d_ext[3], c.d_patch_cell_ptr, c.d_patch_halo_ptr, c.d_patch_halo,
+                    c.d_patch_cells, c.d_bfacets, c.d_gd, c.d_gd_fields, c.d_gd_elem, c.d_gd_inv_ptr,
+                    c.d_gd_inv_idx, c.d_gd_elemF, c.d_gd_vinv_ptr, c.d_gd_vinv_idx, c.d_gd_kpos};
+    for (void *p : ptrs)
+        if (p) hipFree(p);
+    for (Amg *a : {c.amg, c.amg_alt})
+        if (a) {
+            a->release();
+            delete a;
+        }
+    if (c.comm) {
+        c.comm->release();
+        delete c.comm;
+    }
+    gd_prep_release(c);
+    fs_tiles_release(c);
+    for (auto &e : c.prof.ev) hipEventDestroy(e);
+    iter_graphs_clear(c);
+    if (c.d_mail_seq) hipFree(c.d_mail_seq);
+    if (c.h_mail) hipHostFree(c.h_mail);
+    if (c.d_val32) hipFree(c.d_val32);
+    if (c.d_s16) hipFree(c.d_s16);
+    if (c.d_planes_rows) hipFree(c.d_planes_rows);
+    if (c.d_Z) hipFree(c.d_Z);
+    if (c.d_kscale2) hipFree(c.d_kscale2);
+    if (c.h_stage) hipHostFree(c.h_stage);
+    if (c.d_snapshot) hipFree(c.d_snapshot);
+    if (c.d_seg_dinv) hipFree(c.d_seg_dinv);
+    lean3_release(c);
+    for (int s_ = 0; s_ < FEDM_MAX_SPECIES; ++s_) {
+        if (c.d_expr_ops[s_]) hipFree(c.d_expr_ops[s_]);
+        if (c.d_expr_consts[s_]) hipFree(c.d_expr_consts[s_]);
+    }
+    if (c.stream) hipStreamDestroy(c.stream);
+    delete h;
+}
+
+int fedm_set_state(fedm_ctx *h, const double *u_new, const double *u_old, const double *u_old1) {
+    Ctx &c = h->c;
+    c.err_cache_comp = -1;   // the state changes: the kept error norm is stale
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    if (u_new) c.halo_pending = false;  // the caller's vector carries its own ghost values
+    if (put_vec(c, c.d_u, u_new) || put_vec(c, c.d_uold, u_old) || put_vec(c, c.d_uold1, u_old1)) return -1;
+    return 0;
+}
+
+int fedm_get_state(fedm_ctx *h, double *u_new) {
+    Ctx &c = h->c;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    return get_vec(c, u_new, c.d_u);
+}
+
+int fedm_get_state_old(fedm_ctx *h, double *u_old) {
+    Ctx &c = h->c;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    return get_vec(c, u_old, c.d_uold);
+}
+
+int fedm_shift_state(fedm_ctx *h) {
+    Ctx &c = h->c;
+    c.err_cache_comp = -1;   // the state changes: the kept error norm is stale
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    std::swap(c.d_uold1, c.d_uold);  // old1 <- old (by rotation), then old <- new
+    launch_scale_copy(c, 1.0, c.d_u, c.d_uold);
+    return 0;
+}
+
+int fedm_reset_state(fedm_ctx *h) {
+    Ctx &c = h->c;
+    c.err_cache_comp = -1;   // the state changes: the kept error norm is stale
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    launch_scale_copy(c, 1.0, c.d_uold, c.d_u);
+    return 0;
+}
+
+int fedm_state_snapshot(fedm_ctx *h) {
+    Ctx &c = h->c;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    if (c.halo_pending) {   // (several GPUs: the ghost entries of the state are exchanged lazily)
+        comm_halo(c, c.d_u);
+        c.halo_pending = false;
+    }
+    if (!c.d_snapshot) FEDM_HIP_CHECK(hipMalloc((void **)&c.d_snapshot, sizeof(double) * 3 * c.np));
+    const double *src[3] = {c.d_u, c.d_uold, c.d_uold1};
+    for (int k = 0; k < 3; ++k)
+        FEDM_HIP_CHECK(hipMemcpyAsync(c.d_snapshot + (size_t)k * c.np, src[k], sizeof(double) * c.np,
+                                      hipMemcpyDeviceToDevice, c.stream));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    // ... and what the solver has learnt from the steps before (how many Krylov steps to queue ahead, at which Newton
+    // iteration the final check is expected): steps repeated from the checkpoint then run as they did the first time
+    c.snap_krylov_steps_hint = c.krylov_steps_hint;
+    c.snap_newton_its_hint = c.newton_its_hint;
+    return 0;
+}
+
+int fedm_state_restore(fedm_ctx *h) {
+    Ctx &c = h->c;
+    if (!c.d_snapshot) {
+        set_error("fedm_state_restore: no snapshot taken");
+        return -2;
+    }
+    c.err_cache_comp = -1;
+    c.krylov_steps_hint = c.snap_krylov_steps_hint;
+    c.newton_its_hint = c.snap_newton_its_hint;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    c.halo_pending = false;   // the snapshot was taken with exchanged ghosts
+    double *dst[3] = {c.d_u, c.d_uold, c.d_uold1};
+    for (int k = 0; k < 3; ++k)
+        FEDM_HIP_CHECK(hipMemcpyAsync(dst[k], c.d_snapshot + (size_t)k * c.np, sizeof(double) * c.np,
+                                      hipMemcpyDeviceToDevice, c.stream));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+int fedm_set_step(fedm_ctx *h, double dt, double dt_old) {
+    h->c.dt = dt;
+    h->c.dt_old = dt_old;
+    return 0;
+}
+
+int fedm_set_dirichlet_values(fedm_ctx *h, const double *vals) {
+    Ctx &c = h->c;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    if (c.n_dir)
+        FEDM_HIP_CHECK(hipMemcpy(c.d_dir_vals, vals, sizeof(double) * c.n_dir, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int fedm_set_ext_source(fedm_ctx *h, int species, const double *nodal) {
+    Ctx &c = h->c;
+    if (species < 0 || species >= c.ns || !c.d_ext[species]) {
+        set_error("species has no Expression source");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipMemcpyAsync(c.d_ext[species], nodal,
+                                  sizeof(double) * (size_t)c.nc * c.model.ext_nodes[species],
+                                  hipMemcpyHostToDevice, c.stream));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+// the program is checked here once (stack discipline, index ranges): the kernel trusts it
+int fedm_ext_source_program(fedm_ctx *h, int species, int n_ops, const int32_t *ops, int n_consts,
+                            const double *consts, int n_params) {
+    Ctx &c = h->c;
+    if (species < 0 || species >= c.ns || !c.d_ext[species]) {
+        set_error("species has no Expression source");
+        return -2;
+    }
+    const int nodes = c.model.ext_nodes[species];
+    if (nodes != 3 && nodes != 6 && nodes != 10) {
+        set_error("device evaluation of Expression sources: degree 1, 2 or 3");
+        return -2;
+    }
+    if (!ops || n_ops < 1 || n_ops > FEDM_EXPR_MAX_OPS || n_consts < 0 || (n_consts > 0 && !consts) ||
+        n_params < 0 || n_params > FEDM_EXPR_MAX_PARAMS) {
+        set_error("bad expression program");
+        return -2;
+    }
+    int depth = 0;
+    for (int k = 0; k < n_ops; ++k) {
+        const int op = ops[2 * k], arg = ops[2 * k + 1];
+        bool ok = true;
+        if (op == FEDM_OP_CONST) ok = arg >= 0 && arg < n_consts, ++depth;
+        else if (op == FEDM_OP_X) ok = arg == 0 || arg == 1, ++depth;
+        else if (op == FEDM_OP_PARAM) ok = arg >= 0 && arg < n_params, ++depth;
+        else if (op >= FEDM_OP_ADD && op <= FEDM_OP_POW) ok = depth >= 2, --depth;
+        else if (op >= FEDM_OP_NEG && op <= FEDM_OP_ATAN) ok = depth >= 1;
+        else ok = false;
+        if (!ok || depth > FEDM_EXPR_STACK) {
+            set_error("bad expression program (opcode, operand index or stack depth)");
+            return -2;
+        }
+    }
+    if (depth != 1) {
+        set_error("bad expression program (it must leave one value)");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    if (c.d_expr_ops[species]) hipFree(c.d_expr_ops[species]);
+    if (c.d_expr_consts[species]) hipFree(c.d_expr_consts[species]);
+    c.d_expr_ops[species] = nullptr;
+    c.d_expr_consts[species] = nullptr;
+    c.expr_n_ops[species] = 0;
+    FEDM_HIP_CHECK(hipMalloc((void **)&c.d_expr_ops[species], sizeof(int) * 2 * n_ops));
+    FEDM_HIP_CHECK(hipMalloc((void **)&c.d_expr_consts[species], sizeof(double) * (n_consts > 0 ? n_consts : 1)));
+    FEDM_HIP_CHECK(hipMemcpy(c.d_expr_ops[species], ops, sizeof(int) * 2 * n_ops, hipMemcpyHostToDevice));
+    if (n_consts > 0)
+        FEDM_HIP_CHECK(hipMemcpy(c.d_expr_consts[species], consts, sizeof(double) * n_consts, hipMemcpyHostToDevice));
+    c.expr_n_ops[species] = n_ops;
+    c.expr_n_params[species] = n_params;
+    return 0;
+}
+
+int fedm_ext_source_eval(fedm_ctx *h, int species, const double *params) {
+    Ctx &c = h->c;
+    if (species < 0 || species >= c.ns || !c.d_ext[species] || c.expr_n_ops[species] == 0) {
+        set_error("species has no expression program");
+        return -2;
+    }
+    if (c.expr_n_params[species] > 0 && !params) {
+        set_error("null argument");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    launch_ext_source_eval(c, species, params);
+    FEDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int fedm_sync_ghosts(fedm_ctx *h) {
+    Ctx &c = h->c;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    comm_halo(c, c.d_u);
+    comm_halo(c, c.d_uold);
+    comm_halo(c, c.d_uold1);
+    c.halo_pending = false;
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    if (comm_failed(c)) {
+        set_error(c.comm->error);
+        return -1;
+    }
+    return 0;
+}
+
+int fedm_set_fieldsplit(fedm_ctx *h, int sweeps, const double *weights) {
+    if (sweeps < 1 || sweeps > 16 || !weights) {
+        set_error("field-split sweeps must be 1..16 with one weight each");
+        return -2;
+    }
+    for (int i = 0; i < sweeps; ++i)
+        if (!(weights[i] > 0.0 && weights[i] < 4.0)) {
+            set_error("field-split weights must be positive");
+            return -2;
+        }
+    hipSetDevice(h->c.device);
+    hipStreamSynchronize(h->c.stream);
+    iter_graphs_clear(h->c);
+    Ctx &c = h->c;
+    set_hard_mode(c, false);
+    c.fs_sweeps = c.fs_main_sweeps = sweeps;
+    for (int i = 0; i < sweeps; ++i) c.fs_w[i] = c.fs_main_w[i] = weights[i];
+    c.fs_alt_sweeps = 0;
+    return 0;
+}
+
+int fedm_set_fieldsplit_alternative(fedm_ctx *h, int alt_sweeps, const double *alt_weights,
+                                    double switch_above, double back_below) {
+    Ctx &c = h->c;
+    if (alt_sweeps < 0 || alt_sweeps > 16 || (alt_sweeps > 0 && !alt_weights) || !(back_below < switch_above)) {
+        set_error("alternative field-split sweeps must be 0..16 with one weight each, back_below < switch_above");
+        return -2;
+    }
+    for (int i = 0; i < alt_sweeps; ++i)
+        if (!(alt_weights[i] > 0.0 && alt_weights[i] < 4.0)) {
+            set_error("field-split weights must be positive");
+            return -2;
+        }
+    hipSetDevice(c.device);
+    set_hard_mode(c, false);  // back to the main set first
+    c.fs_alt_sweeps = alt_sweeps;
+    for (int i = 0; i < alt_sweeps; ++i) c.fs_alt_w[i] = alt_weights[i];
+    c.fs_switch_above = switch_above;
+    c.fs_back_below = back_below;
+    return 0;
+}
+
+int fedm_fieldsplit_policy(fedm_ctx *h, int64_t out[4]) {
+    if (!h || !out) return -2;
+    const Ctx &c = h->c;
+    out[0] = (c.fs_measured_policy && !(c.comm && c.comm->nranks > 1)) ? 1 : 0;
+    out[1] = c.fs_alt_active ? 1 : 0;
+    out[2] = c.fs_solves[0];
+    out[3] = c.fs_solves[1];
+    return 0;
+}
+
+int fedm_set_assembly(fedm_ctx *h, int kind) {
+    Ctx &c = h->c;
+    if (kind == 1 && (!c.pat.patch_ok || patch_lds_bytes(c) > 160 * 1024 || c.model_kind == 1)) {
+        set_error("LDS patch assembly unavailable for this mesh");
+        return -2;
+    }
+    if (kind != 0 && kind != 1) {
+        set_error("assembly kind must be 0 (colouring) or 1 (LDS patches)");
+        return -2;
+    }
+    c.assembly_kind = kind;
+    return 0;
+}
+
+int fedm_set_preconditioner_side(fedm_ctx *h, int right) {
+    Ctx &c = h->c;
+    if (right != 0 && right != 1) {
+        set_error("preconditioner side must be 0 (left) or 1 (right)");
+        return -2;
+    }
+    if (c.right_precond != (right == 1)) {
+        hipStreamSynchronize(c.stream);
+        iter_graphs_clear(c);  // captured for the other variant
+        c.right_precond = right == 1;
+    }
+    return 0;
+}
+
+int fedm_set_fieldsplit_order(fedm_ctx *h, int upper) {
+    Ctx &c = h->c;
+    if (upper != 0 && upper != 1) {
+        set_error("field-split order must be 0 (lower) or 1 (upper)");
+        return -2;
+    }
+    if (c.fs_upper != (upper == 1)) {
+        hipStreamSynchronize(c.stream);
+        iter_graphs_clear(c);  // captured for the other order
+        c.fs_upper = upper == 1;
+    }
+    return 0;
+}
+
+int fedm_set_krylov_scaling(fedm_ctx *h, int mode) {
+    if (!h) return -2;
+    Ctx &c = h->c;
+    if (mode != 0 && mode != 1) {
+        set_error("krylov scaling mode must be 0 (none) or 1 (rows)");
+        return -2;
+    }
+    if (c.krylov_scaling != mode) {
+        FEDM_HIP_CHECK(hipSetDevice(c.device));
+        hipStreamSynchronize(c.stream);
+        iter_graphs_clear(c);  // captured with the other instantiations of the reduction kernels
+        if (mode == 1 && !c.d_kscale2) FEDM_HIP_CHECK(hipMalloc((void **)&c.d_kscale2, sizeof(double) * c.np));
+        c.krylov_scaling = mode;
+    }
+    return 0;
+}
+
+int fedm_get_krylov_scaling(fedm_ctx *h, int *mode, double *d_out) {
+    if (!h) return -2;
+    Ctx &c = h->c;
+    if (mode) *mode = c.krylov_scaling;
+    if (!d_out) return 0;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    // from the Jacobian as it stands: what a scaled solve started now would use (d^2 goes to scratch when no scaled
+    // solve has run on this context)
+    launch_row_scale(c, c.d_kscale2 ? c.d_kscale2 : c.d_tmp, c.d_w);
+    return get_vec(c, d_out, c.d_w);
+}
+
+int fedm_plane_masks(fedm_ctx *h, uint32_t *kept_planes, uint32_t *zero_planes) {
+    Ctx &c = h->c;
+    if (kept_planes) *kept_planes = (c.skip_const_planes && c.assembly_kind == 1 && c.assembly_lean >= 2) ? c.const_plane_mask : 0u;
+    if (zero_planes) *zero_planes = c.neq == 3 ? (c.zero_plane_mask & 10u) : 0u;
+    return 0;
+}
+
+int fedm_sizes(fedm_ctx *h, int64_t *n_vertices, int64_t *n_cells, int64_t *n_eq,
+               int64_t *nnz_blocks, int64_t *stored_blocks, int64_t *n_colours) {
+    Ctx &c = h->c;
+    if (n_vertices) *n_vertices = c.nv;
+    if (n_cells) *n_cells = c.nc;
+    if (n_eq) *n_eq = c.neq;
+    if (nnz_blocks) *nnz_blocks = c.pat.nnz_blocks;
+    if (stored_blocks) *stored_blocks = c.pat.total_bc * SLICE;
+    if (n_colours) *n_colours = (int64_t)c.pat.colour_ptr.size() - 1;
+    return 0;
+}
+
+int fedm_pattern_info(fedm_ctx *h, int64_t out[9]) {
+    if (!h || !out) return -2;
+    Ctx &c = h->c;
+    out[0] = c.pat.n_slices;
+    out[1] = c.pat.max_patch_cells;
+    out[2] = c.pat.max_patch_width;
+    out[3] = c.pat.max_patch_verts;
+    out[4] = (int64_t)c.pat.patch_cells.size();
+    out[5] = (int64_t)c.pat.patch_halo.size();
+    // the volume assembly the next fedm_jacobian call runs (kernels.hip, assembly_prediction: the dispatch's own
+    // conditions): 0 global colouring, 1 LDS patches with the unrolled element routine, 2 LDS patches one equation
+    // row at a time (lean2 kernels), 3 LDS patches, one pass over the cells (lean3 kernels, assemble3.hip)
+    int threads = 0;
+    const int variant = assembly_prediction(c, true, &threads);
+    out[6] = variant < 0 ? 0 : variant;
+    out[7] = threads;
+    // the one-pass kernels with the model's structure compiled in (assemble3.hip, Lean3SigBenchmark)
+    out[8] = variant == 3 ? lean3_signature(c) : 0;
+    return 0;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// Kernels of the segregated (uncoupled) time step: fedm_poisson_update and fedm_newton_solve_species (capi.cpp).
+// Kernels of the segregated (uncoupled) time step: fedm_poisson_update and fedm_newton_solve_species (newton.cpp).
 //
 // The reference solves the potential on its own with the densities frozen (Poisson_solver,
 // fedm/functions.py:1154-1161) and then the species among themselves with the field frozen (Source_term with

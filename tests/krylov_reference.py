@@ -1,8 +1,8 @@
-"""A float64 restatement of the solvers of fedm_amd/csrc/capi.cpp (``gmres()``, ``fedm_newton_solve``) in numpy/scipy,
-written from the algorithms DESIGN.md section 4 names, not from the driver's loops: restarted GMRES(m), flexible with the
-preconditioner on the right (z_j = M^-1 v_j kept, x += Z y, stopping test on the true residual's recurrence) or with
-the preconditioner on the left (M^-1 J x = M^-1 b, stopping test on the preconditioned residual), and the Newton loop
-with PETSc's ``newtonls`` / ``basic`` tests.
+"""A float64 restatement of the solvers of fedm_amd/csrc (``gmres()`` in krylov.cpp, ``fedm_newton_solve`` in
+newton.cpp) in numpy/scipy, written from the algorithms DESIGN.md section 4 names, not from the driver's loops:
+restarted GMRES(m), flexible with the preconditioner on the right (z_j = M^-1 v_j kept, x += Z y, stopping test on
+the true residual's recurrence) or with the preconditioner on the left (M^-1 J x = M^-1 b, stopping test on the
+preconditioned residual), and the Newton loop with PETSc's ``newtonls`` / ``basic`` tests.
 
 It is a predictor, not a bit-level twin of the device: modified Gram-Schmidt with full re-orthogonalisation (two passes
 every step, norms taken explicitly) where the device runs classical Gram-Schmidt in one pass and forms

@@ -1,4 +1,4 @@
-"""The GMRES driver and the Newton loop of fedm_amd/csrc/capi.cpp against float64, path by path.
+"""The GMRES driver and the Newton loop of fedm_amd/csrc/krylov.cpp and newton.cpp against float64, path by path.
 
 What the solvers are fed is pinned elsewhere (assembly, the preconditioner, J x).  Here: what they do with it.  Every
 linear case solves ``J x = b`` through ``DeviceProblem.linear_solve`` (``fedm_debug_linear_solve``: the very ``gmres()``

@@ -609,7 +609,7 @@ def test_non_logarithmic_weak_forms_compile_and_representations_may_not_be_mixed
 def test_polynomial_smoother_recurrence_and_weights():
     """The polynomial-smoother hierarchy (fedm_amg_setup_poly) folds k Richardson sweeps from a zero
     guess into one product x = S b with S <- S + w Dinv (I - A S), and the post-smoother's error
-    propagator into E = I - S_post A (csrc/capi.cpp builds C = R (I - A S_pre), G = E S_pre + S_post,
+    propagator into E = I - S_post A (csrc/amg_setup.cpp builds C = R (I - A S_pre), G = E S_pre + S_post,
     Q = E P from them).  Restated with scipy: the recurrence is the sweeps, the composite level is the
     smoothed two-level cycle, and the weights of amg.chebyshev_smoother_weights are the reciprocals of
     Chebyshev roots inside [lambda_max / fraction, lambda_max]."""

@@ -70,7 +70,7 @@ def test_each_mesh_lands_in_its_band(stats):
 def test_the_lds_sums_put_each_mesh_on_its_side_of_the_limits(stats):
     """Dynamic LDS of one workgroup (limit_meshes.lds_bytes restates assemble3.hip lean3_lds_bytes and kernels.hip
     patch_lds_bytes): a one-pass launch beyond 160 KiB is refused (assemble3.hip lean3_fits), beyond it the LDS patches
-    are given up for the global colouring (capi.cpp fedm_ctx_create), and beyond 64 KiB a launch needs more than the
+    are given up for the global colouring (context.cpp fedm_ctx_create), and beyond 64 KiB a launch needs more than the
     default dynamic LDS."""
     lds = {n: lm.lds_bytes(s["max_patch_width"], s["max_patch_verts"]) for n, s in stats.items()}
     for n in ("cells192", "cells256", "cells384", "verts255", "small"):
