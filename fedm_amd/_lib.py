@@ -127,6 +127,7 @@ _SIGNATURES = {
     "fedm_gd_prep_setup": (C.c_int, [_P, C.POINTER(Csr), C.c_int, C.POINTER(C.c_int32), _D, _D,
                                      C.POINTER(GdFieldProg)]),
     "fedm_gd_prep_step": (C.c_int, [_P]),
+    "fedm_debug_gd_reduced_field": (C.c_int, [_P, _D]),
     "fedm_gd_update_mean_energy": (C.c_int, [_P]),
     "fedm_get_state_old": (C.c_int, [_P, _D]),
     "fedm_ctx_destroy": (None, [_P]),
@@ -141,6 +142,7 @@ _SIGNATURES = {
     "fedm_set_ext_source": (C.c_int, [_P, C.c_int, _D]),
     "fedm_ext_source_program": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _D, C.c_int]),
     "fedm_ext_source_eval": (C.c_int, [_P, C.c_int, _D]),
+    "fedm_debug_get_ext_source": (C.c_int, [_P, C.c_int, _D]),
     "fedm_residual": (C.c_int, [_P, _D, _D]),
     "fedm_jacobian": (C.c_int, [_P]),
     "fedm_jacobian_nnz": (C.c_int64, [_P]),
@@ -217,7 +219,7 @@ EXPR_OPS = {"const": 0, "x": 1, "param": 2, "add": 3, "sub": 4, "mul": 5, "div":
 EXPR_MAX_OPS, EXPR_MAX_PARAMS, EXPR_STACK = 256, 16, 24
 
 
-ABI_VERSION = 9          # include/fedm_hip.h FEDM_ABI_VERSION
+ABI_VERSION = 10         # include/fedm_hip.h FEDM_ABI_VERSION
 
 
 def exported_symbols():

@@ -169,12 +169,37 @@ int fedm_gd_prep_setup(fedm_ctx *h, const fedm_csr *mass, int n_tables, const in
         set_error("bad LMEA field-refresh description");
         return -2;
     }
-    for (int r = 0; r < c.gd_n_fields; ++r)
-        if ((progs[r].kind == FEDM_GDP_TABLE && (progs[r].table < 0 || progs[r].table >= n_tables)) ||
-            (progs[r].kind == FEDM_GDP_SCALED_ROW && (progs[r].src_row < 0 || progs[r].src_row >= c.gd_n_fields))) {
-            set_error("field program refers to a missing table or row");
+    // what np.interp refuses is refused here, before anything is allocated or launched: the kernel trusts the tables
+    if (tab_ptr[0] != 0) {
+        set_error("fedm_gd_prep_setup: tab_ptr must start at 0");
+        return -2;
+    }
+    for (int t = 0; t < n_tables; ++t)
+        if (tab_ptr[t + 1] < tab_ptr[t]) {
+            set_error("fedm_gd_prep_setup: tab_ptr must not decrease");
             return -2;
         }
+    if (tab_ptr[n_tables] > 0 && (!tab_x || !tab_y)) {
+        set_error("fedm_gd_prep_setup: null table arrays");
+        return -2;
+    }
+    for (int r = 0; r < c.gd_n_fields; ++r) {
+        const fedm_gd_field_prog &p = progs[r];
+        if (p.kind < FEDM_GDP_KEEP || p.kind > FEDM_GDP_UE_OLD ||
+            (p.kind == FEDM_GDP_TABLE && p.arg != FEDM_GDP_ARG_ENERGY && p.arg != FEDM_GDP_ARG_REDFIELD)) {
+            set_error("fedm_gd_prep_setup: field program with an unknown kind or argument");
+            return -2;
+        }
+        if ((p.kind == FEDM_GDP_TABLE && (p.table < 0 || p.table >= n_tables)) ||
+            (p.kind == FEDM_GDP_SCALED_ROW && (p.src_row < 0 || p.src_row >= c.gd_n_fields))) {
+            set_error("fedm_gd_prep_setup: field program refers to a missing table or row");
+            return -2;
+        }
+        if (p.kind == FEDM_GDP_TABLE && tab_ptr[p.table + 1] == tab_ptr[p.table]) {
+            set_error("fedm_gd_prep_setup: a field program looks up a table without entries");
+            return -2;
+        }
+    }
     FEDM_HIP_CHECK(hipSetDevice(c.device));
     return gd_prep_setup(c, mass, n_tables, tab_ptr, tab_x, tab_y, progs);
 }

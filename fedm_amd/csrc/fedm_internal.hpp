@@ -349,6 +349,7 @@ int lean3_signature(const Ctx &c);   // the precompiled model structure the one-
 int gd_prep_setup(Ctx &c, const fedm_csr *mass, int n_tables, const int32_t *tab_ptr,
                   const double *tab_x, const double *tab_y, const fedm_gd_field_prog *progs);
 int gd_prep_step(Ctx &c);
+int gd_debug_reduced_field(Ctx &c, double *out);   // d_redE of the last gd_prep_step (nv entries, device order)
 void gd_update_mean_energy(Ctx &c);
 void gd_prep_release(Ctx &c);
 size_t patch_lds_bytes(const Ctx &c, bool jacobian = true);

@@ -432,8 +432,10 @@ int gd_prep_setup(Ctx &c, const fedm_csr *mass, int n_tables, const int32_t *tab
     FEDM_HIP_CHECK(hipMalloc((void **)&g->d_tab_y, sizeof(double) * std::max(ntab, 1)));
     FEDM_HIP_CHECK(hipMalloc((void **)&g->d_progs, sizeof(fedm_gd_field_prog) * g->n_rows));
     FEDM_HIP_CHECK(hipMemcpy(g->d_tab_ptr, tab_ptr, sizeof(int) * (n_tables + 1), hipMemcpyHostToDevice));
-    FEDM_HIP_CHECK(hipMemcpy(g->d_tab_x, tab_x, sizeof(double) * ntab, hipMemcpyHostToDevice));
-    FEDM_HIP_CHECK(hipMemcpy(g->d_tab_y, tab_y, sizeof(double) * ntab, hipMemcpyHostToDevice));
+    if (ntab > 0) {     // (no entries at all: tab_x and tab_y may be null)
+        FEDM_HIP_CHECK(hipMemcpy(g->d_tab_x, tab_x, sizeof(double) * ntab, hipMemcpyHostToDevice));
+        FEDM_HIP_CHECK(hipMemcpy(g->d_tab_y, tab_y, sizeof(double) * ntab, hipMemcpyHostToDevice));
+    }
     FEDM_HIP_CHECK(hipMemcpy(g->d_progs, progs, sizeof(fedm_gd_field_prog) * g->n_rows, hipMemcpyHostToDevice));
     for (double **p : {&g->d_redE, &g->d_b, &g->d_r, &g->d_p, &g->d_q}) {
         FEDM_HIP_CHECK(hipMalloc((void **)p, sizeof(double) * g->nvp));
@@ -470,6 +472,13 @@ int gd_prep_step(Ctx &c) {
     hipLaunchKernelGGL(gd_fields_kernel, dim3((c.nv + 255) / 256), dim3(256), 0, c.stream, c.nv, g.n_rows,
                        g.d_progs, g.d_tab_ptr, g.d_tab_x, g.d_tab_y, g.d_redE, c.d_uold, c.neq, row_me_old,
                        row_me, c.d_gd_fields);
+    return 0;
+}
+
+// test hook: the projected reduced field of the last gd_prep_step, in the device's vertex order
+int gd_debug_reduced_field(Ctx &c, double *out) {
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    FEDM_HIP_CHECK(hipMemcpy(out, c.gd_prep->d_redE, sizeof(double) * c.nv, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -68,6 +68,37 @@ int fedm_debug_block_product(fedm_ctx *h, int which, const double *x, double *y)
     return get_vec(c, y, c.d_w);
 }
 
+int fedm_debug_gd_reduced_field(fedm_ctx *h, double *out) {
+    if (!h || !out) {
+        set_error("fedm_debug_gd_reduced_field: null argument");
+        return -2;
+    }
+    Ctx &c = h->c;
+    if (c.model_kind != 1 || !c.gd_prep) {
+        set_error("fedm_debug_gd_reduced_field: not an LMEA context, or fedm_gd_prep_setup has not been called");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    return gd_debug_reduced_field(c, out);
+}
+
+int fedm_debug_get_ext_source(fedm_ctx *h, int species, double *out) {
+    if (!h || !out) {
+        set_error("fedm_debug_get_ext_source: null argument");
+        return -2;
+    }
+    Ctx &c = h->c;
+    if (species < 0 || species >= c.ns || !c.d_ext[species]) {
+        set_error("species has no Expression source");
+        return -2;
+    }
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    FEDM_HIP_CHECK(hipMemcpy(out, c.d_ext[species], sizeof(double) * (size_t)c.nc * c.model.ext_nodes[species],
+                             hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int fedm_segregated_stats(fedm_ctx *h, int64_t out[8], int reset) {
     if (!h || (!out && !reset)) {
         set_error("fedm_segregated_stats: null argument");

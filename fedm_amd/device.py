@@ -554,6 +554,13 @@ class DeviceProblem:
     def gd_prep_step(self):
         self._check(self.lib.fedm_gd_prep_step(self._h), "fedm_gd_prep_step")
 
+    def get_gd_reduced_field(self):
+        """The projected reduced electric field of the last :meth:`gd_prep_step` (what its E/N look-ups were
+        evaluated at), caller's vertex numbering (``fedm_debug_gd_reduced_field``)."""
+        out = np.empty(self.nv)
+        self._check(self.lib.fedm_debug_gd_reduced_field(self._h, _dp(out)), "fedm_debug_gd_reduced_field")
+        return np.ascontiguousarray(out[self._inv])
+
     def gd_update_mean_energy(self):
         self._check(self.lib.fedm_gd_update_mean_energy(self._h), "fedm_gd_update_mean_energy")
 
@@ -579,6 +586,14 @@ class DeviceProblem:
     def set_ext_source(self, species, nodal):
         v = np.ascontiguousarray(nodal, dtype=np.float64)
         self._check(self.lib.fedm_set_ext_source(self._h, int(species), _dp(v)), "fedm_set_ext_source")
+
+    def get_ext_source(self, species):
+        """The species' source table as it stands on the device, (n_cells, nodes) (``fedm_debug_get_ext_source``)."""
+        degrees = list(getattr(self.model, "ext_source_degree", ()))
+        k = degrees[int(species)] if 0 <= int(species) < len(degrees) else 0
+        out = np.empty((self.nc, (k + 1) * (k + 2) // 2))          # (no source: the library refuses, nothing is written)
+        self._check(self.lib.fedm_debug_get_ext_source(self._h, int(species), _dp(out)), "fedm_debug_get_ext_source")
+        return out
 
     # -- Problem.F / Problem.J ------------------------------------------------
     def residual(self, download=True):

@@ -218,8 +218,11 @@ const char *fedm_last_error(void);
  *    launches.
  * 8: fedm_solver_path_stats, fedm_debug_linear_solve.
  * 9: fedm_set_krylov_scaling, fedm_get_krylov_scaling; additive: fedm_poisson_update, fedm_newton_solve_species,
- *    fedm_segregated_stats, fedm_debug_species_linear_solve, fedm_debug_species_assembly, fedm_debug_block_product, fedm_time_kernel kinds 6, 7. */
-#define FEDM_ABI_VERSION 9
+ *    fedm_segregated_stats, fedm_debug_species_linear_solve, fedm_debug_species_assembly, fedm_debug_block_product, fedm_time_kernel kinds 6, 7.
+ * 10: fedm_debug_gd_reduced_field, fedm_debug_get_ext_source; fedm_gd_prep_setup refuses what np.interp refuses (a
+ *    looked-up table without entries, a tab_ptr that does not start at 0 or decreases, null table arrays, a program
+ *    kind or argument outside its enum). */
+#define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
 /* mesh + model -> device: colouring, sliced block-ELL pattern, buffers.
@@ -236,6 +239,9 @@ int fedm_gd_prep_setup(fedm_ctx *ctx, const fedm_csr *mass, int n_tables, const 
 int fedm_gd_prep_step(fedm_ctx *ctx);            /* after fedm_shift_state, before the solve   */
 int fedm_gd_update_mean_energy(fedm_ctx *ctx);   /* mean_energy = exp(u_0 - u_e), :452         */
 int fedm_gd_get_fields(fedm_ctx *ctx, double *out /* [n_fields][n_vertices] */);
+/* Test hook: the projected reduced electric field of the last fedm_gd_prep_step (the argument of the E/N look-ups),
+ * n_vertices entries in the device's vertex order.  -2 when the context is not LMEA or has no refresh pipeline. */
+int fedm_debug_gd_reduced_field(fedm_ctx *ctx, double *out /* [n_vertices] */);
 void fedm_ctx_destroy(fedm_ctx *ctx);
 
 /* u_new / u_old / u_old1 (N doubles each, any may be NULL to leave unchanged).
@@ -280,6 +286,9 @@ enum {
 int fedm_ext_source_program(fedm_ctx *ctx, int species, int n_ops, const int32_t *ops /* [n_ops][2] */,
                             int n_consts, const double *consts, int n_params);
 int fedm_ext_source_eval(fedm_ctx *ctx, int species, const double *params /* [n_params] */);
+/* Test hook: the species' [n_cells][ext_nodes] table as it stands on the device (after fedm_set_ext_source or
+ * fedm_ext_source_eval); refused (-2) where fedm_set_ext_source is. */
+int fedm_debug_get_ext_source(fedm_ctx *ctx, int species, double *out /* [n_cells][ext_nodes] */);
 
 /* Problem.F: assemble(F) then bc.apply(b, x)              fedm/functions.py:188-194 */
 int fedm_residual(fedm_ctx *ctx, double *F_out /* N or NULL */, double *fnorm /* or NULL */);

@@ -29,14 +29,14 @@ ROOT = Path(__file__).resolve().parent.parent
 
 
 # ---- the binding ---------------------------------------------------------------------------------------------------
-def test_abi_version_9_and_the_two_entry_points():
+def test_abi_version_and_the_two_entry_points():
     import __graft_entry__ as entry
     entry.build()
     from fedm_amd import _lib
     header = (ROOT / "include" / "fedm_hip.h").read_text()
     lib = _lib.load()
     assert lib.fedm_abi_version() == int(re.search(r"#define FEDM_ABI_VERSION (\d+)", header).group(1)) \
-        == _lib.ABI_VERSION == 9
+        == _lib.ABI_VERSION == 10
     # the prototypes the header declares are the ones the binding attaches
     flat = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
     flat = re.sub(r"\s+", " ", flat)

@@ -32,14 +32,14 @@ N = 16                             # cells per side: the file stays well under a
 
 
 # ---- the binding ---------------------------------------------------------------------------------------------------
-def test_abi_still_9_and_the_new_entry_points():
+def test_abi_version_and_the_new_entry_points():
     import __graft_entry__ as entry
     entry.build()
     from fedm_amd import _lib
     header = (ROOT / "include" / "fedm_hip.h").read_text()
     lib = _lib.load()
     assert lib.fedm_abi_version() == int(re.search(r"#define FEDM_ABI_VERSION (\d+)", header).group(1)) \
-        == _lib.ABI_VERSION == 9
+        == _lib.ABI_VERSION == 10
     flat = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
     flat = re.sub(r"\s+", " ", flat)
     assert "int fedm_poisson_update(fedm_ctx *ctx, double rtol, int max_it, int *iterations);" in flat
