@@ -1,7 +1,7 @@
 // Third generation of the LDS-patch assembly (Problem.F / Problem.J, fedm/functions.py:188-202) for the LFA
 // models with a Poisson row and FIAT's 3-point rule: ONE pass over a patch's cells.
 //
-// The second generation (kernels.hip, assemble_lean2_kernel) bounded the live state by one equation row and
+// The second generation (assemble.hip, assemble_lean2_kernel) bounded the live state by one equation row and
 // paid for it: the rows were phases of the workgroup (two barriers and a stream-out each), every phase
 // re-read the cell's nodal values from the staging area by run-time index, rebuilt its geometry and its
 // densities at the quadrature points, and the run-time plane mask put a scalar test in front of every
@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "device_util.hpp"
 #include "element_lean.hpp"
 #include "fedm_internal.hpp"
 #include "amg.hpp"
@@ -120,11 +121,6 @@ struct Lean3Params {
     int planes_upper;
     unsigned planes_zs;
 };
-
-__device__ __forceinline__ int lean3_xcd_contiguous(int b, int n) {
-    const int per = n >> 3, full = per << 3;
-    return b < full ? (b & 7) * per + (b >> 3) : b;
-}
 
 // The moments sum_q X_q phi_a(q) [phi_b(q)] of FIAT's 3-point rule from the three weighted point values.
 __device__ __forceinline__ void p1_moments1(const double (&X)[3], double (&m)[3]) {
@@ -681,7 +677,7 @@ __device__ __forceinline__ void assemble_lean3_body(const Lean3Plan<NS, NR> *__r
         for (unsigned i = 0; i < k; ++i) __builtin_amdgcn_s_sleep(FEDM_LEAN3_STAGGER_SLEEP);
     }
 #endif
-    const int blk = p.xcd ? lean3_xcd_contiguous(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int blk = p.xcd ? xcd_contiguous(blockIdx.x, gridDim.x) : blockIdx.x;
     const int S = p.patch_list ? p.patch_list[blk] : blk;
     const int b0 = p.boff[S], width = p.boff[S + 1] - b0;
     const int c0 = p.cell_ptr[S], n_cells = p.cell_ptr[S + 1] - c0;
@@ -1354,7 +1350,7 @@ static bool lean3_launch(Ctx &c, bool jacobian, const int *list, int n) {
 
 // The models this generation is instantiated for: two species and one reaction (the streamer family) with the
 // planes the model keeps -- potential-potential alone, or together with a structurally zero species plane.
-// Everything else stays on the second generation (kernels.hip).
+// Everything else stays on the second generation (assemble.hip).
 bool lean3_applies(const Ctx &c) {
     // (FEDM_ASSEMBLY_LEAN below 3 keeps the earlier generations: Ctx::assembly_lean, read when the context is created)
     if (c.assembly_lean < 3 || c.ns != 2 || !c.poisson || c.model.n_reactions > 1 || c.pat.max_patch_cells > 2 * 192) return false;

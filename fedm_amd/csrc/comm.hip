@@ -292,7 +292,7 @@ int comm_setup_plan(Ctx &c, Comm &cm, int n_nb, const int32_t *nb_rank, const in
     if (cm.n_boundary)
         FEDM_HIP_CHECK(hipMemcpy(cm.d_boundary, boundary.data(), sizeof(int) * boundary.size(), hipMemcpyHostToDevice));
     // assembly patches (= slices) that stage no ghost vertex: their owned lanes and halo vertices
-    // are all owned.  The state halo travels while they are assembled (kernels.hip, lean2 launch).
+    // are all owned.  The state halo travels while they are assembled (assemble.hip, lean2 launch).
     {
         std::vector<int> pin, pbd;
         for (int sl = 0; sl < c.pat.n_slices; ++sl) {

@@ -1,5 +1,5 @@
 // C ABI of libfedm_hip.so (include/fedm_hip.h): the context, its state and its settings.
-// Host logic only; every flop of the hot path runs in kernels.hip.
+// Host logic only; every flop of the hot path runs in the .hip files.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -452,7 +452,7 @@ static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *mo
         const char *side = getenv("FEDM_PRECOND_SIDE");
         if (side && std::string(side) == "left") c.right_precond = false;
         if (side && std::string(side) == "right") c.right_precond = true;
-        if (!c.pat.patch_ok || patch_lds_bytes(c) > 160 * 1024 || c.model_kind == 1) c.assembly_kind = 0;
+        if (!patch_assembly_available(c)) c.assembly_kind = 0;
     }
     if (upload(c.d_slice_boff, c.pat.slice_boff.data(), c.pat.slice_boff.size())) return -1;
     if (upload(c.d_colidx, c.pat.colidx.data(), c.pat.colidx.size())) return -1;
@@ -779,7 +779,7 @@ int fedm_fieldsplit_policy(fedm_ctx *h, int64_t out[4]) {
 
 int fedm_set_assembly(fedm_ctx *h, int kind) {
     Ctx &c = h->c;
-    if (kind == 1 && (!c.pat.patch_ok || patch_lds_bytes(c) > 160 * 1024 || c.model_kind == 1)) {
+    if (kind == 1 && !patch_assembly_available(c)) {
         set_error("LDS patch assembly unavailable for this mesh");
         return -2;
     }
@@ -876,13 +876,13 @@ int fedm_pattern_info(fedm_ctx *h, int64_t out[9]) {
     out[3] = c.pat.max_patch_verts;
     out[4] = (int64_t)c.pat.patch_cells.size();
     out[5] = (int64_t)c.pat.patch_halo.size();
-    // the volume assembly the next fedm_jacobian call runs (kernels.hip, assembly_prediction: the dispatch's own
-    // conditions): 0 global colouring, 1 LDS patches with the unrolled element routine, 2 LDS patches one equation
+    // the volume assembly the next fedm_jacobian call runs (assemble.hip, assembly_path: the dispatch's own
+    // decision): 0 global colouring, 1 LDS patches with the unrolled element routine, 2 LDS patches one equation
     // row at a time (lean2 kernels), 3 LDS patches, one pass over the cells (lean3 kernels, assemble3.hip)
-    int threads = 0;
-    const int variant = assembly_prediction(c, true, &threads);
+    const AssemblyPath path = assembly_path(c, true, 0);
+    const int variant = path.variant;
     out[6] = variant < 0 ? 0 : variant;
-    out[7] = threads;
+    out[7] = path.threads;
     // the one-pass kernels with the model's structure compiled in (assemble3.hip, Lean3SigBenchmark)
     out[8] = variant == 3 ? lean3_signature(c) : 0;
     return 0;

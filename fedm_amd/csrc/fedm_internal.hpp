@@ -104,7 +104,7 @@ struct Ctx {
     uint32_t const_plane_mask = 0;
     uint32_t zero_plane_mask = 0;   // the structurally zero ones among them (the SpMV skips their bytes)
     bool skip_const_planes = true, const_planes_valid = false;
-    bool halo_pending = false;  // several GPUs: ghost entries of d_u are stale (kernels.hip, flush_pending_halo)
+    bool halo_pending = false;  // several GPUs: ghost entries of d_u are stale (assemble.hip, flush_pending_halo)
     bool assembly_overlap = true;  // ... and the next assembly hides their exchange behind its interior patches
     int model_kind = 0;  // 0: LFA family (fedm_model_desc), 1: LMEA family (fedm_gd_desc)
     fedm_gd_desc gd{};
@@ -319,10 +319,26 @@ constexpr int MAIL_SLOTS = 4;         // publications the host may have unread (
 // it gathered one double per 320-byte stride: most of reduce_finish_kernel's 10 us)
 #define PARTIAL_AT(block, slot) ((size_t)(slot) * RED_BLOCKS + (size_t)(block))
 
-// ---- kernel launchers (kernels.hip) -----------------------------------------------------
+// ---- kernel launchers: assemble.hip -----------------------------------------------------
 // mode: 0 = full model, 1 = Poisson row only (species rows become identity)
 void launch_assemble(Ctx &c, bool jacobian, int mode);
-void launch_assemble_gd(Ctx &c, bool jacobian, int mode);
+// volume + boundary + Dirichlet / padding rows of the species equations, F of the potential rows zeroed.
+// Returns true when the species-only one-pass kernel ran, false when the full assembly did.  volume_only: the volume
+// kernel alone (fedm_time_kernel; the caller clears Ctx::boundary_pending).
+bool launch_assemble_species(Ctx &c, bool jacobian, bool volume_only = false);
+// The volume kernel of an assembly (mode as launch_assemble's) of this context as it stands: what launch_assemble
+// launches and fedm_pattern_info reports.
+struct AssemblyPath {
+    int variant;      // fedm_pattern_info's 0..3, -1 for the LMEA family
+    int threads;      // per workgroup
+    uint32_t cmask;   // the planes the lean kernels keep (Ctx::const_plane_mask, or 0 on the first full assembly)
+};
+AssemblyPath assembly_path(const Ctx &c, bool jacobian, int mode);
+bool patch_assembly_available(const Ctx &c);   // LDS patches possible on this mesh and model (else the global colouring)
+size_t patch_lds_bytes(const Ctx &c, bool jacobian = true);
+void launch_finalize(Ctx &c, bool jacobian, int mode);          // Dirichlet + padding rows
+void launch_set_dirichlet_state(Ctx &c);    // u[dof] = g
+// ---- assemble3.hip, gd.hip, gdprep.hip, segregated.hip --------------------------------------
 bool lean3_applies(const Ctx &c);                                   // assemble3.hip
 void lean3_release(Ctx &c);
 bool launch_assemble_lean3(Ctx &c, bool jacobian, const int *patch_list, int n, uint32_t cmask);
@@ -330,10 +346,15 @@ bool lean3_fits(const Ctx &c, bool jacobian, uint32_t cmask);       // its LDS f
 // species-only one-pass assembly of the whole mesh (no Poisson row, no plane of the potential row or column); false:
 // it does not apply here or does not fit, nothing was launched
 bool launch_assemble_lean3_species(Ctx &c, bool jacobian);
-// volume + boundary + Dirichlet / padding rows of the species equations, F of the potential rows zeroed (kernels.hip).
-// Returns true when the species-only one-pass kernel ran, false when the full assembly did.  volume_only: the volume
-// kernel alone (fedm_time_kernel; the caller clears Ctx::boundary_pending).
-bool launch_assemble_species(Ctx &c, bool jacobian, bool volume_only = false);
+int lean3_signature(const Ctx &c);   // the precompiled model structure the one-pass kernels run with (0: run-time structure)
+void launch_assemble_gd(Ctx &c, bool jacobian, int mode);
+int gd_prep_setup(Ctx &c, const fedm_csr *mass, int n_tables, const int32_t *tab_ptr,
+                  const double *tab_x, const double *tab_y, const fedm_gd_field_prog *progs);
+int gd_prep_step(Ctx &c);
+int gd_debug_reduced_field(Ctx &c, double *out);   // d_redE of the last gd_prep_step (nv entries, device order)
+void gd_update_mean_energy(Ctx &c);
+void gd_prep_release(Ctx &c);
+void launch_ext_source_eval(Ctx &c, int species, const double *params);   // gdprep.hip
 // segregated.hip.  which = 0: y_u = J_uu x_u, y_phi = 0; which = 1: y_phi = J_phiphi x_phi, y_u = 0
 void launch_block_product(Ctx &c, int which, const double *x, double *y);
 void launch_species_block_inverse(Ctx &c);                          // c.d_seg_dinv from the diagonal blocks
@@ -342,31 +363,20 @@ void launch_species_sweep(Ctx &c, double w, const double *r, const double *t, do
 void launch_potential_jacobi(Ctx &c, const double *r, double *z);   // z_phi = r_phi / diag(J_phiphi), z_u = 0
 // y = a x on the species entries (which = 0) or the potential entries (which = 1), 0 on the others
 void launch_pick_entries(Ctx &c, int which, double a, const double *x, double *y);
-// the volume assembly of the next full-model residual (jacobian = false) or Jacobian: variant as fedm_pattern_info's,
-// threads per workgroup (kernels.hip; assemble_patch_t dispatches with the same conditions)
-int assembly_prediction(const Ctx &c, bool jacobian, int *threads);
-int lean3_signature(const Ctx &c);   // the precompiled model structure the one-pass kernels run with (0: run-time structure)
-int gd_prep_setup(Ctx &c, const fedm_csr *mass, int n_tables, const int32_t *tab_ptr,
-                  const double *tab_x, const double *tab_y, const fedm_gd_field_prog *progs);
-int gd_prep_step(Ctx &c);
-int gd_debug_reduced_field(Ctx &c, double *out);   // d_redE of the last gd_prep_step (nv entries, device order)
-void gd_update_mean_energy(Ctx &c);
-void gd_prep_release(Ctx &c);
-size_t patch_lds_bytes(const Ctx &c, bool jacobian = true);
-void launch_finalize(Ctx &c, bool jacobian, int mode);          // Dirichlet + padding rows
+// ---- spmv.hip -------------------------------------------------------------------------------
 void launch_block_inverse(Ctx &c);                              // d_dinv from diagonal blocks
 void launch_row_scale(Ctx &c, double *d2, double *d_out);       // d^2 (and d, unless null) of the rows' equilibration
 void launch_spmv(Ctx &c, const double *x, double *y, bool scale_dinv, const int *slice_list = nullptr,
                  int n_list = 0);
-void launch_ext_source_eval(Ctx &c, int species, const double *params);   // gdprep.hip
 void launch_spmv_fieldsplit(Ctx &c, const double *x, double *t, double *z, double *b0, double scale,
                             const int *slice_list = nullptr, int n_list = 0, bool compact32 = false);
 void launch_apply_dinv(Ctx &c, const double *x, double *y, double alpha);
-void launch_dots(Ctx &c, const double *const *xs, const double *y, int k, bool finish = false);
 // (finish = false, several GPUs: the local sums into d_red[0..k) only)   false: not applicable, nothing launched
 bool launch_spmv_dots(Ctx &c, const double *x, double *y, const double *const *xs, int k, bool finish = true);
 int ensure_spmv_dots(Ctx &c);
-// (see cgs_update_fs_kernel, kernels.hip; false: not instantiated for this case)
+// ---- kernels.hip ----------------------------------------------------------------------------
+void launch_dots(Ctx &c, const double *const *xs, const double *y, int k, bool finish = false);
+// (see cgs_update_fs_kernel; false: not instantiated for this case)
 bool launch_cgs_update_fs(Ctx &c, int k, const double *const *xs, double *y, float *g32, double *b0);
 bool launch_scale_copy_fs(Ctx &c, double a, const double *x, double *y, float *g32, double *b0);
 void launch_dots_fused(Ctx &c, const double *const *xs, double *y, int k, const double *x0,
@@ -384,7 +394,6 @@ void launch_multi_axpy(Ctx &c, const double *coef_host, int k, const double *con
                        double *y, double sign);                             // y += sign*sum c_i x_i
 void launch_field_error(Ctx &c, int comp);  // d_red[0]=|new-old+eps|^2, d_red[1]=|old+eps|^2
 void launch_field_error_slots34(Ctx &c, int comp);
-void launch_set_dirichlet_state(Ctx &c);    // u[dof] = g
 unsigned long long publish_values(Ctx &c, const double *src, int k);   // src[0..k) into the host mailbox, no wait
 void publish_values_queued(Ctx &c, const double *src, int k);            // ... the launch alone (stream captures)
 void wait_red_seq(Ctx &c, unsigned long long seq);  // a particular publication (steps launched ahead)

@@ -209,7 +209,7 @@ def lds_bytes(width, verts):
     * one-pass kernels, the potential plane kept (eight):  8 (64 w 8 + 64 * 3 + 9 v)
       (assemble3.hip, lean3_lds_bytes: acc + SLICE neq + 2 verts + (neq + 2 ns) verts doubles)
     * generic patch kernel:                                8 (64 w 9 + 64 * 3 + 2 v + (3 + 2) v)
-      (kernels.hip, patch_lds_bytes: acc + SLICE neq + 2 mv + (neq + ns) mv doubles)"""
+      (assemble.hip, patch_lds_bytes: acc + SLICE neq + 2 mv + (neq + ns) mv doubles)"""
     return {"lean3_all_planes": 4608 * width + 1536 + 72 * verts,
             "lean3_planes_kept": 4096 * width + 1536 + 72 * verts,
             "generic": 4608 * width + 1536 + 56 * verts}

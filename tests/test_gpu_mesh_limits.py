@@ -66,7 +66,7 @@ def _reference(name):
 
 
 def expected_kernel(stats, env, jacobian, first):
-    """(variant, threads) the dispatch must take: kernels.hip assemble_patch_t / context.cpp's choice of the colouring,
+    """(variant, threads) the dispatch must take: assemble.hip assembly_path / context.cpp's choice of the colouring,
     restated from the mesh's statistics and the LDS sums (limit_meshes.lds_bytes)."""
     cells, w, v = stats["max_patch_cells"], stats["max_patch_width"], stats["max_patch_verts"]
     lds = lm.lds_bytes(w, v)

@@ -1,5 +1,5 @@
 """The field-split preconditioner on the device (fedm_amd/csrc/amg.hip, fs_tiles.hip, the product's epilogue in
-kernels.hip) against its float64 restatement (tests/fieldsplit_reference.py): z = M^-1 t for a t = J x and for
+spmv.hip) against its float64 restatement (tests/fieldsplit_reference.py): z = M^-1 t for a t = J x and for
 t = (0, t_phi), which isolates the V-cycle.
 
 Flexible GMRES converges with almost any nonsingular M and Newton only checks the true residual, so a wrong

@@ -20,7 +20,7 @@ def stats():
 
 
 def _lean2_lds(width, verts, threads):
-    """kernels.hip assemble_patch_t, the row-phase kernels: one row of accumulators (64 w 3), the residual (64 x 3),
+    """assemble.hip assemble_patch_t, the row-phase kernels: one row of accumulators (64 w 3), the residual (64 x 3),
     the staged vertex data (coordinates 2 v, u 3 v, folded history 2 v, exp(u / 6) 2 v) and the column of cell
     constants, LeanStash<1>::N = 5 + 2 doubles a thread (element_lean.hpp:41)."""
     return 8 * (64 * 3 * width + 64 * 3 + 2 * verts + (3 + 2 * 2) * verts + 7 * threads)
@@ -68,7 +68,7 @@ def test_each_mesh_lands_in_its_band(stats):
 
 
 def test_the_lds_sums_put_each_mesh_on_its_side_of_the_limits(stats):
-    """Dynamic LDS of one workgroup (limit_meshes.lds_bytes restates assemble3.hip lean3_lds_bytes and kernels.hip
+    """Dynamic LDS of one workgroup (limit_meshes.lds_bytes restates assemble3.hip lean3_lds_bytes and assemble.hip
     patch_lds_bytes): a one-pass launch beyond 160 KiB is refused (assemble3.hip lean3_fits), beyond it the LDS patches
     are given up for the global colouring (context.cpp fedm_ctx_create), and beyond 64 KiB a launch needs more than the
     default dynamic LDS."""
