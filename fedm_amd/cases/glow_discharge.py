@@ -30,7 +30,7 @@ class Case:
 
     def __init__(self, nx=100, ny=100, file_input=DECK, device=0, T_final=1e-11,
                  relative_tolerance=1e-4, maximum_iterations=20, quiet=True, error_file=None,
-                 device_pipeline=True, mesh=None, energy_loss=None, energy_Ei=0.0):
+                 device_pipeline=True, mesh=None, energy_loss=None, energy_Ei=0.0, quadrature_degree=4):
         import tempfile
         self.quiet = quiet
         model = "4_particles"
@@ -78,7 +78,8 @@ class Case:
                            energy_loss=self.energy_loss, energy_Ei=energy_Ei,
                            mean_energy_form="unknown_ratio" if sentinels else None,     # u[0] / u[n - 1], fedm_gd.py:365
                            ref=[ref_met, ref_met, ref_zero, ref_zero],
-                           gamma=[0.06, 0.06, 0.0, 0.0], we_secondary=5.0, quadrature_degree=4)
+                           gamma=[0.06, 0.06, 0.0, 0.0], we_secondary=5.0,
+                           quadrature_degree=quadrature_degree)      # (fedm_gd.py:28 sets 4)
         z = mesh.coords[:, 1]
         self.powered = np.nonzero(np.abs(z) <= 3e-16)[0]
         self.grounded = np.nonzero(np.abs(z - self.gap) <= 3e-16)[0]

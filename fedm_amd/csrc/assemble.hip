@@ -690,6 +690,9 @@ static void assemble_dispatch(Ctx &c, bool jacobian, int mode) {
 }
 
 void launch_assemble(Ctx &c, bool jacobian, int mode) {
+    int *rec = c.launched[jacobian ? 1 : 0];   // what this assembly launches (note_assembly_launch)
+    rec[0] = -1;
+    rec[1] = rec[2] = rec[3] = 0;
     if (c.model_kind == 1) {
         flush_pending_halo(c);
         prof_begin(c, jacobian ? 0 : 2);
@@ -698,9 +701,6 @@ void launch_assemble(Ctx &c, bool jacobian, int mode) {
         return;
     }
     if (jacobian) c.planes_fused = false;   // (set by the one-pass kernel when it forms the field split's planes itself)
-    int *rec = c.launched[jacobian ? 1 : 0];   // what this assembly launches (note_assembly_launch)
-    rec[0] = -1;
-    rec[1] = rec[2] = rec[3] = 0;
     prof_begin(c, jacobian ? 0 : 2);  // the volume kernel only (all colours in variant 0)
     if (c.ns == 1 && !c.poisson) assemble_dispatch<1, false>(c, jacobian, mode);
     else if (c.ns == 1 && c.poisson) assemble_dispatch<1, true>(c, jacobian, mode);

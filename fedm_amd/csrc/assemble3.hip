@@ -1268,11 +1268,8 @@ static bool lean3_launch_one(Ctx &c, bool jacobian, const int *list, int n, int 
             hipGetLastError();
             n_cu = 256;
         }
-        auto grid_for = [&](const void *kernel, size_t &granted) {
-            if (lds > 64 * 1024 && lds > granted) {
-                hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                granted = lds;
-            }
+        auto grid_for = [&](const void *kernel) {
+            grant_dynamic_lds(kernel, c.device, lds);
             int per_cu = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, T, lds) != hipSuccess || per_cu <= 0) {
                 hipGetLastError();
@@ -1284,25 +1281,18 @@ static bool lean3_launch_one(Ctx &c, bool jacobian, const int *list, int n, int 
             return g;
         };
         if (jacobian) {
-            static size_t granted = 0;
-            const int g = grid_for(reinterpret_cast<const void *>(&assemble_lean3p_kernel<NS, NR, T, CMASK, SIG>), granted);
+            const int g = grid_for(reinterpret_cast<const void *>(&assemble_lean3p_kernel<NS, NR, T, CMASK, SIG>));
             lean3_dispatch(c, whole, assemble_lean3p_kernel<NS, NR, T, CMASK, SIG>, g, T, lds, plan, p.val, p.F, p);
             note_assembly_launch(c, true, 3, T, g);
         } else {
-            static size_t granted = 0;
-            const int g = grid_for(reinterpret_cast<const void *>(&residual_lean3p_kernel<NS, NR, T, SIG>), granted);
+            const int g = grid_for(reinterpret_cast<const void *>(&residual_lean3p_kernel<NS, NR, T, SIG>));
             lean3_dispatch(c, whole, residual_lean3p_kernel<NS, NR, T, SIG>, g, T, lds, plan, p.val, p.F, p);
             note_assembly_launch(c, false, 3, T, g);
         }
         return true;
     }
     if (jacobian) {
-        static size_t granted = 0;   // per instantiation: beyond the 64 KiB default the dynamic LDS is opt-in
-        if (lds > 64 * 1024 && lds > granted) {
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&assemble_lean3_kernel<NS, NR, T, CMASK, SIG>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            granted = lds;
-        }
+        grant_dynamic_lds(&assemble_lean3_kernel<NS, NR, T, CMASK, SIG>, c.device, lds);
         // the field split's planes from the accumulators (Ctx::planes_fused): the whole mesh in this one launch, the
         // planes' arrays there (from the second assembly on), kept species planes structurally zero
         const bool fuse = whole && !list && c.planes_fuse_ok && c.d_s16 && c.d_val32 && c.d_dinv && c.amg && c.poisson &&
@@ -1425,12 +1415,7 @@ static bool lean3_launch_species(Ctx &c, bool jacobian) {
     const size_t lds = lean3_lds_bytes(c.neq, c.ns, width, verts, PL::N, jacobian);
     if (lds > 160 * 1024) return false;
     if (jacobian) {
-        static size_t granted = 0;
-        if (lds > 64 * 1024 && lds > granted) {
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&assemble_lean3s_kernel<NS, NR, T, CMASK, SIG>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            granted = lds;
-        }
+        grant_dynamic_lds(&assemble_lean3s_kernel<NS, NR, T, CMASK, SIG>, c.device, lds);
         lean3_dispatch(c, true, assemble_lean3s_kernel<NS, NR, T, CMASK, SIG>, n, T, lds, plan, p);
     } else {
         lean3_dispatch(c, true, residual_lean3s_kernel<NS, NR, T, SIG>, n, T, lds, plan, p);

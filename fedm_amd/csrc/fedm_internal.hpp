@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "fedm_hip.h"
@@ -119,7 +121,10 @@ struct Ctx {
     int *d_gd_inv_idx = nullptr;          // cell * 9 + (a * 3 + b)
     double *d_gd_elemF = nullptr;         // element residuals [3 * neq][nc]
     int *d_gd_vinv_ptr = nullptr, *d_gd_vinv_idx = nullptr;   // vertex -> cell * 3 + local vertex
-    int gd_hand_mode = 5;                 // gd.hip, launch_assemble_gd
+    // gd.hip, gd_plan: FEDM_GD_HAND (0 | 2 | 3 | 4 | 5), and the first letters of FEDM_GD_WAVES (auto | rows | two) and
+    // FEDM_GD_GATHER (rows | positions), all three as they stood when the context was created
+    int gd_hand_mode = 5;
+    char gd_waves = 'a', gd_gather = 'r';
     uint32_t *d_gd_kpos = nullptr;        // (cell, a, b) -> place in the contributions sorted by matrix position
     GdPrep *gd_prep = nullptr;  // on-device per-step coefficient refresh (LMEA)
     Pattern pat;
@@ -262,7 +267,7 @@ struct Ctx {
     void *lean3_classes = nullptr; // assemble3.hip: patch lists by LDS need (Lean3Classes), built at first use
     double *d_snapshot = nullptr;  // fedm_state_snapshot: u, u_old, u_old1 (3 np doubles, allocated on first use)
     // the volume assembly the last residual [0] and Jacobian [1] launched (fedm_launched_assembly): variant
-    // (fedm_pattern_info's numbering, -1 before the first), threads per workgroup, launches, workgroups of all launches
+    // (include/fedm_hip.h's numbering, -1 before the first), threads per workgroup, launches, workgroups of all launches
     int launched[2][4] = {{-1, 0, 0, 0}, {-1, 0, 0, 0}};
     // which branches of gmres() and fedm_newton_solve ran (fedm_solver_path_stats; indices PS_*): host counters only
     int64_t path_stats[24] = {};
@@ -308,6 +313,23 @@ inline void note_assembly_launch(Ctx &c, bool jacobian, int variant, int threads
     r[1] = threads;
     r[2] += 1;
     r[3] += workgroups;
+}
+
+// Dynamic LDS beyond the 64 KiB default is opt-in per kernel and device.  Call before every launch that may need it:
+// the largest size set so far is remembered, and the attribute is set again only for a launch that needs more.  A
+// refusal by the runtime is passed over, as the sites did before: it is the launch that follows that fails.
+// Not thread-safe, and a refused size is remembered as if it had been set: both like the per-site statics it replaces.
+inline void grant_dynamic_lds(const void *kernel, int device, size_t bytes) {
+    if (bytes <= 64 * 1024) return;
+    static std::map<std::pair<const void *, int>, size_t> granted;
+    size_t &g = granted[{kernel, device}];
+    if (bytes <= g) return;
+    hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    g = bytes;
+}
+template <class... Args>
+inline void grant_dynamic_lds(void (*kernel)(Args...), int device, size_t bytes) {
+    grant_dynamic_lds(reinterpret_cast<const void *>(kernel), device, bytes);
 }
 
 constexpr int RED_BLOCKS = 512;

@@ -620,29 +620,24 @@ static void fs_tiles_launch(Ctx &c, FsTiles &ft, unsigned zmask, const float *g3
     const dim3 g(ft.n_tiles), b(T);
     const size_t lds = sizeof(float) * 2 * (size_t)ft.max_vertices * NS + sizeof(uint32_t) * (size_t)((W + 1) / 2) * ft.max_rows;
     const int slots = (ft.max_rows + T - 1) / T;
-    static size_t lds_granted[5] = {0, 0, 0, 0, 0};   // per instantiation <NS, W, SL>: beyond the 64 KiB default it is opt-in
     static const int tile_xcd = [] {
         const char *e = std::getenv("FEDM_FS_TILE_XCD");
         return (e && e[0] == '0') ? 0 : 1;
     }();
-#define FEDM_TILE_SWEEPS(SL, IDX)                                                                                \
+#define FEDM_TILE_SWEEPS(SL)                                                                                     \
     do {                                                                                                         \
-        if (lds > 64 * 1024 && lds > lds_granted[IDX]) {                                                         \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&fs_tile_sweeps_kernel<NS, W, SL>),               \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                           \
-            lds_granted[IDX] = lds;                                                                              \
-        }                                                                                                        \
+        grant_dynamic_lds(&fs_tile_sweeps_kernel<NS, W, SL>, c.device, lds);                                     \
         hipLaunchKernelGGL((fs_tile_sweeps_kernel<NS, W, SL>), g, b, lds, c.stream, ft.d_tile, ft.record, ft.max_vertices, \
                            ft.max_rows, ft.width, ft.d_vertex, ft.d_rowinfo, ft.d_cols, c.d_slice_boff, c.d_s16, zmask, g32, in, out32, z, wt, last ? 1 : 0, \
                            x0, cpl32, b0, tile_xcd);                                                             \
     } while (0)
     if constexpr (NS > 2) {
-        FEDM_TILE_SWEEPS(1, 0);          // (fs_tiles_get: a row a thread)
-    } else if (slots <= 2) FEDM_TILE_SWEEPS(2, 0);
-    else if (slots <= 3) FEDM_TILE_SWEEPS(3, 1);
-    else if (slots <= 4) FEDM_TILE_SWEEPS(4, 2);
-    else if (slots <= 6) FEDM_TILE_SWEEPS(6, 3);
-    else FEDM_TILE_SWEEPS(8, 4);
+        FEDM_TILE_SWEEPS(1);             // (fs_tiles_get: a row a thread)
+    } else if (slots <= 2) FEDM_TILE_SWEEPS(2);
+    else if (slots <= 3) FEDM_TILE_SWEEPS(3);
+    else if (slots <= 4) FEDM_TILE_SWEEPS(4);
+    else if (slots <= 6) FEDM_TILE_SWEEPS(6);
+    else FEDM_TILE_SWEEPS(8);
 #undef FEDM_TILE_SWEEPS
 }
 
@@ -713,27 +708,22 @@ bool mg_tiles_sweeps(Ctx &c, const EllMat &A, const double *b, const double *xin
     const int neq2 = c.neq * c.neq;
     const size_t mg_lds = mg_tiles_lds_bytes(ft->width, ft->max_vertices, ft->max_rows);
     if (mg_lds > ft->lds_limit) return false;     // (the sweeps as kernels of their own)
-    static size_t mg_granted[6] = {0, 0, 0, 0, 0, 0};
-#define FEDM_MG_TILE(WW, SL, IDX)                                                                                 \
+#define FEDM_MG_TILE(WW, SL)                                                                                      \
     do {                                                                                                          \
-        if (mg_lds > 64 * 1024 && mg_lds > mg_granted[IDX]) {                                                     \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&mg_tile_sweeps_kernel<WW, SL>),                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)mg_lds);                         \
-            mg_granted[IDX] = mg_lds;                                                                             \
-        }                                                                                                         \
+        grant_dynamic_lds(&mg_tile_sweeps_kernel<WW, SL>, c.device, mg_lds);                                      \
         hipLaunchKernelGGL((mg_tile_sweeps_kernel<WW, SL>), g, bl, mg_lds,                                        \
                            c.stream, ft->d_tile, ft->record, ft->max_vertices, ft->max_rows, ft->width, ft->d_vertex, \
                            ft->d_rowinfo, ft->d_cols, c.d_slice_boff, c.d_val, neq2, neq2 - 1, A.dinv, b, xin, wt, out, ostride, ooff, 1); \
     } while (0)
-#define FEDM_MG_TILE_S(WW, BASE)                                                                                  \
+#define FEDM_MG_TILE_S(WW)                                                                                        \
     do {                                                                                                          \
-        if (slots <= 2) FEDM_MG_TILE(WW, 2, BASE);                                                                \
-        else if (slots <= 3) FEDM_MG_TILE(WW, 3, BASE + 1);                                                       \
+        if (slots <= 2) FEDM_MG_TILE(WW, 2);                                                                      \
+        else if (slots <= 3) FEDM_MG_TILE(WW, 3);                                                                 \
         else return false;                                                                                        \
     } while (0)
-    if (ft->width <= 7) FEDM_MG_TILE_S(7, 0);
-    else if (ft->width <= 9) FEDM_MG_TILE_S(9, 2);
-    else FEDM_MG_TILE_S(12, 4);
+    if (ft->width <= 7) FEDM_MG_TILE_S(7);
+    else if (ft->width <= 9) FEDM_MG_TILE_S(9);
+    else FEDM_MG_TILE_S(12);
 #undef FEDM_MG_TILE_S
 #undef FEDM_MG_TILE
     if (hipPeekAtLastError() != hipSuccess) {

@@ -5,16 +5,22 @@
 //                                                         examples/glow_discharge/fedm-gd.py:354-359
 //   * 'flux source' walls with reflection and secondary emission    fedm/functions.py:514-522
 //   * Poisson                                              fedm/functions.py:401
-// The residual is written once on "value + spatial gradient" objects over a forward-mode
-// dual scalar; the element Jacobian is obtained column by column (one dual direction per
-// local dof), which is exact like UFL's `derivative` (fedm-gd.py:402) without a hand
-// derivation of the many cross terms.  Cells of one colour per launch (conflict-free
-// read-modify-write, bitwise reproducible); one thread per cell for the residual, one thread
-// per (cell, local dof) for the Jacobian -- a colour alone has too few cells to fill the chip.
+// What the file holds:
+//   * gd_jacobian_rows_kernel: residual and Jacobian from HAND-DERIVED element blocks, all cells in one launch, a
+//     workgroup per 64 cells with its waves on the equation rows; the blocks go into the matrix with atomics, or into
+//     an element buffer (in cell order or in the order of their destinations) that a gather sums in a fixed order
+//     (gd_gather_kernel, gd_gather_dest_kernel, gd_gather_dest_rows_kernel; gd_gather_residual_kernel for F).  This
+//     is what runs.
+//   * gd_assemble_kernel, the cross-check of the hand derivation (FEDM_GD_HAND=0): the residual written once on "value +
+//     spatial gradient" objects over a forward-mode dual scalar, the element Jacobian column by column (one dual
+//     direction per local dof), exact like UFL's `derivative` (fedm-gd.py:402).  Cells of one colour per launch
+//     (conflict-free read-modify-write, bitwise reproducible); one thread per cell for the residual, one per (cell,
+//     local dof) for the Jacobian.
+//   * the host side at the end: gd_elem_setup (element buffers and inverse maps, at first use), gd_plan (every choice
+//     an assembly makes, from the switches read when the context was created) and launch_assemble_gd.
 #include "fedm_internal.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 namespace fedm {
@@ -495,14 +501,11 @@ __device__ __forceinline__ GdFluxD gd_flux_partials(const double *fl, int f_mu, 
 // value written once, fixed summation order; 1 = fp64 atomics straight into the matrix (the fall-back
 // when the buffer cannot be allocated).  The residual is added with atomics.
 // STORE 0: residual only (launched with one column vertex: gridDim.y = 1).
-// NRC, NQC > 0: the numbers of reactions and of quadrature points at compile time (the loops over them
-// unroll, the model's scalars -- weights, powers, points -- are loaded once instead of by a dependent
-// scalar load and a wait in every pass of the innermost loops); 0: taken from the descriptor.
 // BALL (round 4): the three column vertices side by side -- 45 + 9 accumulators, the point functions evaluated ONCE
 // per quadrature point instead of once per column vertex.  That is the variant that spilled 600 bytes at two waves
 // per SIMD; here it runs at ONE wave per SIMD with the whole 512-entry register file: a
 // third of the instructions per wave for half the resident waves.
-template <int NEQ, int STORE, int NRC = 0, int NQC = 0, bool BALL = false, int WV = 0>
+template <int NEQ, int STORE, bool BALL = false, int WV = 0>
 __global__ __launch_bounds__(64 * (NEQ - 1)) __attribute__((amdgpu_waves_per_eu(BALL ? 1 : 2, BALL ? 1 : 2))) void gd_jacobian_rows_kernel(
     const fedm_gd_desc *__restrict__ md, const double *__restrict__ fields, int nv,
     const int *__restrict__ cell_list, int n_cells, const int *__restrict__ cells,
@@ -522,8 +525,8 @@ __global__ __launch_bounds__(64 * (NEQ - 1)) __attribute__((amdgpu_waves_per_eu(
     const int lc = threadIdx.x & (SLICE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ci = blockIdx.x * SLICE + lc;
-    const int nr = NRC > 0 ? NRC : md->n_reactions;
-    const int nqp = NQC > 0 ? NQC : md->n_qp;
+    const int nr = md->n_reactions;
+    const int nqp = md->n_qp;
     const int NF = 4 * ns + 2 * nr + 3;
     extern __shared__ double gd_lds[];
     int *lds_vtx = reinterpret_cast<int *>(gd_lds);                 // [64][3] global vertex ids (-1: no cell)
@@ -1210,178 +1213,136 @@ static int gd_elem_setup(Ctx &c) {
     return 0;
 }
 
+// What one LMEA assembly launches.  gd_plan decides, from Ctx::gd_hand_mode / gd_waves / gd_gather (FEDM_GD_HAND,
+// FEDM_GD_WAVES, FEDM_GD_GATHER when the context is created), the model and the mesh; launch_assemble_gd only launches.
+//   hand mode 0: the dual-number kernel, a launch per colour (the cross-check of the hand-derived blocks)
+//             2: hand-derived blocks, fp64 atomics into the matrix
+//             4: ... through the element buffer in cell order + gather
+//             3: ... the buffer in the order of the blocks' destinations
+//             5 (default): ... with the three column vertices side by side (BALL)
+struct GdPlan {
+    enum Gather { NONE, CELLS, POSITIONS, ROWS };   // of the matrix: none, gd_gather_kernel, gd_gather_dest_kernel, .._rows_kernel
+    bool jacobian;
+    int mode;
+    int variant;             // fedm_launched_assembly's numbering: 4 = dual-number colours, 5 .. 8 = the hand-derived forms
+    int store, wv;           // STORE and WV of gd_jacobian_rows_kernel
+    bool ball;               // its BALL
+    Gather gather;
+    bool clear_val;          // the matrix is zeroed first (the gather writes every value of the rows it covers)
+    int row_first, row_last; // in Poisson-only mode the other rows keep their zeros (identity rows follow)
+    dim3 grid, block;
+    size_t lds_bytes;
+    int exp_table;           // exp(u) at the quadrature points kept in LDS
+    const uint32_t *slots;   // d_cell_slots, or d_gd_kpos for the buffer in destination order
+    double *val, *elemF;     // d_val or d_gd_elem; d_gd_elemF (element residuals, summed per vertex in a fixed order) or null (atomics)
+};
+
+// two waves a workgroup taking two rows each in turn: for an even number of rows, and more than two of them
+constexpr bool gd_two_waves_apply(int neq) { return (neq - 1) % 2 == 0 && neq > 3; }
+
+static GdPlan gd_plan(Ctx &c, bool jacobian, int mode) {
+    GdPlan p{};
+    p.jacobian = jacobian;
+    p.mode = mode;
+    p.row_first = mode == 1 ? c.neq - 1 : 0;
+    p.row_last = c.neq - 1;
+    const int hand = c.gd_hand_mode;
+    if (hand < 2) {   // a grid per colour: gd_launch
+        p.variant = 4;
+        p.block = dim3(128);
+        p.clear_val = jacobian;
+        return p;
+    }
+    // the element buffers: the Jacobian's from mode 3 on, the residual's with the destination order only; built at
+    // first use, and the atomics where they cannot be
+    const bool dest_order = hand == 3 || hand == 5;
+    const bool wanted = jacobian ? hand >= 3 : dest_order;
+    const bool buffers = wanted && gd_elem_setup(c) == 0;
+    p.variant = hand == 2 || (wanted && !buffers) ? 5 : hand == 4 ? 6 : hand == 3 ? 7 : 8;
+    p.store = !jacobian ? 0 : !buffers ? 1 : dest_order ? 3 : 2;
+    p.ball = jacobian && buffers && hand == 5;
+    p.grid = dim3((unsigned)((c.nc + SLICE - 1) / SLICE), 1);
+    // BALL, two waves a workgroup, two workgroups a CU: the set-up is paid once for two rows and the rows balance -- 509
+    // against 558 us at 402 k DOFs (2 500 workgroups), 268 against 260 us at 200 k (1 243: the rounds of workgroups
+    // quantise the same way): from six workgroups a CU on (FEDM_GD_WAVES=rows / two: whatever the size)
+    if (p.ball && gd_two_waves_apply(c.neq) &&
+        (c.gd_waves == 't' || (c.gd_waves != 'r' && (long long)p.grid.x >= 6LL * 256)))
+        p.wv = 2;
+    p.block = dim3(SLICE * (p.wv ? p.wv : c.neq - 1));
+    // the gather's thread mapping: a thread per (position, equation row) by default (measured at 200 k DOFs, F + J:
+    // 353 us with a thread per position, 287-296 us per (position, row), the same per (position, plane))
+    if (jacobian && buffers) p.gather = !dest_order ? GdPlan::CELLS : c.gd_gather == 'r' ? GdPlan::ROWS : GdPlan::POSITIONS;
+    p.clear_val = jacobian && (!buffers || mode != 0);
+    p.lds_bytes = sizeof(double) * ((size_t)(3 * SLICE + 1) / 2 + (size_t)SLICE * c.gd_n_fields * 3 + (size_t)SLICE * 3 * c.neq);
+    // table of exp(u) at the quadrature points, while two workgroups still fit a CU's 160 KB
+    const size_t lds_table = sizeof(double) * (size_t)c.gd.n_qp * c.neq * SLICE;
+    p.exp_table = p.lds_bytes + lds_table <= 80 * 1024 ? 1 : 0;
+    if (p.exp_table) p.lds_bytes += lds_table;
+    p.lds_bytes += (size_t)(c.neq - 1) * FEDM_GD_MAX_REACTIONS * 12 + FEDM_GD_MAX_REACTIONS * 4 + 8;   // the rows' reaction weights and powers, the sentinel list
+    p.slots = p.store == 3 ? c.d_gd_kpos : c.d_cell_slots;
+    p.val = p.store == 0 ? nullptr : p.store == 1 ? c.d_val : c.d_gd_elem;
+    p.elemF = buffers ? c.d_gd_elemF : nullptr;
+    return p;
+}
+
+template <int NEQ>
+static void gd_launch(Ctx &c, const GdPlan &p) {
+    if (p.variant == 4) {
+        const int ncol = (int)c.pat.colour_ptr.size() - 1;
+        for (int k = 0; k < ncol; ++k) {
+            const int n = c.pat.colour_ptr[k + 1] - c.pat.colour_ptr[k];
+            if (n == 0) continue;
+            const size_t threads = p.jacobian ? (size_t)n * 3 * c.neq : (size_t)n;
+            const dim3 g((unsigned)((threads + p.block.x - 1) / p.block.x));
+            hipLaunchKernelGGL((gd_assemble_kernel<NEQ>), g, p.block, 0, c.stream, c.d_gd, c.d_gd_fields, c.nv,
+                               c.d_colour_cells + c.pat.colour_ptr[k], n, c.d_cells, c.d_coords, c.d_ftags,
+                               c.d_cell_slots, c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, c.d_val, c.d_F,
+                               p.jacobian ? 1 : 0, p.mode);
+            note_assembly_launch(c, p.jacobian, p.variant, (int)p.block.x, (int)g.x);
+        }
+        return;
+    }
+    // all cells in one launch; the Jacobian and the residual-only form are the same point functions
+    auto element = [&](auto kernel) {
+        grant_dynamic_lds(kernel, c.device, p.lds_bytes);
+        hipLaunchKernelGGL(kernel, p.grid, p.block, p.lds_bytes, c.stream, c.d_gd, c.d_gd_fields, c.nv,
+                           (const int *)nullptr, c.nc, c.d_cells, c.d_coords, c.d_ftags, p.slots, c.d_u, c.d_uold,
+                           c.d_uold1, c.dt, c.dt_old, p.val, c.d_F, p.mode, p.elemF, p.exp_table);
+        note_assembly_launch(c, p.jacobian, p.variant, (int)p.block.x, (int)p.grid.x);
+    };
+    constexpr int WV2 = gd_two_waves_apply(NEQ) ? 2 : 0;   // (p.wv is 2 only where this is)
+    if (p.store == 0) element(gd_jacobian_rows_kernel<NEQ, 0>);
+    else if (p.store == 1) element(gd_jacobian_rows_kernel<NEQ, 1>);
+    else if (p.store == 2) element(gd_jacobian_rows_kernel<NEQ, 2>);
+    else if (!p.ball) element(gd_jacobian_rows_kernel<NEQ, 3>);
+    else if (!p.wv) element(gd_jacobian_rows_kernel<NEQ, 3, true>);
+    else element(gd_jacobian_rows_kernel<NEQ, 3, true, WV2>);
+    const int n_pos = (int)(c.pat.total_bc * SLICE);
+    const dim3 b(256), g_pos((n_pos + 255) / 256);
+    if (p.gather == GdPlan::ROWS)
+        hipLaunchKernelGGL((gd_gather_dest_rows_kernel<NEQ>), dim3(g_pos.x, p.row_last - p.row_first + 1), b, 0, c.stream,
+                           n_pos, c.d_gd_inv_ptr, c.d_gd_elem, c.d_val, p.row_first, p.row_last, c.nc);
+    else if (p.gather == GdPlan::POSITIONS)
+        hipLaunchKernelGGL((gd_gather_dest_kernel<NEQ>), g_pos, b, 0, c.stream, n_pos, c.d_gd_inv_ptr, c.d_gd_elem,
+                           c.d_val, p.row_first, p.row_last, c.nc);
+    else if (p.gather == GdPlan::CELLS)
+        hipLaunchKernelGGL((gd_gather_kernel<NEQ>), g_pos, b, 0, c.stream, n_pos, c.d_gd_inv_ptr, c.d_gd_inv_idx,
+                           c.d_gd_elem, c.d_val, p.row_first, p.row_last, c.nc);
+    if (p.elemF)
+        hipLaunchKernelGGL((gd_gather_residual_kernel<NEQ>), dim3((c.nv + 255) / 256), b, 0, c.stream, c.nv,
+                           c.d_gd_vinv_ptr, c.d_gd_vinv_idx, p.elemF, c.d_F, p.row_first, c.nc);
+}
+
 void launch_assemble_gd(Ctx &c, bool jacobian, int mode) {
     hipMemsetAsync(c.d_F, 0, sizeof(double) * c.np, c.stream);
-    const int ncol = (int)c.pat.colour_ptr.size() - 1;
-    // Ctx::gd_hand_mode (FEDM_GD_HAND when the context is created): 0 = dual numbers, a launch per
-    // colour (the cross-check of the hand-derived blocks), 2 = hand-derived blocks, fp64 atomics into the
-    // matrix, 3 (default) = hand-derived blocks, element buffer in destination order + gather, 4 = the buffer in cell order
-    const int hand_mode = c.gd_hand_mode;
-    if (jacobian && hand_mode >= 2) {
-        // in Poisson-only mode the other rows keep the zeros of the memset (identity rows follow)
-        const int n = c.nc;
-        const bool gather = hand_mode >= 3 && gd_elem_setup(c) == 0;
-        const bool dest_order = hand_mode == 3 || hand_mode == 5;   // (4: the buffer in cell order, round 2's layout)
-        const bool ball = hand_mode == 5;
-        // the gather's thread mapping: a thread per (position, equation row) by default (measured at 200 k DOFs, F + J:
-        // 353 us with a thread per position, 287-296 us per (position, row), the same per (position, plane));
-        // FEDM_GD_GATHER=positions|rows
-        const char *gd_waves_env = std::getenv("FEDM_GD_WAVES");     // (per launch: the tests switch it)
-        const char gd_waves_mode = gd_waves_env ? gd_waves_env[0] : 'a';
-        static const char gather_kind = [] {
-            const char *e = std::getenv("FEDM_GD_GATHER");
-            return e ? e[0] : 'r';
-        }();
-        const bool gather_rows = gather_kind == 'r';
-        if (!gather || mode != 0)   // (the gather writes every value of the rows it covers)
-            hipMemsetAsync(c.d_val, 0, sizeof(double) * (size_t)c.pat.total_bc * SLICE * c.neq * c.neq, c.stream);
-        const int cpb = SLICE, nf = c.gd_n_fields;
-        size_t lds_h = sizeof(double) * ((size_t)(3 * cpb + 1) / 2 + (size_t)cpb * nf * 3 + (size_t)cpb * 3 * c.neq);
-        // table of exp(u) at the quadrature points, while two workgroups still fit a CU's 160 KB
-        const size_t lds_table = sizeof(double) * (size_t)c.gd.n_qp * c.neq * cpb;
-        const int exp_table = lds_h + lds_table <= 80 * 1024 ? 1 : 0;
-        if (exp_table) lds_h += lds_table;
-        lds_h += (size_t)(c.neq - 1) * FEDM_GD_MAX_REACTIONS * 12 + FEDM_GD_MAX_REACTIONS * 4 + 8;   // the rows' reaction weights and powers, the sentinel list
-        const dim3 gh((unsigned)((n + cpb - 1) / cpb), 1), bh(SLICE * (c.neq - 1));
-        const int n_pos = (int)(c.pat.total_bc * SLICE);
-        const int row_first = mode == 1 ? c.neq - 1 : 0, row_last = c.neq - 1;
-#define FEDM_GD_HAND_LAUNCH(NEQ, NRC, NQC)                                                                               \
-    do {                                                                                                          \
-        static bool lds_attr_set = false;   /* per instantiation: a property of these kernels */            \
-        if (lds_h > 64 * 1024 && !lds_attr_set) {   /* more dynamic LDS than the default limit */               \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&gd_jacobian_rows_kernel<NEQ, 3, NRC, NQC>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);                          \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&gd_jacobian_rows_kernel<NEQ, 2, NRC, NQC>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);                          \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&gd_jacobian_rows_kernel<NEQ, 1, NRC, NQC>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);                          \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&gd_jacobian_rows_kernel<NEQ, 0, NRC, NQC>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);                          \
-            lds_attr_set = true;                                                                                  \
-        }                                                                                                         \
-        if (gather && dest_order) {                                                                               \
-            if (ball) {                                                                                           \
-                /* two waves a workgroup, each taking two rows in turn, two workgroups a CU: the set-up is paid once for two   \
-                 * rows and the rows balance -- 509 against 558 us at 402 k DOFs (2 500 workgroups), 268 against 260 us at      \
-                 * 200 k (1 243: the rounds of workgroups quantise the same way): from six workgroups a CU on                  \
-                 * (FEDM_GD_WAVES=rows / two: a wave per row / two waves, whatever the size) */                                 \
-                constexpr int WV2 = (NEQ - 1) % 2 == 0 && NEQ > 3 ? 2 : 0;                                        \
-                if (WV2 && (gd_waves_mode == 't' || (gd_waves_mode != 'r' && (long long)gh.x >= 6LL * 256))) {   \
-                    static bool ball2_attr_set = false;                                                           \
-                    if (lds_h > 64 * 1024 && !ball2_attr_set) {                                                   \
-                        hipFuncSetAttribute(reinterpret_cast<const void *>(&gd_jacobian_rows_kernel<NEQ, 3, NRC, NQC, true, WV2>), \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);              \
-                        ball2_attr_set = true;                                                                    \
-                    }                                                                                             \
-                    hipLaunchKernelGGL((gd_jacobian_rows_kernel<NEQ, 3, NRC, NQC, true, WV2>), gh, dim3(SLICE * (WV2 ? WV2 : 1)), lds_h, c.stream, c.d_gd, c.d_gd_fields, \
-                                       c.nv, (const int *)nullptr, n, c.d_cells, c.d_coords, c.d_ftags, c.d_gd_kpos, \
-                                       c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, c.d_gd_elem, c.d_F, mode, c.d_gd_elemF, exp_table); \
-                } else {                                                                                          \
-                static bool ball_attr_set = false;                                                                \
-                if (lds_h > 64 * 1024 && !ball_attr_set) {                                                        \
-                    hipFuncSetAttribute(reinterpret_cast<const void *>(&gd_jacobian_rows_kernel<NEQ, 3, NRC, NQC, true>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);                  \
-                    ball_attr_set = true;                                                                         \
-                }                                                                                                 \
-                hipLaunchKernelGGL((gd_jacobian_rows_kernel<NEQ, 3, NRC, NQC, true>), gh, bh, lds_h, c.stream, c.d_gd, c.d_gd_fields, \
-                                   c.nv, (const int *)nullptr, n, c.d_cells, c.d_coords, c.d_ftags, c.d_gd_kpos,  \
-                                   c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, c.d_gd_elem, c.d_F, mode, c.d_gd_elemF, exp_table); \
-                }                                                                                                 \
-            } else                                                                                                \
-            hipLaunchKernelGGL((gd_jacobian_rows_kernel<NEQ, 3, NRC, NQC>), gh, bh, lds_h, c.stream, c.d_gd, c.d_gd_fields, \
-                               c.nv, (const int *)nullptr, n, c.d_cells, c.d_coords, c.d_ftags, c.d_gd_kpos,      \
-                               c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, c.d_gd_elem, c.d_F, mode, c.d_gd_elemF, exp_table); \
-            if (gather_rows)                                                                                      \
-                hipLaunchKernelGGL((gd_gather_dest_rows_kernel<NEQ>), dim3((n_pos + 255) / 256, row_last - row_first + 1), \
-                                   dim3(256), 0, c.stream, n_pos, c.d_gd_inv_ptr, c.d_gd_elem, c.d_val, row_first, row_last, n); \
-            else                                                                                                  \
-            hipLaunchKernelGGL((gd_gather_dest_kernel<NEQ>), dim3((n_pos + 255) / 256), dim3(256), 0, c.stream, n_pos, \
-                               c.d_gd_inv_ptr, c.d_gd_elem, c.d_val, row_first, row_last, n);                     \
-            hipLaunchKernelGGL((gd_gather_residual_kernel<NEQ>), dim3((c.nv + 255) / 256), dim3(256), 0, c.stream, \
-                               c.nv, c.d_gd_vinv_ptr, c.d_gd_vinv_idx, c.d_gd_elemF, c.d_F, row_first, n);        \
-        } else if (gather) {                                                                                      \
-            hipLaunchKernelGGL((gd_jacobian_rows_kernel<NEQ, 2, NRC, NQC>), gh, bh, lds_h, c.stream, c.d_gd, c.d_gd_fields, \
-                               c.nv, (const int *)nullptr, n, c.d_cells, c.d_coords, c.d_ftags, c.d_cell_slots,   \
-                               c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, c.d_gd_elem, c.d_F, mode, c.d_gd_elemF, exp_table); \
-            hipLaunchKernelGGL((gd_gather_kernel<NEQ>), dim3((n_pos + 255) / 256), dim3(256), 0, c.stream, n_pos, \
-                               c.d_gd_inv_ptr, c.d_gd_inv_idx, c.d_gd_elem, c.d_val, row_first, row_last, n);     \
-            hipLaunchKernelGGL((gd_gather_residual_kernel<NEQ>), dim3((c.nv + 255) / 256), dim3(256), 0, c.stream, \
-                               c.nv, c.d_gd_vinv_ptr, c.d_gd_vinv_idx, c.d_gd_elemF, c.d_F, row_first, n);        \
-        } else {                                                                                                  \
-            hipLaunchKernelGGL((gd_jacobian_rows_kernel<NEQ, 1, NRC, NQC>), gh, bh, lds_h, c.stream, c.d_gd, c.d_gd_fields, \
-                               c.nv, (const int *)nullptr, n, c.d_cells, c.d_coords, c.d_ftags, c.d_cell_slots,   \
-                               c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, c.d_val, c.d_F, mode, (double *)nullptr, exp_table); \
-        }                                                                                                         \
-    } while (0)
-        switch (c.neq) {
-            case 3: FEDM_GD_HAND_LAUNCH(3, 0, 0); break;
-            case 4: FEDM_GD_HAND_LAUNCH(4, 0, 0); break;
-            case 5: FEDM_GD_HAND_LAUNCH(5, 0, 0); break;
-            case 6: FEDM_GD_HAND_LAUNCH(6, 0, 0); break;
-        }
-#undef FEDM_GD_HAND_LAUNCH
-        return;
-    }
-    if (!jacobian && hand_mode >= 2) {
-        // residual only: the same point functions without the derivative columns, all cells in one
-        // launch; element residuals summed per vertex (no atomics: fixed order)
-        const int n = c.nc;
-        double *elemF = ((hand_mode == 3 || hand_mode == 5) && gd_elem_setup(c) == 0) ? c.d_gd_elemF : nullptr;
-        size_t lds_h = sizeof(double) * ((size_t)(3 * SLICE + 1) / 2 + (size_t)SLICE * c.gd_n_fields * 3 +
-                                         (size_t)SLICE * 3 * c.neq);
-        const size_t lds_table = sizeof(double) * (size_t)c.gd.n_qp * c.neq * SLICE;
-        const int exp_table = lds_h + lds_table <= 80 * 1024 ? 1 : 0;
-        if (exp_table) lds_h += lds_table;
-        lds_h += (size_t)(c.neq - 1) * FEDM_GD_MAX_REACTIONS * 12 + FEDM_GD_MAX_REACTIONS * 4 + 8;
-        const dim3 gh((unsigned)((n + SLICE - 1) / SLICE), 1), bh(SLICE * (c.neq - 1));
-        const int row_first = mode == 1 ? c.neq - 1 : 0;
-#define FEDM_GD_RES_LAUNCH(NEQ, NRC, NQC)                                                                                \
-    do {                                                                                                          \
-        static bool lds_attr_set = false;                                                                         \
-        if (lds_h > 64 * 1024 && !lds_attr_set) {                                                                 \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&gd_jacobian_rows_kernel<NEQ, 2, NRC, NQC>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);                          \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&gd_jacobian_rows_kernel<NEQ, 1, NRC, NQC>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);                          \
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&gd_jacobian_rows_kernel<NEQ, 0, NRC, NQC>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h);                          \
-            lds_attr_set = true;                                                                                  \
-        }                                                                                                         \
-        hipLaunchKernelGGL((gd_jacobian_rows_kernel<NEQ, 0, NRC, NQC>), gh, bh, lds_h, c.stream, c.d_gd, c.d_gd_fields,     \
-                           c.nv, (const int *)nullptr, n, c.d_cells, c.d_coords, c.d_ftags, c.d_cell_slots,       \
-                           c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, (double *)nullptr, c.d_F, mode, elemF, exp_table); \
-        if (elemF)                                                                                                \
-            hipLaunchKernelGGL((gd_gather_residual_kernel<NEQ>), dim3((c.nv + 255) / 256), dim3(256), 0, c.stream, \
-                               c.nv, c.d_gd_vinv_ptr, c.d_gd_vinv_idx, elemF, c.d_F, row_first, n);               \
-    } while (0)
-        switch (c.neq) {
-            case 3: FEDM_GD_RES_LAUNCH(3, 0, 0); break;
-            case 4: FEDM_GD_RES_LAUNCH(4, 0, 0); break;
-            case 5: FEDM_GD_RES_LAUNCH(5, 0, 0); break;
-            case 6: FEDM_GD_RES_LAUNCH(6, 0, 0); break;
-        }
-#undef FEDM_GD_RES_LAUNCH
-        return;
-    }
-    if (jacobian)
+    const GdPlan p = gd_plan(c, jacobian, mode);
+    if (p.clear_val)
         hipMemsetAsync(c.d_val, 0, sizeof(double) * (size_t)c.pat.total_bc * SLICE * c.neq * c.neq, c.stream);
-    for (int k = 0; k < ncol; ++k) {
-        const int n = c.pat.colour_ptr[k + 1] - c.pat.colour_ptr[k];
-        if (n == 0) continue;
-        const size_t threads = jacobian ? (size_t)n * 3 * c.neq : (size_t)n;
-        const dim3 g((unsigned)((threads + 127) / 128)), b(128);
-#define FEDM_GD_LAUNCH(NEQ)                                                                        \
-    hipLaunchKernelGGL((gd_assemble_kernel<NEQ>), g, b, 0, c.stream, c.d_gd, c.d_gd_fields, c.nv,   \
-                       c.d_colour_cells + c.pat.colour_ptr[k], n, c.d_cells, c.d_coords, c.d_ftags, \
-                       c.d_cell_slots, c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, c.d_val, c.d_F,  \
-                       jacobian ? 1 : 0, mode)
-        switch (c.neq) {
-            case 3: FEDM_GD_LAUNCH(3); break;
-            case 4: FEDM_GD_LAUNCH(4); break;
-            case 5: FEDM_GD_LAUNCH(5); break;
-            case 6: FEDM_GD_LAUNCH(6); break;
-        }
-#undef FEDM_GD_LAUNCH
+    switch (c.neq) {
+        case 3: gd_launch<3>(c, p); break;
+        case 4: gd_launch<4>(c, p); break;
+        case 5: gd_launch<5>(c, p); break;
+        case 6: gd_launch<6>(c, p); break;
     }
 }
 

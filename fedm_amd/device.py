@@ -364,7 +364,10 @@ SOLVER_PATH_STATS = ("cycles", "steps_single", "steps_pair", "steps_last", "step
                      "verify_failed")
 
 # fedm_pattern_info's / fedm_launched_assembly's numbering of the volume-assembly kernels
-_VARIANTS = ("global colouring", "lds-patches/unrolled", "lds-patches", "lds-patches/one-pass")
+_VARIANTS = ("global colouring", "lds-patches/unrolled", "lds-patches", "lds-patches/one-pass",
+             # the LMEA family's element kernels (fedm_launched_assembly only)
+             "lmea/dual-number colours", "lmea/atomics", "lmea/element buffer, cell order",
+             "lmea/element buffer, destination order", "lmea/element buffer, destination order, columns side by side")
 
 
 class DeviceProblem:

@@ -476,10 +476,14 @@ int fedm_pattern_stats(const fedm_mesh_desc *mesh, int64_t out[12]);
  * its numbers read at run time}.  The variant can change after the first Jacobian: that one writes all planes, the
  * later ones keep the constant planes and need less LDS. */
 int fedm_pattern_info(fedm_ctx *ctx, int64_t out[9]);
-/* The volume-assembly kernels the last residual-only assembly and the last Jacobian assembly of the LFA family
- * actually launched: out = {residual: variant (fedm_pattern_info's numbering; -1: none yet), threads per workgroup,
- * launches, workgroups of all launches; Jacobian: the same four}.  With several launches (the halo-overlap halves,
- * the colouring's colours, FEDM_LEAN3_CLASSES) variant and threads are the last one's. */
+/* The volume-assembly kernels the last residual-only assembly and the last Jacobian assembly actually launched:
+ * out = {residual: variant (-1: none yet), threads per workgroup, launches, workgroups of all launches; Jacobian: the
+ * same four}.  Variants 0..3 are fedm_pattern_info's (LFA family); the LMEA family's element kernels follow: 4
+ * dual-number kernel per colour (FEDM_GD_HAND=0), 5 hand-derived blocks added with atomics (2, and the fall-back when
+ * the element buffers cannot be allocated), 6 through the element buffer in cell order (4), 7 in the order of the
+ * blocks' destinations (3), 8 the same with the three column vertices side by side (5); their gathers are not counted.
+ * With several launches (the halo-overlap halves, the colouring's colours, FEDM_LEAN3_CLASSES) variant and threads are
+ * the last one's. */
 int fedm_launched_assembly(fedm_ctx *ctx, int64_t out[8]);
 /* Which branches of the GMRES driver and of the Newton loop have run on this context since it was created (or since
  * the last call with reset != 0): host counters, nothing is added on the device.  out (may be NULL with reset) =

@@ -15,29 +15,27 @@ DECK = ROOT / "decks" / "glow_discharge" / "file_input" / "4_particles"
 SENTINEL_LOSSES = [11.55, 7.77e77, -11.55, 4.21, -7.34, 0.0, 9.99e99]
 
 
-@pytest.mark.parametrize("losses", ["deck", "sentinels"])
-@pytest.mark.parametrize("variant", ["5", "3", "4", "2", "0"])
-def test_gd_residual_and_jacobian_match_the_oracle(variant, losses, monkeypatch):
-    """LMEA element Jacobian against the oracle for the device variants (csrc/gd.hip): hand-derived blocks with
-    the three column vertices side by side at one wave per SIMD (5), one column vertex per pass (3), both
-    through the element buffer in the order of their destinations + gather, the buffer in cell
-    order (4, round 2's layout), the same blocks added with atomics (2), and the dual-number kernel (0) that
-    cross-checks the hand derivation.  "sentinels": the ionisation loses Ei - mean energy and the elastic collisions
-    the mean energy itself, as the decks' sentinel loss values ask (fedm/functions.py:906-909), with the mean-energy
-    argument the scripts pass, u[0] / u[n - 1] -- two more columns in the energy row's derivative."""
+# fedm_launched_assembly's names (fedm_amd.device._VARIANTS) of the element kernels FEDM_GD_HAND selects
+LAUNCHED = {"0": "lmea/dual-number colours", "2": "lmea/atomics", "4": "lmea/element buffer, cell order",
+            "3": "lmea/element buffer, destination order",
+            "5": "lmea/element buffer, destination order, columns side by side"}
+_REFERENCE = {}
+
+
+def _reference(case, losses="deck", degree=4):
+    """The oracle's F and J at a perturbed state of the 10 x 10 crossed mesh (221 vertices, 400 cells: seven workgroups
+    of 64 cells, the last with 16, and a position count that is no multiple of 256), with the state and the nodal
+    fields they were computed from.  Computed once per (losses, quadrature degree) and read-only from then on."""
     from oracle import gd as ogd
-    from fedm_amd.cases import glow_discharge as gdc
-    monkeypatch.setenv("FEDM_GD_HAND", variant)
-    # (variant 5 on a mesh of this size runs a wave per row; "sentinels" also takes its two-wave workgroups, which
-    # large meshes get: two rows a wave in turn)
-    monkeypatch.setenv("FEDM_GD_WAVES", "two" if losses == "sentinels" else "auto")
-    extra = dict(energy_loss=SENTINEL_LOSSES, energy_Ei=15.76) if losses == "sentinels" else {}
-    case = gdc.Case(nx=10, ny=10, device_pipeline=False, **extra)
+    from oracle.quadrature import interval_rule, triangle_rule
+    if (losses, degree) in _REFERENCE:
+        return _REFERENCE[losses, degree]
     o = ogd.GlowDischarge(DECK, 10, 10)
+    o.xq, o.wq = triangle_rule(degree)       # (nothing else in the oracle depends on the rule)
+    o.tq, o.wt = interval_rule(degree)
     if losses == "sentinels":
         o.deck.energy_loss, o.deck.energy_Ei = list(SENTINEL_LOSSES), 15.76
     nv = o.mesh.nv
-    assert np.array_equal(o.mesh.cells, case.mesh.cells)
     rng = np.random.default_rng(0)
     me_old = 3.0 + rng.normal(0, 0.3, nv)
     me = me_old + rng.normal(0, 0.05, nv)
@@ -48,38 +46,158 @@ def test_gd_residual_and_jacobian_match_the_oracle(variant, losses, monkeypatch)
     Uo = U + rng.normal(0, 0.02, U.shape)
     Uo1 = U + rng.normal(0, 0.02, U.shape)
     redE = o.reduced_field(U[:, 4])
-    assert np.allclose(case.project_reduced_field(U[:, 4]), redE, rtol=1e-12)
     co = o.coefficients(me_old, redE)
     t, dt, dt_old = 2e-12, 1.1e-12, 0.7e-12
-    dv = o.dirichlet_values(t)
-    F_cpu, J_cpu = o.residual_jacobian(U, Uo, Uo1, dt, dt_old, co, me_old, me, Uo[:, 3], dv)
-    # same nodal fields through the product pipeline
-    case.mean_energy_old.vector()[:] = me_old
-    case.mean_energy.vector()[:] = me
-    case.redE.vector()[:] = redE
+    F_cpu, J_cpu = o.residual_jacobian(U, Uo, Uo1, dt, dt_old, co, me_old, me, Uo[:, 3], o.dirichlet_values(t))
+    ref = dict(cells=o.mesh.cells, me_old=me_old, me=me, U=U, Uo=Uo, Uo1=Uo1, redE=redE, co=co, t=t, dt=dt,
+               dt_old=dt_old, F=F_cpu, J=J_cpu)
+    for v in ref.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    _REFERENCE[losses, degree] = ref
+    return ref
+
+
+def _upload(case, ref):
+    """The reference's state and nodal fields through the product pipeline onto the case's device problem."""
     from fedm_amd import functions as ff
+    assert np.array_equal(ref["cells"], case.mesh.cells)
+    assert np.allclose(case.project_reduced_field(ref["U"][:, 4]), ref["redE"], rtol=1e-12)
+    case.mean_energy_old.vector()[:] = ref["me_old"]
+    case.mean_energy.vector()[:] = ref["me"]
+    case.redE.vector()[:] = ref["redE"]
     ff.Transport_coefficient_interpolation("update", case.mu_dep, case.N0, case.Tgas, case.mu, case.mu_x,
                                            case.mu_y, case.mean_energy_old, case.redE)
     ff.Transport_coefficient_interpolation("update", case.D_dep, case.N0, case.Tgas, case.D, case.D_x,
                                            case.D_y, case.mean_energy_old, case.redE, case.mu)
     ff.Rate_coefficient_interpolation("update", case.k_dep, case.k, case.k_x, case.k_y,
                                       case.mean_energy_old, case.redE, Te=0, Tgas=0)
+    co = ref["co"]
     for a, b in zip(case.mu + case.D + case.k, co["mu"] + co["D"] + co["k"]):
         assert np.allclose(a.vector(), b, rtol=1e-14, atol=0)
-    case.U = Uo            # u_e_old field = old electron log density
+    case.U = ref["Uo"].copy()            # u_e_old field = old electron log density
     case.upload_fields()
     prob = case.prob
-    prob.set_state(U, Uo, Uo1)
-    prob.set_step(dt, dt_old)
-    prob.set_dirichlet_values(case.dirichlet_values(t))
-    F_gpu, _ = prob.residual()
+    prob.set_state(ref["U"], ref["Uo"], ref["Uo1"])
+    prob.set_step(ref["dt"], ref["dt_old"])
+    prob.set_dirichlet_values(case.dirichlet_values(ref["t"]))
+    return prob
+
+
+def _residual_error(F_gpu, F_cpu):
+    """largest error of F relative to the scale of its component"""
     scale = np.abs(F_cpu).reshape(-1, 5).max(axis=0)
-    assert (np.abs(F_gpu - F_cpu).reshape(-1, 5) / scale).max() < 1e-11
+    return (np.abs(F_gpu - F_cpu).reshape(-1, 5) / scale).max()
+
+
+def _jacobian_error(J_gpu, J_cpu):
+    """largest error of J relative to the largest entry of its row"""
+    rs = np.maximum(abs(J_cpu).max(axis=1).toarray().ravel(), 1e-300)
+    return (sp.diags(1.0 / rs) @ abs(J_gpu - J_cpu)).max()
+
+
+@pytest.mark.parametrize("losses", ["deck", "sentinels"])
+@pytest.mark.parametrize("variant", ["5", "3", "4", "2", "0"])
+def test_gd_residual_and_jacobian_match_the_oracle(variant, losses, monkeypatch):
+    """LMEA element Jacobian against the oracle for the device variants (csrc/gd.hip): hand-derived blocks with
+    the three column vertices side by side at one wave per SIMD (5), one column vertex per pass (3), both
+    through the element buffer in the order of their destinations + gather, the buffer in cell
+    order (4, round 2's layout), the same blocks added with atomics (2), and the dual-number kernel (0) that
+    cross-checks the hand derivation.  "sentinels": the ionisation loses Ei - mean energy and the elastic collisions
+    the mean energy itself, as the decks' sentinel loss values ask (fedm/functions.py:906-909), with the mean-energy
+    argument the scripts pass, u[0] / u[n - 1] -- two more columns in the energy row's derivative.
+    The launch record says which element kernel ran: the variant of FEDM_GD_HAND, one launch over the seven workgroups
+    of 64 cells (a launch per colour for the dual-number kernel), a wave per species/energy row -- or, for variant 5
+    under FEDM_GD_WAVES=two, the two-wave workgroups that large meshes get (two rows a wave in turn)."""
+    from fedm_amd.cases import glow_discharge as gdc
+    monkeypatch.setenv("FEDM_GD_HAND", variant)
+    monkeypatch.setenv("FEDM_GD_WAVES", "two" if losses == "sentinels" else "auto")
+    extra = dict(energy_loss=SENTINEL_LOSSES, energy_Ei=15.76) if losses == "sentinels" else {}
+    case = gdc.Case(nx=10, ny=10, device_pipeline=False, **extra)
+    ref = _reference(case, losses)
+    prob = _upload(case, ref)
+    F_gpu, _ = prob.residual()
+    assert _residual_error(F_gpu, ref["F"]) < 1e-11
     prob.jacobian()
     J_gpu = prob.jacobian_csr()
-    D = abs(J_gpu - J_cpu)
-    rs = np.maximum(abs(J_cpu).max(axis=1).toarray().ravel(), 1e-300)
-    assert (sp.diags(1.0 / rs) @ D).max() < 1e-9
+    assert _jacobian_error(J_gpu, ref["J"]) < 1e-9
+    rec = prob.launched_assembly()
+    n_colours = prob.sizes()["n_colours"]       # (greedy colouring: none of them is empty)
+    for what in ("residual", "jacobian"):
+        assert rec[what]["variant"] == LAUNCHED[variant], (what, rec)
+        assert rec[what]["launches"] == (n_colours if variant == "0" else 1), (what, rec)
+        if variant != "0":
+            two_waves = what == "jacobian" and variant == "5" and losses == "sentinels"
+            assert rec[what]["threads"] == (128 if two_waves else 256), (what, rec)
+            assert rec[what]["workgroups"] == 7, (what, rec)
+
+
+@pytest.mark.parametrize("variant", ["5", "3"])
+def test_gd_gathers_per_position_and_per_row_agree_bit_for_bit(variant, monkeypatch):
+    """The element buffer in destination order is summed into the matrix by a thread per stored position
+    (FEDM_GD_GATHER=positions, gd_gather_dest_kernel) or per (stored position, equation row) (rows, the default,
+    gd_gather_dest_rows_kernel).  Both add a position's contributions in list order, so J -- and F, which neither
+    touches -- are the same bits; "positions" is also held to the oracle.
+    The launch record names the element kernel only, so nothing here shows WHICH gather ran: that "positions" reaches
+    gd_gather_dest_kernel rests on the first letter of FEDM_GD_GATHER as csrc/context.cpp reads it (anything but 'r')."""
+    from fedm_amd.cases import glow_discharge as gdc
+    monkeypatch.setenv("FEDM_GD_HAND", variant)
+    out = {}
+    for gather in ("positions", "rows"):
+        monkeypatch.setenv("FEDM_GD_GATHER", gather)
+        case = gdc.Case(nx=10, ny=10, device_pipeline=False)
+        ref = _reference(case)
+        prob = _upload(case, ref)
+        F_gpu, _ = prob.residual()
+        prob.jacobian()
+        assert prob.launched_assembly()["jacobian"]["variant"] == LAUNCHED[variant]
+        out[gather] = (F_gpu, prob.residual_vector(), prob.jacobian_csr())
+        prob.close()
+    assert _residual_error(out["positions"][0], ref["F"]) < 1e-11
+    assert _residual_error(out["positions"][1], ref["F"]) < 1e-11
+    assert _jacobian_error(out["positions"][2], ref["J"]) < 1e-9
+    assert np.array_equal(out["positions"][0], out["rows"][0])
+    assert np.array_equal(out["positions"][1], out["rows"][1])
+    Jp, Jr = out["positions"][2], out["rows"][2]
+    assert np.array_equal(Jp.indptr, Jr.indptr) and np.array_equal(Jp.indices, Jr.indices)
+    assert np.array_equal(Jp.data, Jr.data)
+
+
+def _gd_lds_bytes(n_eq, n_fields, n_qp):
+    """Dynamic LDS of gd_jacobian_rows_kernel (csrc/gd.hip, gd_plan): vertex ids, nodal fields and unknowns of 64 cells,
+    the table of exp(u) at the quadrature points while it fits 80 KiB, the rows' reaction weights and powers."""
+    from fedm_amd import _lib
+    lds = 8 * ((3 * 64 + 1) // 2 + 64 * n_fields * 3 + 64 * 3 * n_eq)
+    table = 8 * n_qp * n_eq * 64
+    if lds + table <= 80 * 1024:
+        lds += table
+    return lds + (n_eq - 1) * _lib.GD_MAX_REACTIONS * 12 + _lib.GD_MAX_REACTIONS * 4 + 8
+
+
+def test_gd_second_context_with_a_larger_lds_need():
+    """Dynamic LDS beyond 64 KiB is opt-in per kernel.  The element kernel's need depends on the model (fields,
+    quadrature points), not on the mesh: a degree-2 case (3 points, 67 656 bytes) and then, in the same process, a
+    degree-4 case (6 points, 75 336 bytes) -- the second needs a larger grant than the first one set.  Both against
+    the oracle with its rule at the same degree.  (A refused launch is an error on the host and leaves F zero.)"""
+    from fedm_amd import quadrature
+    from fedm_amd.cases import glow_discharge as gdc
+    needs = []
+    for degree in (2, 4):
+        case = gdc.Case(nx=10, ny=10, device_pipeline=False, quadrature_degree=degree)
+        ref = _reference(case, degree=degree)
+        prob = _upload(case, ref)
+        needs.append(_gd_lds_bytes(5, prob.model.n_fields, len(quadrature.triangle(degree)[1])))
+        F_gpu, _ = prob.residual()
+        f_err = _residual_error(F_gpu, ref["F"])
+        prob.jacobian()
+        j_err = _jacobian_error(prob.jacobian_csr(), ref["J"])
+        fj_err = _residual_error(prob.residual_vector(), ref["F"])
+        print(f"degree {degree}: LDS {needs[-1]} bytes, F {f_err:.2e}, F of F + J {fj_err:.2e}, J {j_err:.2e}")
+        assert f_err < 1e-11 and fj_err < 1e-11, degree
+        assert j_err < 1e-9, degree
+        prob.close()
+    assert needs == [67656, 75336]
+    assert 64 * 1024 < needs[0] < needs[1]
 
 
 @pytest.mark.parametrize("cg", ["one launch", "launches"])

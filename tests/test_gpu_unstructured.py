@@ -221,6 +221,11 @@ def test_two_ranks_match_one_gpu_on_the_unstructured_mesh():
         assert np.allclose(np.array(r[3]), ref_log, rtol=1e-6)
 
 
+# fedm_launched_assembly's names of the LMEA element kernels FEDM_GD_HAND selects
+LMEA_LAUNCHED = {"0": "lmea/dual-number colours", "2": "lmea/atomics", "4": "lmea/element buffer, cell order",
+                 "3": "lmea/element buffer, destination order"}
+
+
 def test_lmea_kernels_on_an_unstructured_mesh(monkeypatch):
     """The glow-discharge (LMEA) assembly -- element buffer + gather by stored matrix position, coloured
     dual-number cross-check, 'flux source' walls -- has only ever run on DOLFIN's crossed meshes: residual
@@ -274,6 +279,8 @@ def test_lmea_kernels_on_an_unstructured_mesh(monkeypatch):
         prob.jacobian()
         J_gpu = prob.jacobian_csr()
         assert _rel_rows(J_gpu, J_cpu) < 1e-9, variant
+        rec = prob.launched_assembly()      # the element kernel of this FEDM_GD_HAND ran
+        assert rec["residual"]["variant"] == rec["jacobian"]["variant"] == LMEA_LAUNCHED[variant], rec
         prob.close()
 
 

@@ -1,5 +1,5 @@
 """Time of one LMEA F + J assembly (glow discharge, NxN crossed mesh: 200 -> 402k DOFs, 141 -> 200k), back to back.
-python tools/gd_kernel_time.py [N]     (FEDM_GD_HAND=0..5 selects the variant, FEDM_HIP_LIB an experiment build)"""
+python tools/gd_kernel_time.py [N]     (FEDM_GD_HAND=0|2|3|4|5 selects the variant, FEDM_HIP_LIB an experiment build)"""
 import sys, io, contextlib, os
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
