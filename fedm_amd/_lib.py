@@ -9,6 +9,7 @@ from pathlib import Path
 
 MAX_SPECIES, MAX_TERMS, MAX_REACTIONS, MAX_TAGS = 4, 6, 8, 8
 MAX_QP, MAX_FQP, MAX_EXT_NODES = 32, 8, 10
+MAX_TABLES, MAX_TABLE_KNOTS = 16, 4096
 
 EQ_TYPES = {"reaction": 0, "diffusion-reaction": 1, "drift-diffusion-reaction": 2}
 BC_KINDS = {"zero flux": 0, "Neumann": 1}
@@ -121,6 +122,8 @@ _SIGNATURES = {
     "fedm_last_error": (C.c_char_p, []),
     "fedm_abi_version": (C.c_int, []),
     "fedm_ctx_create": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(ModelDesc), C.c_int, C.POINTER(_P)]),
+    "fedm_ctx_create_tabulated": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(ModelDesc), C.c_int, C.POINTER(C.c_int32),
+                                            _D, _D, C.c_int, C.POINTER(_P)]),
     "fedm_ctx_create_gd": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(GdDesc), C.c_int, C.POINTER(_P)]),
     "fedm_gd_set_fields": (C.c_int, [_P, _D]),
     "fedm_gd_get_fields": (C.c_int, [_P, _D]),
@@ -253,6 +256,11 @@ def load():
     if lib.fedm_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH} implements ABI version {lib.fedm_abi_version()}, this binding was "
                            f"written against {ABI_VERSION} (include/fedm_hip.h FEDM_ABI_VERSION): rebuild it")
+    # (entry points added under one ABI version are not announced by it: the symbols themselves are checked)
+    missing = [name for name in _SIGNATURES if not hasattr(lib, name)]
+    if missing:
+        raise RuntimeError(f"{LIB_PATH} reports ABI version {ABI_VERSION} but lacks {', '.join(missing)} "
+                           "(include/fedm_hip.h): rebuild it")
     for name, (res, args) in _SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res

@@ -25,6 +25,7 @@ DECK = Path(__file__).resolve().parents[2] / "decks" / "streamer_discharge" / "f
 MU_E = "2.3987*E_m**(-0.26)"
 D_E = "4.3628e-3*E_m**(0.22)"
 ALPHA = "(1.1944e6 + 4.3666e26 * E_m**(-3))*exp(-2.73e7/E_m)-340.75"
+N0 = 760.0 * 3.21877e22       # gas number density at 760 Torr, 300 K [1/m^3]: what E/N tables are scaled with
 
 
 def model(mu_e=MU_E, D_e=D_E, alpha=ALPHA, quadrature_degree=2):
@@ -38,10 +39,19 @@ def model(mu_e=MU_E, D_e=D_E, alpha=ALPHA, quadrature_degree=2):
                  bc_kind=BC_TYPE, quadrature_degree=quadrature_degree)
 
 
+def _deck_coefficient(kx, ky, dependence):
+    """A transport coefficient as the deck readers return it: a number, a 'fun:E' string, or an E/N table
+    (kx in Td, ky = N0 * coefficient), which the element kernels look up at the cell's own |E|."""
+    if dependence == "E/N":
+        return TermSum.table(np.asarray(kx, dtype=np.float64) * N0 * 1e-21, ky) / N0
+    return TermSum.coerce(ky)
+
+
 def model_from_deck(file_input=DECK, model_name="benchmark_model", quadrature_degree=2):
     """The same model configured the way the script does it (fedm-streamer.py:47-53,
     227-245): species list, particle properties and transport coefficients through the
-    deck readers; the 'fun:E' strings are parsed, never eval'd."""
+    deck readers; the 'fun:E' strings are parsed, never eval'd.  ``tabulated_model`` holds the electrons'
+    coefficients and alpha / N0 as `Dependence: E/N` tables (tools/make_tabulated_deck.py)."""
     from .. import file_io, functions
     file_io.files.file_input = Path(file_input)
     path = file_io.files.file_input / model_name
@@ -49,12 +59,17 @@ def model_from_deck(file_input=DECK, model_name="benchmark_model", quadrature_de
     M, sign = file_io.read_particle_properties(prop_files, model_name)
     n_species, n_eq, species, M, sign = functions.modify_approximation_vars(
         "LFA", n_species, species, M, sign)
-    _, D_y, _ = file_io.read_transport_coefficients(species, "Diffusion", model_name)
-    _, mu_y, _ = file_io.read_transport_coefficients(species, "mobility", model_name)
-    alpha = file_io.read_single_string(path / "transport_coefficients" / "alpha.dat")
-    mu = [TermSum.coerce(v) for v in mu_y]
-    D = [TermSum.coerce(v) for v in D_y]
-    rate = parse(alpha) * mu[1] * TermSum.field()
+    D_x, D_y, D_dep = file_io.read_transport_coefficients(species, "Diffusion", model_name)
+    mu_x, mu_y, mu_dep = file_io.read_transport_coefficients(species, "mobility", model_name)
+    mu = [_deck_coefficient(*xyd) for xyd in zip(mu_x, mu_y, mu_dep)]
+    D = [_deck_coefficient(*xyd) for xyd in zip(D_x, D_y, D_dep)]
+    alpha_file = path / "transport_coefficients" / "alpha.dat"
+    if file_io.read_dependence(alpha_file) == "E/N":        # alpha / N0 against E/N
+        (a_x,), (a_y,) = file_io.read_rate_coefficients([alpha_file], ["E/N"])
+        alpha = TermSum.table(np.asarray(a_x, dtype=np.float64) * N0 * 1e-21, a_y) * N0
+    else:
+        alpha = parse(file_io.read_single_string(alpha_file))
+    rate = alpha * mu[1] * TermSum.field()
     return Model(n_species=n_species, poisson=True,
                  eq_type=["reaction", "drift-diffusion-reaction"], Z=sign, mu=mu, D=D,
                  reactions=[Reaction(rate, power=[0, 1], net=[1, 1])],
@@ -106,11 +121,14 @@ def initial_log_densities(coords):
     return u_ion, np.full_like(u_ion, np.log(1e13))
 
 
-def device_problem(coords, cells, device=0, **model_kw):
+def device_problem(coords, cells, device=0, deck_model=None, **model_kw):
+    """``deck_model``: the model of that deck folder (``model_from_deck``: "benchmark_model", "tabulated_model")
+    instead of the built-in strings."""
     msh = Mesh(coords, cells)
     tags = Marking_boundaries(msh, BOUNDARIES)
     dofs, vals = dirichlet(msh.coords)
-    return DeviceProblem(msh.coords, msh.cells, model(**model_kw), facet_tags=tags,
+    lfa = model_from_deck(model_name=deck_model, **model_kw) if deck_model else model(**model_kw)
+    return DeviceProblem(msh.coords, msh.cells, lfa, facet_tags=tags,
                          dirichlet_dofs=dofs, dirichlet_vals=vals, device=device)
 
 

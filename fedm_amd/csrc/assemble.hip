@@ -27,7 +27,7 @@ static void flush_pending_halo(Ctx &c) {
 // and the summation order is fixed -> bitwise reproducible).
 // Problem.F / Problem.J, fedm/functions.py:188-202
 // =============================================================================================
-template <int NS, bool PO, int NR, int CACHE, bool LIN>
+template <int NS, bool PO, int NR, int CACHE, bool LIN, bool TAB>
 __global__ __launch_bounds__(256) void assemble_colour_kernel(
     const fedm_model_desc *__restrict__ md, const int *__restrict__ cell_list, int n_cells,
     const int *__restrict__ cells, const double *__restrict__ coords,
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void assemble_colour_kernel(
     for (int s = 0; s < NS; ++s)
         ext[s] = (extp[s] && md->ext_nodes[s]) ? extp[s] + (size_t)c * md->ext_nodes[s] : nullptr;
 
-    Element<NS, PO, NR, CACHE, LIN> el;
+    Element<NS, PO, NR, CACHE, LIN, TAB> el;
     el.setup(md, x, Uc, Hc, sc, mode);
     uint32_t slot[9];
     if (jacobian) {
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void assemble_colour_kernel(
     }
 }
 
-template <int NS, bool PO, int NR, int CACHE, bool LIN>
+template <int NS, bool PO, int NR, int CACHE, bool LIN, bool TAB>
 static void assemble_colour_t(Ctx &c, bool jacobian, int mode) {
     constexpr int NEQ = NS + (PO ? 1 : 0);
     flush_pending_halo(c);
@@ -100,7 +100,7 @@ static void assemble_colour_t(Ctx &c, bool jacobian, int mode) {
     for (int k = 0; k < ncol; ++k) {
         const int n = c.pat.colour_ptr[k + 1] - c.pat.colour_ptr[k];
         if (n == 0) continue;
-        hipLaunchKernelGGL((assemble_colour_kernel<NS, PO, NR, CACHE, LIN>), dim3((n + 255) / 256), dim3(256), 0,
+        hipLaunchKernelGGL((assemble_colour_kernel<NS, PO, NR, CACHE, LIN, TAB>), dim3((n + 255) / 256), dim3(256), 0,
                            c.stream, c.d_model, c.d_colour_cells + c.pat.colour_ptr[k], n,
                            c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_uold, c.d_uold1, sc,
                            c.d_ext[0], c.d_ext[1], c.d_ext[2], c.d_ext[3], c.d_val, c.d_F,
@@ -140,7 +140,7 @@ extern "C" void fedm_debug_phase(unsigned long long *out, int reset) {
 // JAC = false is the residual-only assembly (final Newton check): without the Jacobian code it
 // needs about half the registers and no accumulators, so it is compiled as a kernel of its own
 // that the compiler may run at a higher occupancy.
-template <int NS, bool PO, int NR, int CACHE, int THREADS, bool JAC, bool LIN>
+template <int NS, bool PO, int NR, int CACHE, int THREADS, bool JAC, bool LIN, bool TAB>
 __device__ __forceinline__ void assemble_patch_body(
     const fedm_model_desc *__restrict__ md, int nv, const int *__restrict__ boff,
     const int *__restrict__ cell_ptr, const PatchCell *__restrict__ pcells,
@@ -210,7 +210,7 @@ __device__ __forceinline__ void assemble_patch_body(
             ext[s] = (extp[s] && md->ext_nodes[s]) ? extp[s] + (size_t)pc.cell * md->ext_nodes[s] : nullptr;
 
         FEDM_T(3)
-        Element<NS, PO, NR, CACHE, LIN> el;
+        Element<NS, PO, NR, CACHE, LIN, TAB> el;
         el.setup(md, x, Uc, Hc, sc, mode);
         FEDM_T(4)
 #pragma unroll
@@ -260,15 +260,15 @@ __device__ __forceinline__ void assemble_patch_body(
     md, nv, boff, cell_ptr, pcells, halo_ptr, halo, coords, u, uold, uold1, sc, ext0, ext1, ext2,  \
         ext3, val, F, mode, acc_doubles, max_verts
 
-template <int NS, bool PO, int NR, int CACHE, int THREADS, bool LIN>
+template <int NS, bool PO, int NR, int CACHE, int THREADS, bool LIN, bool TAB>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void assemble_patch_kernel(
     FEDM_PATCH_PARAMS) {
-    assemble_patch_body<NS, PO, NR, CACHE, THREADS, true, LIN>(FEDM_PATCH_ARGS);
+    assemble_patch_body<NS, PO, NR, CACHE, THREADS, true, LIN, TAB>(FEDM_PATCH_ARGS);
 }
 
-template <int NS, bool PO, int NR, int CACHE, int THREADS, bool LIN>
+template <int NS, bool PO, int NR, int CACHE, int THREADS, bool LIN, bool TAB>
 __global__ __launch_bounds__(THREADS) void residual_patch_kernel(FEDM_PATCH_PARAMS) {
-    assemble_patch_body<NS, PO, NR, CACHE, THREADS, false, LIN>(FEDM_PATCH_ARGS);
+    assemble_patch_body<NS, PO, NR, CACHE, THREADS, false, LIN, TAB>(FEDM_PATCH_ARGS);
 }
 
 // workgroup barrier that orders LDS accesses only: global stores issued before it stay in flight
@@ -280,7 +280,7 @@ __device__ __forceinline__ void lds_only_barrier() {
 
 // Second generation of the row-phase kernel (element_lean.hpp, lean2_*): per-vertex exponentials,
 // cell constants kept in an LDS column between the rows; JAC = false is the residual-only assembly.
-template <int NS, int NR, int THREADS, bool JAC>
+template <int NS, int NR, int THREADS, bool JAC, bool TAB>
 __device__ __forceinline__ void assemble_lean2_body(FEDM_PATCH_PARAMS, int xcd, const int *__restrict__ patch_list,
                                                     uint32_t cmask) {
     constexpr int NEQ = NS + 1, NEQ2 = NEQ * NEQ;
@@ -332,7 +332,7 @@ __device__ __forceinline__ void assemble_lean2_body(FEDM_PATCH_PARAMS, int xcd, 
     __syncthreads();
     FEDM_T(1)   // barrier: the staged loads arrive
     LeanCell lc = {0, 0, 0, 0};
-    if (active) lc = lean2_prologue<NS, NR>(md, pc_own, vx, Ul, cst + threadIdx.x, THREADS);
+    if (active) lc = lean2_prologue<NS, NR, TAB>(md, pc_own, vx, Ul, cst + threadIdx.x, THREADS);
     FEDM_T(2)   // prologue: cell record, field, rate coefficient
     if constexpr (!JAC) {
         // residual only: no accumulators, no row phases -- the rows share the cell's geometry
@@ -342,7 +342,7 @@ __device__ __forceinline__ void assemble_lean2_body(FEDM_PATCH_PARAMS, int xcd, 
             lean2_geometry(md, lc, vx, lv, G, W, cst[LeanStash<NR>::IDET * THREADS + threadIdx.x]);
 #pragma unroll
             for (int row = 0; row < NEQ; ++row)
-                lean2_row_core<NS, NR, false>(md, row, lc, lv, G, W, Ul, Hl, Al, sc, acc, Fl, cst + threadIdx.x, THREADS);
+                lean2_row_core<NS, NR, false, -1, TAB>(md, row, lc, lv, G, W, Ul, Hl, Al, sc, acc, Fl, cst + threadIdx.x, THREADS);
         }
     }
 #pragma unroll 1
@@ -355,7 +355,7 @@ __device__ __forceinline__ void assemble_lean2_body(FEDM_PATCH_PARAMS, int xcd, 
 #define FEDM_ROW_CASE(R)                                                                                   \
     case R:                                                                                                \
         if constexpr (NEQ > R)                                                                             \
-            lean2_row<NS, NR, JAC, R>(md, row, lc, vx, Ul, Hl, Al, sc, acc, Fl, cst + threadIdx.x, THREADS, cmask); \
+            lean2_row<NS, NR, JAC, R, TAB>(md, row, lc, vx, Ul, Hl, Al, sc, acc, Fl, cst + threadIdx.x, THREADS, cmask); \
         break;
             switch (row) {
                 FEDM_ROW_CASE(0)
@@ -366,7 +366,7 @@ __device__ __forceinline__ void assemble_lean2_body(FEDM_PATCH_PARAMS, int xcd, 
             }
 #undef FEDM_ROW_CASE
 #else
-            lean2_row<NS, NR, JAC>(md, row, lc, vx, Ul, Hl, Al, sc, acc, Fl, cst + threadIdx.x, THREADS, cmask);
+            lean2_row<NS, NR, JAC, -1, TAB>(md, row, lc, vx, Ul, Hl, Al, sc, acc, Fl, cst + threadIdx.x, THREADS, cmask);
 #endif
         }
         FEDM_T(3)   // the row (wave 0's view)
@@ -423,16 +423,16 @@ __device__ __forceinline__ void assemble_lean2_body(FEDM_PATCH_PARAMS, int xcd, 
 #ifndef FEDM_LEAN2_WAVES
 #define FEDM_LEAN2_WAVES 3
 #endif
-template <int NS, int NR, int THREADS>
+template <int NS, int NR, int THREADS, bool TAB>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(FEDM_LEAN2_WAVES, FEDM_LEAN2_WAVES))) void assemble_lean2_kernel(
     FEDM_PATCH_PARAMS, int xcd, const int *__restrict__ patch_list, uint32_t cmask) {
-    assemble_lean2_body<NS, NR, THREADS, true>(FEDM_PATCH_ARGS, xcd, patch_list, cmask);
+    assemble_lean2_body<NS, NR, THREADS, true, TAB>(FEDM_PATCH_ARGS, xcd, patch_list, cmask);
 }
 
-template <int NS, int NR, int THREADS>
+template <int NS, int NR, int THREADS, bool TAB>
 __global__ __launch_bounds__(THREADS) void residual_lean2_kernel(FEDM_PATCH_PARAMS, int xcd,
                                                                  const int *__restrict__ patch_list, uint32_t cmask) {
-    assemble_lean2_body<NS, NR, THREADS, false>(FEDM_PATCH_ARGS, xcd, patch_list, cmask);
+    assemble_lean2_body<NS, NR, THREADS, false, TAB>(FEDM_PATCH_ARGS, xcd, patch_list, cmask);
 }
 #undef FEDM_PATCH_PARAMS
 #undef FEDM_PATCH_ARGS
@@ -495,7 +495,7 @@ static AssemblyPath assembly_path_upto(const Ctx &c, bool jacobian, int mode, in
 
 AssemblyPath assembly_path(const Ctx &c, bool jacobian, int mode) { return assembly_path_upto(c, jacobian, mode, 3); }
 
-template <int NS, bool PO, int NR, int CACHE, bool LIN>
+template <int NS, bool PO, int NR, int CACHE, bool LIN, bool TAB>
 static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
     constexpr int NEQ = NS + (PO ? 1 : 0);
     const StepCoef sc = step_coef(c.dt, c.dt_old);
@@ -507,7 +507,7 @@ static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
     // the whole mesh.
     const AssemblyPath fallback = path.variant == 3 ? assembly_path_upto(c, jacobian, mode, 2) : path;
 #define FEDM_PATCH_LAUNCH(KERNEL, T)                                                              \
-    hipLaunchKernelGGL((KERNEL<NS, PO, NR, CACHE, T, LIN>), dim3(c.pat.n_slices), dim3(T),         \
+    hipLaunchKernelGGL((KERNEL<NS, PO, NR, CACHE, T, LIN, TAB>), dim3(c.pat.n_slices), dim3(T),         \
                        patch_lds_bytes(c, jacobian), c.stream, c.d_model, c.nv, c.d_slice_boff,    \
                        c.d_patch_cell_ptr, c.d_patch_cells, c.d_patch_halo_ptr, c.d_patch_halo,    \
                        c.d_coords, c.d_u, c.d_uold, c.d_uold1, sc, c.d_ext[0], c.d_ext[1],         \
@@ -526,7 +526,7 @@ static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
                                                        (size_t)LeanStash<NR>::N * T);
 #define FEDM_LEAN2_LAUNCH_T(KERNEL, LIST, N, TT)                                                            \
     do {                                                                                                    \
-        hipLaunchKernelGGL((KERNEL<NS, NR, TT>), dim3(N), dim3(TT), lds_bytes, c.stream, c.d_model,         \
+        hipLaunchKernelGGL((KERNEL<NS, NR, TT, TAB>), dim3(N), dim3(TT), lds_bytes, c.stream, c.d_model,         \
                            c.nv, c.d_slice_boff, c.d_patch_cell_ptr, c.d_patch_cells, c.d_patch_halo_ptr,   \
                            c.d_patch_halo, c.d_coords, c.d_u, c.d_uold, c.d_uold1, sc, c.d_ext[0],          \
                            c.d_ext[1], c.d_ext[2], c.d_ext[3], c.d_val, c.d_F, mode, acc_row,               \
@@ -602,7 +602,7 @@ static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
 // =============================================================================================
 // SPECIES_COLS: the species columns only (the segregated step's species assembly: the planes of the potential column
 // are not touched)
-template <int NS, bool ATOMIC, bool SPECIES_COLS = false>
+template <int NS, bool ATOMIC, bool SPECIES_COLS = false, bool TAB = false>
 __global__ void boundary_kernel(const fedm_model_desc *__restrict__ md, int n_facets,
                                 const int *__restrict__ facets /* [n][3] = cell, local facet, tag */,
                                 const int *__restrict__ cells, const double *__restrict__ coords,
@@ -633,19 +633,29 @@ __global__ void boundary_kernel(const fedm_model_desc *__restrict__ md, int n_fa
         if (ATOMIC) unsafeAtomicAdd(p, value);
         else *p += value;
     };
-    boundary_facet<NS>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
+    boundary_facet<NS, TAB>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
 }
 
 template <bool ATOMIC>
 static void launch_boundary_range(Ctx &c, bool jacobian, int f0, int n) {
     const dim3 g((n + 127) / 128), b(128);
     const int *fl = c.d_bfacets + 3 * f0;
+#define FEDM_BK(NS_, TAB_)                                                                                          \
+    hipLaunchKernelGGL((boundary_kernel<NS_, ATOMIC, false, TAB_>), g, b, 0, c.stream, c.d_model, n, fl, c.d_cells,  \
+                       c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0)
+#define FEDM_BK_CASE(NS_)                                                                                           \
+    case NS_:                                                                                                       \
+        if (c.model_tables) FEDM_BK(NS_, true);                                                                     \
+        else FEDM_BK(NS_, false);                                                                                   \
+        break;
     switch (c.ns) {
-        case 1: hipLaunchKernelGGL((boundary_kernel<1, ATOMIC>), g, b, 0, c.stream, c.d_model, n, fl, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0); break;
-        case 2: hipLaunchKernelGGL((boundary_kernel<2, ATOMIC>), g, b, 0, c.stream, c.d_model, n, fl, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0); break;
-        case 3: hipLaunchKernelGGL((boundary_kernel<3, ATOMIC>), g, b, 0, c.stream, c.d_model, n, fl, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0); break;
-        case 4: hipLaunchKernelGGL((boundary_kernel<4, ATOMIC>), g, b, 0, c.stream, c.d_model, n, fl, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0); break;
+        FEDM_BK_CASE(1)
+        FEDM_BK_CASE(2)
+        FEDM_BK_CASE(3)
+        FEDM_BK_CASE(4)
     }
+#undef FEDM_BK_CASE
+#undef FEDM_BK
 }
 
 static void launch_boundary(Ctx &c, bool jacobian) {
@@ -663,10 +673,23 @@ static void launch_boundary(Ctx &c, bool jacobian) {
     }
 }
 
+template <int NS, bool PO, int NR, int CACHE, bool LIN, bool TAB>
+static void assemble_variant_tab(Ctx &c, bool jacobian, int mode) {
+    if (c.assembly_kind == 1) assemble_patch_t<NS, PO, NR, CACHE, LIN, TAB>(c, jacobian, mode);
+    else assemble_colour_t<NS, PO, NR, CACHE, LIN, TAB>(c, jacobian, mode);
+}
+
+// a model with tabulated coefficient factors (Ctx::model_tables; it has a Poisson row: there is no |E| without one)
+// takes the instantiations that look them up, every other model the ones without the look-up
 template <int NS, bool PO, int NR, int CACHE, bool LIN = false>
 static void assemble_variant(Ctx &c, bool jacobian, int mode) {
-    if (c.assembly_kind == 1) assemble_patch_t<NS, PO, NR, CACHE, LIN>(c, jacobian, mode);
-    else assemble_colour_t<NS, PO, NR, CACHE, LIN>(c, jacobian, mode);
+    if constexpr (PO) {
+        if (c.model_tables) {
+            assemble_variant_tab<NS, PO, NR, CACHE, LIN, true>(c, jacobian, mode);
+            return;
+        }
+    }
+    assemble_variant_tab<NS, PO, NR, CACHE, LIN, false>(c, jacobian, mode);
 }
 
 template <int NS, bool PO>
@@ -844,7 +867,7 @@ __global__ void identity_rows_kernel(int nv, int nvp, int neq, int ns_frozen,
 
 // boundary_kernel<NS, true> and dirichlet_kernel in one launch (128-thread blocks: the first ones take the facets, the
 // rest the Dirichlet and padding rows) -- allowed when no row belongs to both (Ctx::boundary_rows_disjoint)
-template <int NS>
+template <int NS, bool TAB>
 __global__ __launch_bounds__(128) void boundary_dirichlet_kernel(
     const fedm_model_desc *__restrict__ md, int n_facets, int facet_blocks, const int *__restrict__ facets,
     const int *__restrict__ cells, const double *__restrict__ coords, const uint32_t *__restrict__ cell_slots,
@@ -869,7 +892,7 @@ __global__ __launch_bounds__(128) void boundary_dirichlet_kernel(
             const uint32_t slot = cell_slots[(size_t)c * 9 + a * 3 + b];
             unsafeAtomicAdd(&val[((size_t)(slot >> 6) * NEQ2 + sr * NEQ + scol) * SLICE + (slot & 63)], value);
         };
-        boundary_facet<NS>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
+        boundary_facet<NS, TAB>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
         return;
     }
     // the rows of dirichlet_kernel (one GPU: Dirichlet dofs, then the padding vertices [id_first, id_first + n_id))
@@ -904,15 +927,21 @@ void launch_finalize(Ctx &c, bool jacobian, int mode) {
         if (mode == 0 && jac == jacobian) {
             const int fb = (c.n_bfacets + 127) / 128, n_id = c.nvp - c.nv;
             const int rb = (c.n_dir + n_id + 127) / 128;
-#define FEDM_BD(NS_)                                                                                              \
-    hipLaunchKernelGGL(boundary_dirichlet_kernel<NS_>, dim3(fb + rb), dim3(128), 0, c.stream, c.d_model, c.n_bfacets, fb, \
+#define FEDM_BD_T(NS_, TAB_)                                                                                      \
+    hipLaunchKernelGGL((boundary_dirichlet_kernel<NS_, TAB_>), dim3(fb + rb), dim3(128), 0, c.stream, c.d_model, c.n_bfacets, fb, \
                        c.d_bfacets, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0, c.n_dir, \
                        c.d_dir_dofs, c.d_dir_vals, c.d_slice_boff, c.d_diag_slot, c.nv, n_id)
+#define FEDM_BD(NS_)                                                                                              \
+    do {                                                                                                          \
+        if (c.model_tables) FEDM_BD_T(NS_, true);                                                                 \
+        else FEDM_BD_T(NS_, false);                                                                               \
+    } while (0)
             if (c.ns == 1) FEDM_BD(1);
             else if (c.ns == 2) FEDM_BD(2);
             else if (c.ns == 3) FEDM_BD(3);
             else FEDM_BD(4);
 #undef FEDM_BD
+#undef FEDM_BD_T
             return;
         }
         launch_boundary(c, jac);   // (not the pair this was deferred for: the facets first, then the rows as usual)

@@ -986,6 +986,11 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(FEDM_RE
 template <int NS, int NR>
 static bool lean3_build_plan(const fedm_model_desc &m, Lean3Plan<NS, NR> &pl) {
     if (m.n_species != NS || m.n_reactions > NR || !m.poisson) return false;
+    // a tabulated factor (fedm_termsum::pad_) has no slot in the plan: such models stay on the second generation
+    for (int j = 0; j < m.n_reactions; ++j)
+        if (m.k[j].pad_ != 0) return false;
+    for (int s = 0; s < NS; ++s)
+        if (m.mu[s].pad_ != 0 || m.D[s].pad_ != 0) return false;
     pl = Lean3Plan<NS, NR>{};
     pl.nreac = m.n_reactions;
     pl.axisymmetric = m.axisymmetric;

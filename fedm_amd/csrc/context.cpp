@@ -1,6 +1,7 @@
 // C ABI of libfedm_hip.so (include/fedm_hip.h): the context, its state and its settings.
 // Host logic only; every flop of the hot path runs in the .hip files.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -77,6 +78,108 @@ static int check_model(const fedm_model_desc &m) {
     return 0;
 }
 
+// the tables of fedm_ctx_create_tabulated as the caller passed them (checked by check_tables before anything is allocated)
+struct HostTables {
+    int n = 0;
+    const int32_t *ptr = nullptr;
+    const double *x = nullptr, *y = nullptr;
+    const char *who = "fedm_ctx_create";   // the entry point, for the messages
+};
+
+// Every table reference of the model against the tables: 0, or 1 with the message set.  The kernels trust both.
+static int check_tables(const fedm_model_desc &m, const HostTables &t) {
+    const std::string who = std::string(t.who) + ": ";
+    if (t.n < 0 || t.n > FEDM_MAX_TABLES) {
+        set_error(who + std::to_string(t.n) + " tables, at most " + std::to_string(FEDM_MAX_TABLES));
+        return 1;
+    }
+    if (t.n > 0 && !t.ptr) {
+        set_error(who + "null tab_ptr");
+        return 1;
+    }
+    if (t.ptr && t.ptr[0] != 0) {
+        set_error(who + "tab_ptr must start at 0");
+        return 1;
+    }
+    for (int k = 0; k < t.n; ++k)
+        if (t.ptr[k + 1] < t.ptr[k]) {
+            set_error(who + "tab_ptr must not decrease (table " + std::to_string(k) + ")");
+            return 1;
+        }
+    const int total = t.n > 0 ? t.ptr[t.n] : 0;
+    if (total > FEDM_MAX_TABLE_KNOTS) {
+        set_error(who + std::to_string(total) + " knots in all, at most " + std::to_string(FEDM_MAX_TABLE_KNOTS));
+        return 1;
+    }
+    if (total > 0 && (!t.x || !t.y)) {
+        set_error(who + "null table arrays");
+        return 1;
+    }
+    for (int k = 0; k < t.n; ++k) {
+        const int b = t.ptr[k], e = t.ptr[k + 1];
+        if (e == b) {
+            set_error(who + "table " + std::to_string(k) + " has no entries");
+            return 1;
+        }
+        for (int i = b; i < e; ++i) {
+            if (!std::isfinite(t.x[i]) || !std::isfinite(t.y[i])) {
+                set_error(who + "table " + std::to_string(k) + " has a knot or value that is not finite (entry " +
+                          std::to_string(i - b) + ")");
+                return 1;
+            }
+            if (i > b && !(t.x[i] > t.x[i - 1])) {
+                set_error(who + "the knots of table " + std::to_string(k) + " do not strictly increase (entry " +
+                          std::to_string(i - b) + ")");
+                return 1;
+            }
+        }
+    }
+    auto refs_ok = [&](const fedm_termsum &ts, const char *name, int idx) {
+        if (ts.pad_ == 0) return true;
+        const std::string coef = std::string(name) + "[" + std::to_string(idx) + "]";
+        if (!m.poisson) {
+            set_error(who + coef + " refers to a table, but the model has no Poisson equation (no |E|)");
+            return false;
+        }
+        const int r1 = ts.pad_ & 0xffff, r2 = (ts.pad_ >> 16) & 0xffff;
+        for (int r : {r1, r2})
+            if (r > t.n) {
+                set_error(who + coef + " refers to table " + std::to_string(r - 1) + ", " + std::to_string(t.n) +
+                          " tables were passed");
+                return false;
+            }
+        if (r1 == 0) {
+            set_error(who + coef + " has a second table factor without a first");
+            return false;
+        }
+        return true;
+    };
+    for (int s = 0; s < m.n_species; ++s)
+        if (!refs_ok(m.mu[s], "mu", s) || !refs_ok(m.D[s], "D", s)) return 1;
+    for (int j = 0; j < m.n_reactions; ++j)
+        if (!refs_ok(m.k[j], "k", j)) return 1;
+    return 0;
+}
+
+// {fedm_model_desc; ModelTables; x; y} in one device allocation (fedm_internal.hpp, ModelTables)
+static int upload_model(fedm_model_desc *&dst, const fedm_model_desc &m, const HostTables &t) {
+    const int total = t.n > 0 ? t.ptr[t.n] : 0;
+    std::vector<unsigned char> buf(sizeof(fedm_model_desc) + sizeof(ModelTables) + sizeof(double) * 2 * (size_t)total);
+    std::memcpy(buf.data(), &m, sizeof(m));
+    ModelTables mt{};
+    mt.n_tables = t.n;
+    mt.n_knots = total;
+    for (int k = 0; k <= t.n && t.n > 0; ++k) mt.ptr[k] = t.ptr[k];
+    std::memcpy(buf.data() + sizeof(m), &mt, sizeof(mt));
+    if (total) {
+        std::memcpy(buf.data() + sizeof(m) + sizeof(mt), t.x, sizeof(double) * total);
+        std::memcpy(buf.data() + sizeof(m) + sizeof(mt) + sizeof(double) * total, t.y, sizeof(double) * total);
+    }
+    FEDM_HIP_CHECK(hipMalloc((void **)&dst, buf.size()));
+    FEDM_HIP_CHECK(hipMemcpy(dst, buf.data(), buf.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
 int put_vec(Ctx &c, double *dst, const double *src) {
     if (!src) return 0;
     std::memcpy(c.h_stage, src, sizeof(double) * c.n);
@@ -102,15 +205,15 @@ const char *fedm_last_error(void) { return g_error.c_str(); }
 int fedm_abi_version(void) { return FEDM_ABI_VERSION; }
 
 static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *model,
-                           const fedm_gd_desc *gd, int device, fedm_ctx **out);
+                           const fedm_gd_desc *gd, const HostTables &tables, int device, fedm_ctx **out);
 
 // every error exit of the set-up releases what had been allocated so far (context, stream, device
 // and pinned memory): a caller that retries after an out-of-memory must not accumulate leaked HBM
 static int ctx_create_guarded(const fedm_mesh_desc *mesh, const fedm_model_desc *model,
-                              const fedm_gd_desc *gd, int device, fedm_ctx **out) {
+                              const fedm_gd_desc *gd, const HostTables &tables, int device, fedm_ctx **out) {
     *out = nullptr;
     fedm_ctx *h = nullptr;
-    const int rc = ctx_create_impl(mesh, model, gd, device, &h);
+    const int rc = ctx_create_impl(mesh, model, gd, tables, device, &h);
     if (rc != 0) {
         const std::string msg = g_error;  // destroy may overwrite it
         if (h) fedm_ctx_destroy(h);
@@ -121,8 +224,8 @@ static int ctx_create_guarded(const fedm_mesh_desc *mesh, const fedm_model_desc 
     return 0;
 }
 
-int fedm_ctx_create(const fedm_mesh_desc *mesh, const fedm_model_desc *model, int device,
-                    fedm_ctx **out) {
+static int ctx_create_lfa(const fedm_mesh_desc *mesh, const fedm_model_desc *model, const HostTables &tables,
+                          int device, fedm_ctx **out) {
     if (!mesh || !model || !out) {
         set_error("null argument");
         return -2;
@@ -138,7 +241,30 @@ int fedm_ctx_create(const fedm_mesh_desc *mesh, const fedm_model_desc *model, in
                   " quadrature points)");
         return -2;
     }
-    return ctx_create_guarded(mesh, model, nullptr, device, out);
+    if (check_tables(*model, tables)) return -2;
+    return ctx_create_guarded(mesh, model, nullptr, tables, device, out);
+}
+
+int fedm_ctx_create(const fedm_mesh_desc *mesh, const fedm_model_desc *model, int device,
+                    fedm_ctx **out) {
+    return ctx_create_lfa(mesh, model, HostTables{}, device, out);
+}
+
+int fedm_ctx_create_tabulated(const fedm_mesh_desc *mesh, const fedm_model_desc *model, int n_tables,
+                              const int32_t *tab_ptr, const double *tab_x, const double *tab_y, int device,
+                              fedm_ctx **out) {
+    HostTables t;
+    t.n = n_tables;
+    t.ptr = tab_ptr;
+    t.x = tab_x;
+    t.y = tab_y;
+    t.who = "fedm_ctx_create_tabulated";
+    if (n_tables > 0 && !tab_ptr) {
+        set_error("fedm_ctx_create_tabulated: null tab_ptr");
+        return -2;
+    }
+    if (n_tables == 0) t.ptr = nullptr;   // (no tables: fedm_ctx_create)
+    return ctx_create_lfa(mesh, model, t, device, out);
 }
 
 int fedm_ctx_create_gd(const fedm_mesh_desc *mesh, const fedm_gd_desc *gd, int device,
@@ -159,7 +285,7 @@ int fedm_ctx_create_gd(const fedm_mesh_desc *mesh, const fedm_gd_desc *gd, int d
                 set_error("LMEA reaction powers must be between 0 and 15");
                 return -2;
             }
-    return ctx_create_guarded(mesh, nullptr, gd, device, out);
+    return ctx_create_guarded(mesh, nullptr, gd, HostTables{}, device, out);
 }
 
 int fedm_gd_prep_setup(fedm_ctx *h, const fedm_csr *mass, int n_tables, const int32_t *tab_ptr,
@@ -253,7 +379,7 @@ int fedm_gd_set_fields(fedm_ctx *h, const double *fields) {
 }
 
 static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *model,
-                           const fedm_gd_desc *gd, int device, fedm_ctx **out) {
+                           const fedm_gd_desc *gd, const HostTables &tables, int device, fedm_ctx **out) {
     if (mesh->n_vertices < 3 || mesh->n_cells < 1) {
         set_error("empty mesh");
         return -2;
@@ -276,6 +402,9 @@ static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *mo
     const int n_tags_model = model ? model->n_tags : gd->n_tags;
     if (model) {
         c.model = *model;
+        for (int s_ = 0; s_ < model->n_species; ++s_)
+            c.model_tables = c.model_tables || model->mu[s_].pad_ != 0 || model->D[s_].pad_ != 0;
+        for (int j = 0; j < model->n_reactions; ++j) c.model_tables = c.model_tables || model->k[j].pad_ != 0;
         c.ns = model->n_species;
         c.poisson = model->poisson != 0;
     } else {  // LMEA: energy + (n_species - 1) particle equations + potential
@@ -401,7 +530,7 @@ static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *mo
     if (upload(c.d_cell_slots, c.pat.cell_slots.data(), c.pat.cell_slots.size())) return -1;
     if (upload(c.d_colour_cells, c.pat.colour_cells.data(), c.pat.colour_cells.size())) return -1;
     if (model) {
-        if (upload(c.d_model, model, 1)) return -1;
+        if (upload_model(c.d_model, *model, tables)) return -1;
     } else {
         if (upload(c.d_gd, gd, 1)) return -1;
         c.gd_n_fields = FEDM_GD_N_FIELDS(gd->n_species, gd->n_reactions);

@@ -11,6 +11,7 @@
 // residual and the n_eq x n_eq Jacobian blocks are closed-form combinations of them.
 #pragma once
 #include "fedm_internal.hpp"
+#include "table_lookup.h"
 
 namespace fedm {
 
@@ -19,10 +20,26 @@ __device__ __forceinline__ int sym6(int a, int b) {
     return a == b ? a : (a + b + 2);
 }
 
-// value and d/dE of  sum_i c_i E^p_i exp(q_i E^r_i).  E^r needs no transcendental for the
+// One tabulated factor T(E) of a coefficient and its derivative (table_lookup.h); ref = 1 + the table's index.  The
+// tables follow the descriptor in device memory (ModelTables): a few hundred bytes that stay cache-resident.
+__device__ __forceinline__ void table_factor(const fedm_model_desc *__restrict__ md, int ref, double E, double &val,
+                                             double &der) {
+    const ModelTables *mt = reinterpret_cast<const ModelTables *>(md + 1);
+    const int first = mt->ptr[ref - 1], n = mt->ptr[ref] - first;
+    const double *x = reinterpret_cast<const double *>(mt + 1) + first;
+    fedm_table_eval(x, x + mt->n_knots, n, E, &val, &der);
+}
+
+// value and d/dE of  g(E) [T1(E) [T2(E)]],  g = sum_i c_i E^p_i exp(q_i E^r_i).  E^r needs no transcendental for the
 // integer r the decks use (exp(-2.73e7/E_m): r = -1); divisions are multiplications by 1/E.
-__device__ __forceinline__ void termsum_eval(const fedm_termsum &ts, double E, double invE,
-                                             double lnE, double &val, double &der) {
+// TAB: the model has tabulated factors (fedm_termsum::pad_; Ctx::model_tables).  A compile-time switch chosen on the
+// host per model, like LIN: as a run-time branch the look-up's search loop at every coefficient cost the closed-form
+// models registers and several instantiations scratch for code they never run; with it their kernels are the ones
+// they had.  Within a TAB kernel the test on a coefficient's reference is wave-uniform, the factors multiply by the
+// product rule.
+template <bool TAB>
+__device__ __forceinline__ void termsum_eval(const fedm_model_desc *__restrict__ md, const fedm_termsum &ts, double E,
+                                             double invE, double lnE, double &val, double &der) {
     val = 0.0;
     der = 0.0;
     for (int i = 0; i < ts.n_terms; ++i) {
@@ -43,6 +60,19 @@ __device__ __forceinline__ void termsum_eval(const fedm_termsum &ts, double E, d
         const double t = c * exp(p * lnE + g);
         val += t;
         der += t * (p + r * g) * invE;
+    }
+    if constexpr (TAB) {
+        const int refs = ts.pad_;
+        if (refs == 0) return;
+#pragma unroll 1
+        for (int k = 0; k < 2; ++k) {
+            const int ref = (refs >> (16 * k)) & 0xffff;
+            if (ref == 0) continue;
+            double tv, td;
+            table_factor(md, ref, E, tv, td);
+            der = der * tv + val * td;
+            val *= tv;
+        }
     }
 }
 
@@ -100,7 +130,8 @@ struct CellGeom {
 // that the few resident waves cannot hide, and the constant weights fold into the arithmetic.
 // LIN: the unknowns are the densities themselves (fedm_model_desc::linear_representation); a
 // compile-time switch -- as a run-time flag it costs the logarithmic kernels up to 300 bytes of scratch.
-template <int NS, bool PO, int NR, int CACHE, bool LIN = false>
+// TAB: coefficients may carry tabulated factors (termsum_eval).
+template <int NS, bool PO, int NR, int CACHE, bool LIN = false, bool TAB = false>
 struct Element {
     static constexpr int NEQ = NS + (PO ? 1 : 0);
     static constexpr int IPHI = NEQ - 1;
@@ -184,7 +215,7 @@ struct Element {
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
             kv[j] = kd[j] = 0.0;
-            if (j < nreac) termsum_eval(md->k[j], Em, invEm_, lnE, kv[j], kd[j]);
+            if (j < nreac) termsum_eval<TAB>(md, md->k[j], Em, invEm_, lnE, kv[j], kd[j]);
         }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
@@ -199,7 +230,7 @@ struct Element {
             fdrift[s] = false;
             vel[s][0] = vel[s][1] = 0.0;
             if (flux[s]) {
-                termsum_eval(md->D[s], Em, invEm_, lnE, Dv[s], Dd[s]);
+                termsum_eval<TAB>(md, md->D[s], Em, invEm_, lnE, Dv[s], Dd[s]);
                 vel[s][0] = -Dv[s] * gradu[s][0];
                 vel[s][1] = -Dv[s] * gradu[s][1];
                 if (md->eq_type[s] == FEDM_EQ_DRIFT_DIFFUSION_REACTION) {
@@ -207,7 +238,7 @@ struct Element {
                         vel[s][0] += md->drift_w[s][0];
                         vel[s][1] += md->drift_w[s][1];
                     } else if (PO) {
-                        termsum_eval(md->mu[s], Em, invEm_, lnE, muv[s], mud[s]);
+                        termsum_eval<TAB>(md, md->mu[s], Em, invEm_, lnE, muv[s], mud[s]);
                         vel[s][0] += md->Z[s] * muv[s] * E[0];
                         vel[s][1] += md->Z[s] * muv[s] * E[1];
                         fdrift[s] = true;
@@ -438,7 +469,7 @@ struct Element {
 // Contributions are added with global fp64 atomics (a few thousand facets; adjacent facets
 // share a vertex).  R: [3][NEQ] residual, blocks via `add(a, b, s_row, s_col, value)`.
 // ---------------------------------------------------------------------------------------------
-template <int NS, class AddR, class AddJ>
+template <int NS, bool TAB, class AddR, class AddJ>
 __device__ void boundary_facet(const fedm_model_desc *__restrict__ md, const double x[3][2],
                                const double Uc[3][NS + 1], int fi, int tag, bool jacobian,
                                AddR addR, AddJ addJ) {
@@ -468,7 +499,7 @@ __device__ void boundary_facet(const fedm_model_desc *__restrict__ md, const dou
             md->bc_kind[tag - 1][s] != FEDM_BC_NEUMANN)
             continue;
         double muv, mud;
-        termsum_eval(md->mu[s], Em, 1.0 / Em, lnE, muv, mud);
+        termsum_eval<TAB>(md, md->mu[s], Em, 1.0 / Em, lnE, muv, mud);
         double EM1[3] = {0.0, 0.0, 0.0}, EM2[3][3] = {{0.0}};
         for (int t = 0; t < md->n_fqp; ++t) {
             double phi[3] = {0.0, 0.0, 0.0};

@@ -42,7 +42,7 @@ struct LeanStash {
     static constexpr int IDET = 4, KV = 5;
 };
 
-template <int NS, int NR>
+template <int NS, int NR, bool TAB = false>
 __device__ __forceinline__ LeanCell lean2_prologue(const fedm_model_desc *__restrict__ md, const PatchCell &pc,
                                                    const double *__restrict__ vx, const double *__restrict__ Ul,
                                                    double *__restrict__ cst, int stride) {
@@ -80,7 +80,7 @@ __device__ __forceinline__ LeanCell lean2_prologue(const fedm_model_desc *__rest
     cst[LeanStash<NR>::IDET * stride] = cg.inv_det;
     if constexpr (LeanStash<NR>::K) {
         double kv = 0.0, kd = 0.0;
-        if (md->n_reactions > 0) termsum_eval(md->k[0], Em, invEm, lnE, kv, kd);
+        if (md->n_reactions > 0) termsum_eval<TAB>(md, md->k[0], Em, invEm, lnE, kv, kd);
         cst[LeanStash<NR>::KV * stride] = kv;
         cst[(LeanStash<NR>::KV + 1) * stride] = kd;
     }
@@ -124,7 +124,8 @@ __device__ __forceinline__ void lean2_geometry(const fedm_model_desc *__restrict
 // ninths of its matrix bytes).  The tests are wave-uniform.
 // ROW >= 0: the equation row is known at compile time (the selects on the row index fold away, the
 // model scalars of the row become constant-offset loads); ROW = -1: run-time row.
-template <int NS, int NR, bool JAC, int ROW = -1>
+// TAB: coefficients may carry tabulated factors (element.hpp, termsum_eval).
+template <int NS, int NR, bool JAC, int ROW = -1, bool TAB = false>
 __device__ __forceinline__ void lean2_row_core(const fedm_model_desc *__restrict__ md, int row_rt, const LeanCell &lc,
                                                const int (&lv)[3], const double (&G)[3][2], const double (&W)[3],
                                                const double *__restrict__ Ul,
@@ -209,7 +210,7 @@ __device__ __forceinline__ void lean2_row_core(const fedm_model_desc *__restrict
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
             kv[j] = kd[j] = 0.0;
-            if (j < nreac) termsum_eval(md->k[j], Em, invEm, lnE, kv[j], kd[j]);
+            if (j < nreac) termsum_eval<TAB>(md, md->k[j], Em, invEm, lnE, kv[j], kd[j]);
         }
     }
     double Us[3], Hs[3];
@@ -229,7 +230,7 @@ __device__ __forceinline__ void lean2_row_core(const fedm_model_desc *__restrict
             gradu[0] += Us[a] * G[a][0];
             gradu[1] += Us[a] * G[a][1];
         }
-        termsum_eval(md->D[s], Em, invEm, lnE, Dv, Dd);
+        termsum_eval<TAB>(md, md->D[s], Em, invEm, lnE, Dv, Dd);
         vel[0] = -Dv * gradu[0];
         vel[1] = -Dv * gradu[1];
         if (eq == FEDM_EQ_DRIFT_DIFFUSION_REACTION) {
@@ -237,7 +238,7 @@ __device__ __forceinline__ void lean2_row_core(const fedm_model_desc *__restrict
                 vel[0] += md->drift_w[s][0];
                 vel[1] += md->drift_w[s][1];
             } else {
-                termsum_eval(md->mu[s], Em, invEm, lnE, muv, mud);
+                termsum_eval<TAB>(md, md->mu[s], Em, invEm, lnE, muv, mud);
                 vel[0] += Z * muv * E[0];
                 vel[1] += Z * muv * E[1];
                 fdrift = true;
@@ -346,7 +347,7 @@ __device__ __forceinline__ void lean2_row_core(const fedm_model_desc *__restrict
 }
 
 // one equation row with the geometry recomputed (F + J: nothing but the packed indices lives across rows)
-template <int NS, int NR, bool JAC, int ROW = -1>
+template <int NS, int NR, bool JAC, int ROW = -1, bool TAB = false>
 __device__ __forceinline__ void lean2_row(const fedm_model_desc *__restrict__ md, int row, const LeanCell &lc,
                                           const double *__restrict__ vx, const double *__restrict__ Ul,
                                           const double *__restrict__ Hl, const double *__restrict__ Al,
@@ -355,7 +356,7 @@ __device__ __forceinline__ void lean2_row(const fedm_model_desc *__restrict__ md
     int lv[3];
     double G[3][2], W[3];
     lean2_geometry(md, lc, vx, lv, G, W, cst[LeanStash<NR>::IDET * stride]);
-    lean2_row_core<NS, NR, JAC, ROW>(md, row, lc, lv, G, W, Ul, Hl, Al, sc, acc, Fl, cst, stride, cmask);
+    lean2_row_core<NS, NR, JAC, ROW, TAB>(md, row, lc, lv, G, W, Ul, Hl, Al, sc, acc, Fl, cst, stride, cmask);
 }
 
 }  // namespace fedm

@@ -55,6 +55,17 @@ struct Pattern {
 // LDS bank clashes; not for models whose tables are indexed by (cell, local node) -- Expression sources
 void build_pattern(const fedm_mesh_desc &mesh, Pattern &pat, bool allow_rotation = true);
 
+// The tabulated coefficient factors of an LFA model (fedm_ctx_create_tabulated).  The device copy of the model is one
+// allocation {fedm_model_desc; ModelTables; double x[n_knots]; double y[n_knots]}: whoever holds the descriptor's
+// device pointer reaches the tables (element.hpp, termsum_eval) and no kernel signature changes.  A model without
+// tables carries the header alone (n_tables = 0); nothing reads it then.
+struct ModelTables {
+    int32_t n_tables, n_knots;
+    int32_t ptr[FEDM_MAX_TABLES + 1];   // knots of table t: [ptr[t], ptr[t + 1])
+    int32_t pad_;
+};
+static_assert(sizeof(fedm_model_desc) % 8 == 0 && sizeof(ModelTables) % 8 == 0, "the knots follow as doubles");
+
 struct Amg;
 struct Comm;
 struct GdPrep;
@@ -98,6 +109,7 @@ struct Ctx {
     bool poisson = false;
     int64_t n = 0, np = 0;  // nv*neq, nvp*neq
     fedm_model_desc model{};
+    bool model_tables = false;   // some coefficient has a tabulated factor (fedm_ctx_create_tabulated): the TAB kernels
     int assembly_lean = 3;   // patch assembly generation where it applies: 0 unrolled element, 2 one equation
                              // row at a time (element_lean.hpp), 3 one pass over the cells (assemble3.hip)
     bool xcd_remap = true;   // patch / slice -> workgroup mapping contiguous per XCD

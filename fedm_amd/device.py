@@ -51,7 +51,26 @@ class Model:
     def n_eq(self):
         return self.n_species + (1 if self.poisson else 0)
 
-    def to_c(self):
+    def to_c_tabulated(self):
+        """The descriptor and the model's distinct coefficient tables as fedm_ctx_create_tabulated takes them:
+        (md, tab_ptr int32[n_tables + 1], tab_x, tab_y).  Equal tables go in once."""
+        tables = []
+        md = self.to_c(tables)
+        ptr = np.zeros(len(tables) + 1, dtype=np.int32)
+        ptr[1:] = np.cumsum([t.x.size for t in tables])
+        if ptr[-1] > _lib.MAX_TABLE_KNOTS:
+            raise ValueError(f"the model's coefficient tables have {ptr[-1]} knots in all, at most "
+                             f"{_lib.MAX_TABLE_KNOTS}")
+        cat = lambda arrs: np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros(0), dtype=np.float64)
+        return md, ptr, cat([t.x for t in tables]), cat([t.y for t in tables])
+
+    def to_c(self, tables=None):
+        """The descriptor ALONE.  For a model with tabulated coefficients it holds their table references
+        (``fedm_termsum.pad_``) but not the tables they index: ``tables`` is the list that collects those, and
+        ``to_c_tabulated()`` -- which DeviceProblem calls -- returns both.  Called without a list the references are
+        still written (the descriptor's bytes identify the model, which is what callers of this form compare);
+        ``fedm_ctx_create`` refuses such a descriptor, so it cannot reach the device without its tables."""
+        tables = [] if tables is None else tables
         md = _lib.ModelDesc()
         ns = self.n_species
         md.linear_representation = 0 if self.log_representation else 1
@@ -64,8 +83,8 @@ class Model:
         for s in range(ns):
             md.eq_type[s] = _lib.EQ_TYPES[self.eq_type[s]]
             md.Z[s] = float(self.Z[s])
-            TermSum.coerce(mu[s]).fill(md.mu[s])
-            TermSum.coerce(D[s]).fill(md.D[s])
+            TermSum.coerce(mu[s]).fill(md.mu[s], tables)
+            TermSum.coerce(D[s]).fill(md.D[s], tables)
             if w[s] is not None:
                 md.has_drift_w[s] = 1
                 md.drift_w[s][0], md.drift_w[s][1] = float(w[s][0]), float(w[s][1])
@@ -73,7 +92,7 @@ class Model:
             raise ValueError(f"at most {_lib.MAX_REACTIONS} reactions")
         md.n_reactions = len(self.reactions)
         for j, rc in enumerate(self.reactions):
-            TermSum.coerce(rc.k).fill(md.k[j])
+            TermSum.coerce(rc.k).fill(md.k[j], tables)
             for s in range(ns):
                 md.power[j][s] = int(rc.power[s])
                 md.net[j][s] = int(rc.net[s])
@@ -414,7 +433,13 @@ class DeviceProblem:
             self._cells_dev = np.ascontiguousarray(self._cells_dev[by_vertex])
             if self._tags is not None:
                 self._tags = np.ascontiguousarray(self._tags.reshape(self.nc, 3)[by_vertex])
-        md = model.to_c()
+        tab = None
+        if isinstance(model, GdModel):
+            md = model.to_c()
+        else:
+            md, *tab = model.to_c_tabulated()
+            if tab[0].size == 1:
+                tab = None
         mesh = _lib.MeshDesc()
         mesh.n_vertices, mesh.n_cells = self.nv, self.nc
         mesh.coords = _dp(self._coords_dev)
@@ -436,8 +461,14 @@ class DeviceProblem:
             mesh.identity_vertices = self._identity.ctypes.data_as(C.POINTER(C.c_int32))
             mesh.halo_depth = self.halo_depth
         handle = C.c_void_p()
-        create = self.lib.fedm_ctx_create_gd if isinstance(model, GdModel) else self.lib.fedm_ctx_create
-        rc = create(C.byref(mesh), C.byref(md), int(device), C.byref(handle))
+        if tab is not None:     # tabulated E/N coefficients: looked up in the element routines
+            tab_ptr, tab_x, tab_y = tab
+            rc = self.lib.fedm_ctx_create_tabulated(C.byref(mesh), C.byref(md), tab_ptr.size - 1,
+                                                    tab_ptr.ctypes.data_as(C.POINTER(C.c_int32)), _dp(tab_x),
+                                                    _dp(tab_y), int(device), C.byref(handle))
+        else:
+            create = self.lib.fedm_ctx_create_gd if isinstance(model, GdModel) else self.lib.fedm_ctx_create
+            rc = create(C.byref(mesh), C.byref(md), int(device), C.byref(handle))
         if rc != 0:
             raise RuntimeError(f"fedm_ctx_create failed ({rc}): {_lib.last_error()}")
         self._h = handle

@@ -309,7 +309,7 @@ def compile_forms(F, quadrature_degree=None):
             if any(i >= ns for i in term.powers):
                 raise ValueError("source terms may only contain exp(u) of the species")
             for rc in reactions:                       # same rate on several species rows
-                if rc.k.terms == term.coef.terms and list(rc.power) == power and rc.net[s] == 0:
+                if rc.k.same_as(term.coef) and list(rc.power) == power and rc.net[s] == 0:
                     rc.net[s] = 1
                     break
             else:
@@ -781,6 +781,24 @@ def Rate_coefficient_interpolation(status, dependences, k_coeffs, kxs, kys, ener
         rule = rules[tag]
         if rule is not None:
             field.vector()[:] = rule(kx, ky)
+
+
+def Coefficient_table(E_m, kx, ky, N0):
+    """Extension (no counterpart in fedm/functions.py): an E/N table of an LFA model as a coefficient of the
+    form, the implicit counterpart of ``np.interp(redfield, kx, ky)``.  ``kx`` in Td and ``ky`` as
+    ``read_transport_coefficients`` / ``read_rate_coefficients`` return them for a ``Dependence: E/N`` file;
+    ``E_m`` is what ``sqrt(inner(-grad(u[n]), -grad(u[n])))`` returns.  The result goes where an ``eval``'d
+    ``fun:E`` string goes -- ``Flux(...)``, the source terms --
+    e.g. ``mu[1] = Coefficient_table(E_m, mu_x[1], mu_y[1], N0) / N0``.
+
+    The reference looks such tables up per node at the projected field of the PREVIOUS step
+    (Transport_coefficient_interpolation, fedm/functions.py:629-630); here the element kernels look them up at
+    the cell's own |E| of the CURRENT iterate with the exact derivative: implicit in the potential, cell-wise.
+    The knots become V/m, x_E = kx * N0 * 1e-21 (fedm-gd.py:309: redfield = 1e21 |E| / N0)."""
+    from .termsum import TermSum
+    if not (isinstance(E_m, TermSum) and not E_m.tables and E_m.terms == TermSum.field().terms):
+        raise TypeError("fedm.Coefficient_table: E_m must be the field magnitude sqrt(inner(-grad(u[n]), -grad(u[n])))")
+    return TermSum.table(np.asarray(kx, dtype=np.float64) * float(N0) * 1e-21, ky)
 
 
 def semi_implicit_coefficients(dependences, mean_energy_new, mean_energy_old, coefficients,

@@ -35,6 +35,8 @@ extern "C" {
 #define FEDM_MAX_QP 32
 #define FEDM_MAX_FQP 8
 #define FEDM_MAX_EXT_NODES 10
+#define FEDM_MAX_TABLES 16        /* tabulated coefficient factors of one model (fedm_ctx_create_tabulated)  */
+#define FEDM_MAX_TABLE_KNOTS 4096 /* knots of all tables together: 64 KiB of x and y, cache-resident         */
 
 #define FEDM_EQ_REACTION 0                 /* 'reaction'                 functions.py:333 */
 #define FEDM_EQ_DIFFUSION_REACTION 1       /* 'diffusion-reaction'                       */
@@ -48,7 +50,10 @@ extern "C" {
 #define FEDM_DIVERGED_LINEAR 3
 
 /* f(E) = sum_i c[i] * E^p[i] * exp(q[i] * E^r[i]); normal form of the deck's
- * 'fun:E' strings (file_input/benchmark_model/transport_coefficients/e_Nb.dat:12) */
+ * 'fun:E' strings (file_input/benchmark_model/transport_coefficients/e_Nb.dat:12).
+ * pad_ is the table reference: f(E) = (the sum) * T1(E) [* T2(E)] with piecewise-linear tables handed to
+ * fedm_ctx_create_tabulated (the decks' 'Dependence: E/N' files).  Low 16 bits: 1 + index of the first factor,
+ * high 16 bits: 1 + index of the second, 0: none -- what every descriptor written before tables existed holds. */
 typedef struct {
     int32_t n_terms;
     int32_t pad_;
@@ -221,7 +226,8 @@ const char *fedm_last_error(void);
  *    fedm_segregated_stats, fedm_debug_species_linear_solve, fedm_debug_species_assembly, fedm_debug_block_product, fedm_time_kernel kinds 6, 7.
  * 10: fedm_debug_gd_reduced_field, fedm_debug_get_ext_source; fedm_gd_prep_setup refuses what np.interp refuses (a
  *    looked-up table without entries, a tab_ptr that does not start at 0 or decreases, null table arrays, a program
- *    kind or argument outside its enum). */
+ *    kind or argument outside its enum).  Additive under 10 (no struct changes size or offsets, no signature changes):
+ *    fedm_ctx_create_tabulated; fedm_termsum.pad_, which had to be 0, is the table reference. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -229,6 +235,22 @@ int fedm_abi_version(void);
  * Replaces FunctionSpace/derivative/Problem set-up, fedm-streamer.py:133-291. */
 int fedm_ctx_create(const fedm_mesh_desc *mesh, const fedm_model_desc *model, int device,
                     fedm_ctx **out);
+/* fedm_ctx_create for a model whose coefficients carry table references (fedm_termsum.pad_): n_tables
+ * piecewise-linear tables laid out as fedm_gd_prep_setup's -- concatenated knots tab_x [V/m] and values tab_y with
+ * tab_ptr[n_tables + 1], starting at 0 and not decreasing.  The element routines look a factor up at the cell's own
+ * |E| (P1: constant per cell): np.interp's value -- tab_y's first / last entry outside the knots -- and the exact
+ * derivative, the segment's slope inside [first knot, last knot) and 0 outside, so the Jacobian stays the exact
+ * Gateaux derivative.  (The reference looks E/N tables up per NODE at the projected field of the previous step,
+ * fedm/functions.py:629-630; that lagged form is what the LMEA family does here, fedm_gd_prep_setup.)
+ * Refused (-2, nothing allocated, fedm_last_error names the table): more than FEDM_MAX_TABLES tables or
+ * FEDM_MAX_TABLE_KNOTS knots in all, a reference beyond n_tables, a table without entries, knots that do not strictly
+ * increase, a knot or value that is not finite, a tab_ptr that does not start at 0 or decreases, null arrays with
+ * entries, a reference in a model without the Poisson equation (there is no |E|).  fedm_ctx_create is this call with
+ * no tables: it refuses any reference.  Models with a reference run the second-generation assembly (variants 1, 2 of
+ * fedm_pattern_info; 0 by global colouring), never the one-pass kernels. */
+int fedm_ctx_create_tabulated(const fedm_mesh_desc *mesh, const fedm_model_desc *model, int n_tables,
+                              const int32_t *tab_ptr, const double *tab_x, const double *tab_y, int device,
+                              fedm_ctx **out);
 int fedm_ctx_create_gd(const fedm_mesh_desc *mesh, const fedm_gd_desc *model, int device,
                        fedm_ctx **out);
 int fedm_gd_set_fields(fedm_ctx *ctx, const double *fields /* [n_fields][n_vertices] */);
