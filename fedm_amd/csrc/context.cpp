@@ -598,7 +598,7 @@ static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *mo
     for (auto v : vecs)
         if (alloc_zero(*v, (size_t)c.np, c.stream)) return -1;
     if (alloc_zero(c.d_partials, (size_t)RED_BLOCKS * RED_K, c.stream)) return -1;
-    if (alloc_zero(c.d_red, RED_K, c.stream)) return -1;
+    if (alloc_zero(c.d_red, 2 * RED_K, c.stream)) return -1;
     FEDM_HIP_CHECK(hipHostMalloc((void **)&c.h_mail, sizeof(double) * MAIL_SLOTS * (RED_K + 1), hipHostMallocDefault));
     std::memset(c.h_mail, 0, sizeof(double) * MAIL_SLOTS * (RED_K + 1));
     c.h_red = c.h_mail;
@@ -720,6 +720,7 @@ int fedm_state_snapshot(fedm_ctx *h) {
     // ... and what the solver has learnt from the steps before (how many Krylov steps to queue ahead, at which Newton
     // iteration the final check is expected): steps repeated from the checkpoint then run as they did the first time
     c.snap_krylov_steps_hint = c.krylov_steps_hint;
+    std::copy(std::begin(c.krylov_hints), std::end(c.krylov_hints), std::begin(c.snap_krylov_hints));
     c.snap_newton_its_hint = c.newton_its_hint;
     return 0;
 }
@@ -732,6 +733,7 @@ int fedm_state_restore(fedm_ctx *h) {
     }
     c.err_cache_comp = -1;
     c.krylov_steps_hint = c.snap_krylov_steps_hint;
+    std::copy(std::begin(c.snap_krylov_hints), std::end(c.snap_krylov_hints), std::begin(c.krylov_hints));
     c.newton_its_hint = c.snap_newton_its_hint;
     FEDM_HIP_CHECK(hipSetDevice(c.device));
     c.halo_pending = false;   // the snapshot was taken with exchanged ghosts

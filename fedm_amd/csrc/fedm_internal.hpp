@@ -236,7 +236,17 @@ struct Ctx {
     long fs_solves[2] = {0, 0};         // Newton solves run under the [main, alternative] set (fedm_fieldsplit_policy)
     double *d_V = nullptr;  // (restart+1) Krylov vectors
     int krylov_cap = 0;
-    int krylov_steps_hint = 0;   // Krylov steps of the previous solve: how far ahead steps are queued
+    int krylov_steps_hint = 0;   // Krylov steps of the previous solve: how far ahead steps are queued (a slot without history)
+    // What the solves of one kind have taught: the k-th linear solve of a Newton loop resembles the k-th of the loop
+    // before it far more than the solve in front of it (early in a streamer run the counts alternate 2, 3, 2, 3).
+    // Slots 0 .. KRYLOV_HINT_SLOTS - 1: by Newton iteration (the last one shared by all later iterations); slot
+    // KRYLOV_HINT_SLOTS: solves outside a Newton loop (fedm_debug_linear_solve).
+    struct KrylovHint {
+        int its = -1;               // Krylov steps of the last solve in this slot (-1: none yet, krylov_steps_hint decides)
+        uint32_t refine_mask = 0;   // bit j: step j of that solve needed a second Gram-Schmidt pass (gmres: refined steps)
+    };
+    static constexpr int KRYLOV_HINT_SLOTS = 8;
+    KrylovHint krylov_hints[KRYLOV_HINT_SLOTS + 1], snap_krylov_hints[KRYLOV_HINT_SLOTS + 1];
     // Flexible GMRES with the field split on the right: z_j = Minv v_j is kept, so the update is
     // Z y and no preconditioner application is spent on the right-hand side.
     double *d_Z = nullptr;
@@ -250,7 +260,7 @@ struct Ctx {
     // reductions
     double *d_partials = nullptr;  // [RED_BLOCKS][RED_K]
     double *d_partials_wide = nullptr;  // [8][workgroups of the Jacobian product]: spmv_dots_kernel
-    double *d_red = nullptr;       // [RED_K]
+    double *d_red = nullptr;       // [2][RED_K]: the reductions' results; row 1: the coefficients of a refined step's second update
     double *h_mail = nullptr;      // pinned, host-mapped: MAIL_SLOTS slots of [RED_K] values + sequence tag
     double *h_red = nullptr;       // the slot of the publication last waited for (wait_red); written
                                    // by the last kernel of a reduction and polled by the host
@@ -265,6 +275,7 @@ struct Ctx {
     // the same two kinds without the update of their last step (the step expected to end the solve: its
     // normalised vector is only needed if the solve goes on, and is then formed by a launch of its own)
     std::vector<hipGraphExec_t> iter_graph_last, iter_graph_pair_last;
+    std::vector<hipGraphExec_t> iter_graph_refined;   // one GPU, on the right: step j followed by its second Gram-Schmidt pass
     bool iter_graphs_ok = true;   // false after a failed capture: plain launches from then on
     bool capturing = false;
     int newton_its_hint = -1;     // Newton iterations of the previous converged solve
@@ -316,6 +327,7 @@ enum PathStat {
     PS_NEWTON_MAX_IT,       // Newton solves that stopped at max_it
     PS_VERIFIED,            // true residuals formed at the start of a cycle (restarts, and before a success is reported)
     PS_VERIFY_FAILED,       // ... that contradicted the recurrence's 'converged': another cycle ran (or the solve gave up)
+    PS_SECOND_PASSES_DEVICE,// second Gram-Schmidt passes that ran in the queue, behind their step (counted by PS_SECOND_PASSES too)
     PS_COUNT
 };
 
@@ -347,6 +359,7 @@ inline void grant_dynamic_lds(void (*kernel)(Args...), int device, size_t bytes)
 constexpr int RED_BLOCKS = 512;
 constexpr int RED_K = 40;
 constexpr int RED_SPARE = RED_K - 3;
+constexpr int RED_REFINE = RED_K - 4;   // a refined Krylov step's flag: 0 first pass sound, 1 refined, 2 refined and still unsound
 constexpr int MAIL_SLOTS = 4;         // publications the host may have unread (GMRES keeps up to three steps in flight)  // a norm that rides along with the next Krylov publication
 // per-block partial sums, one contiguous row per slot: the single workgroup that finishes a
 // reduction reads a slot's RED_BLOCKS partials as 4 KB of consecutive doubles (with [block][slot]
@@ -405,14 +418,20 @@ void launch_spmv(Ctx &c, const double *x, double *y, bool scale_dinv, const int 
 void launch_spmv_fieldsplit(Ctx &c, const double *x, double *t, double *z, double *b0, double scale,
                             const int *slice_list = nullptr, int n_list = 0, bool compact32 = false);
 void launch_apply_dinv(Ctx &c, const double *x, double *y, double alpha);
-// (finish = false, several GPUs: the local sums into d_red[0..k) only)   false: not applicable, nothing launched
-bool launch_spmv_dots(Ctx &c, const double *x, double *y, const double *const *xs, int k, bool finish = true);
+// finish: the local sums into d_red[0..k) only (several GPUs), the finish formulae and the publication, or -- a refined
+// step -- the formulae and d_red[RED_REFINE] without a publication.   false: not applicable, nothing launched
+bool spmv_dots_applicable(const Ctx &c, int k);
+enum { SPMV_DOTS_SUMS = 0, SPMV_DOTS_PUBLISH = 1, SPMV_DOTS_REFINED = 2 };
+bool launch_spmv_dots(Ctx &c, const double *x, double *y, const double *const *xs, int k, int finish = SPMV_DOTS_PUBLISH);
 int ensure_spmv_dots(Ctx &c);
 // ---- kernels.hip ----------------------------------------------------------------------------
 void launch_dots(Ctx &c, const double *const *xs, const double *y, int k, bool finish = false);
 // (see cgs_update_fs_kernel; false: not instantiated for this case)
 bool launch_cgs_update_fs(Ctx &c, int k, const double *const *xs, double *y, float *g32, double *b0);
 bool launch_scale_copy_fs(Ctx &c, double a, const double *x, double *y, float *g32, double *b0);
+// the second Gram-Schmidt pass behind step j, in the queue (see dots_refine_kernel); publishes once
+bool cgs_refine_applicable(const Ctx &c, int j);
+bool launch_cgs_refine(Ctx &c, int j, const double *const *vs, double *t, float *g32, double *b0);
 void launch_dots_fused(Ctx &c, const double *const *xs, double *y, int k, const double *x0,
                        bool finish = true);
 void launch_cgs_finish(Ctx &c, int k);  // finish formulae + publication on d_red[0..k)

@@ -37,10 +37,9 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[K], double *par
 // partials[block][kbase + i] = sum over the block's grid-stride range of xs[i] * y
 // W (row-equilibrated GMRES, fedm_set_krylov_scaling): the sums run in the inner product <x, y> = sum_i wgt_i x_i y_i,
 // wgt = d^2 of row_scale_kernel.  A template flag: the unweighted instantiation is the code it was.
-template <int K, bool W = false>
-__global__ __launch_bounds__(256) void dots_kernel(PtrPack8 xs, const double *__restrict__ y,
-                                                   size_t n, double *__restrict__ partials, int kbase,
-                                                   const double *__restrict__ wgt = nullptr) {
+template <int K, bool W>
+__device__ __forceinline__ void dots_block(const PtrPack8 &xs, const double *__restrict__ y, size_t n,
+                                           double *__restrict__ partials, int kbase, const double *__restrict__ wgt) {
     double acc[K];
 #pragma unroll
     for (int i = 0; i < K; ++i) acc[i] = 0.0;
@@ -51,6 +50,82 @@ __global__ __launch_bounds__(256) void dots_kernel(PtrPack8 xs, const double *__
         for (int i = 0; i < K; ++i) acc[i] += xs.p[i][idx] * yv;
     }
     block_reduce_store<K>(acc, partials, kbase);
+}
+
+template <int K, bool W = false>
+__global__ __launch_bounds__(256) void dots_kernel(PtrPack8 xs, const double *__restrict__ y,
+                                                   size_t n, double *__restrict__ partials, int kbase,
+                                                   const double *__restrict__ wgt = nullptr) {
+    dots_block<K, W>(xs, y, n, partials, kbase, wgt);
+}
+
+// ---- the second Gram-Schmidt pass of a refined Krylov step (krylov.cpp), queued behind the step's first pass --------
+// Three kernels that read red[RED_REFINE], written by the step's first finish (spmv_dots_finish_kernel, finish = 2):
+// 0, the first pass was sound -- the reduction and the update return at once and touch nothing, the finish publishes
+// what the first finish left; 1, strong cancellation -- t = w - V h was left unscaled:
+//   dots_refine_kernel    c_i = v_i . t (i < k - 1) and tt = t . t, per-block partials like dots_kernel;
+//   refine_finish_kernel  hn2' = tt - sum c_i^2 (the c_i are rounding-sized beside |t|: no cancellation), scale' =
+//                         1 / sqrt(hn2'); red[i] = h_i + c_i, red[k-1] = hn2', red[RED_REFINE] = 1 (refined) or 2 (hn2'
+//                         fails the test against tt in its turn: scale' = 1, the host refines as it always did);
+//                         coef[i] = c_i and coef[RED_K-1] = scale' for the update; the step's ONE publication;
+//   cgs_refine_fs_kernel  cgs_update_fs_kernel on t with those coefficients.
+template <int K, bool W = false>
+__global__ __launch_bounds__(256) void dots_refine_kernel(PtrPack8 xs, const double *__restrict__ y, size_t n,
+                                                          double *__restrict__ partials,
+                                                          const double *__restrict__ red,
+                                                          const double *__restrict__ wgt = nullptr) {
+    if (red[RED_REFINE] == 0.0) return;
+    dots_block<K, W>(xs, y, n, partials, 0, wgt);
+}
+
+__global__ __launch_bounds__(1024) void refine_finish_kernel(const double *__restrict__ partials, int nblocks, int k,
+                                                            double *__restrict__ red, double *__restrict__ coef,
+                                                            double *mail, unsigned long long *seq) {
+    __shared__ double fin[RED_K];
+    __shared__ double cs[RED_K];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (threadIdx.x < RED_K) fin[threadIdx.x] = red[threadIdx.x];
+    __syncthreads();
+    if (fin[RED_REFINE] != 0.0) {   // (the same for every thread)
+        for (int i = wave; i < k; i += 16) {
+            double sum = 0.0;
+            for (int b = lane; b < nblocks; b += 64) sum += partials[PARTIAL_AT(b, i)];
+            sum = wave_sum(sum);
+            if (lane == 0) cs[i] = sum;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double tt = cs[k - 1];
+            double cc = 0.0;
+            for (int i = 0; i < k - 1; ++i) cc += cs[i] * cs[i];
+            const double hn2 = tt - cc;
+            const bool sound = hn2 > 1e-8 * tt && hn2 > 0.0;
+            const double scale = sound ? 1.0 / sqrt(hn2) : 1.0;
+            for (int i = 0; i < k - 1; ++i) {
+                fin[i] += cs[i];
+                coef[i] = cs[i];
+            }
+            fin[k - 1] = hn2;
+            fin[RED_K - 1] = scale;
+            coef[RED_K - 1] = scale;
+            fin[RED_REFINE] = sound ? 1.0 : 2.0;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 64) {
+        const unsigned long long tag = *seq + 1;
+        double *slot = mail + (tag & (MAIL_SLOTS - 1)) * (RED_K + 1);
+        for (int i = threadIdx.x; i < RED_K; i += 64) {
+            red[i] = fin[i];
+            slot[i] = fin[i];
+        }
+        __threadfence_system();
+        if (threadIdx.x == 0) {
+            *seq = tag;
+            __hip_atomic_store(reinterpret_cast<unsigned long long *>(slot + RED_K), tag, __ATOMIC_RELEASE,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
 }
 
 __global__ void reduce_partials_kernel(const double *__restrict__ partials, int nblocks, int k,
@@ -344,10 +419,9 @@ __device__ __forceinline__ void first_stage_of(int v, const double (&tv)[NS + 1]
 }
 
 template <int K, int NS>
-__global__ __launch_bounds__(256) void cgs_update_fs_kernel(int nvp, const double *__restrict__ coef, PtrPack8 xs,
-                                                            double *__restrict__ y,
-                                                            const double *__restrict__ dinv_uu,
-                                                            float *__restrict__ g32, double *__restrict__ b0) {
+__device__ __forceinline__ void cgs_update_fs_block(int nvp, const double *__restrict__ coef, const PtrPack8 &xs,
+                                                    double *__restrict__ y, const double *__restrict__ dinv_uu,
+                                                    float *__restrict__ g32, double *__restrict__ b0) {
     constexpr int NEQ = NS + 1;
     double cf[K];
 #pragma unroll
@@ -367,6 +441,25 @@ __global__ __launch_bounds__(256) void cgs_update_fs_kernel(int nvp, const doubl
         }
         first_stage_of<NS>(v, tv, dinv_uu, g32, b0);
     }
+}
+
+template <int K, int NS>
+__global__ __launch_bounds__(256) void cgs_update_fs_kernel(int nvp, const double *__restrict__ coef, PtrPack8 xs,
+                                                            double *__restrict__ y,
+                                                            const double *__restrict__ dinv_uu,
+                                                            float *__restrict__ g32, double *__restrict__ b0) {
+    cgs_update_fs_block<K, NS>(nvp, coef, xs, y, dinv_uu, g32, b0);
+}
+
+// the update of a refined step's second pass (dots_refine_kernel): nothing when the first pass was sound
+template <int K, int NS>
+__global__ __launch_bounds__(256) void cgs_refine_fs_kernel(int nvp, const double *__restrict__ red,
+                                                            const double *__restrict__ coef, PtrPack8 xs,
+                                                            double *__restrict__ y,
+                                                            const double *__restrict__ dinv_uu,
+                                                            float *__restrict__ g32, double *__restrict__ b0) {
+    if (red[RED_REFINE] == 0.0) return;
+    cgs_update_fs_block<K, NS>(nvp, coef, xs, y, dinv_uu, g32, b0);
 }
 
 template <int NS>
@@ -402,6 +495,44 @@ bool launch_cgs_update_fs(Ctx &c, int k, const double *const *xs, double *y, flo
         default: FEDM_CGSF(4); break;
     }
 #undef FEDM_CGSF
+    return true;
+}
+
+// The second pass behind step j's first pass and update (vs = {v_0 ... v_j}, t the step's vector, as its update left
+// it): three launches and the step's publication.  false: not instantiated for this case, nothing launched.
+bool cgs_refine_applicable(const Ctx &c, int j) { return c.ns == 2 && j >= 0 && j + 1 <= 4; }
+
+bool launch_cgs_refine(Ctx &c, int j, const double *const *vs, double *t, float *g32, double *b0) {
+    if (!cgs_refine_applicable(c, j)) return false;
+    const int k = j + 2, grid = red_grid(c);
+    PtrPack8 pk;
+    for (int i = 0; i < 8; ++i) pk.p[i] = i < k - 1 ? vs[i] : t;
+    double *coef = c.d_red + RED_K;
+#define FEDM_DR(K)                                                                                                  \
+    if (c.red_w) hipLaunchKernelGGL((dots_refine_kernel<K, true>), dim3(grid), dim3(256), 0, c.stream, pk, t,          \
+                                    (size_t)c.n_dot, c.d_partials, c.d_red, c.red_w);                                \
+    else hipLaunchKernelGGL(dots_refine_kernel<K>, dim3(grid), dim3(256), 0, c.stream, pk, t, (size_t)c.n_dot,       \
+                            c.d_partials, c.d_red)
+    switch (k) {
+        case 2: FEDM_DR(2); break;
+        case 3: FEDM_DR(3); break;
+        case 4: FEDM_DR(4); break;
+        default: FEDM_DR(5); break;
+    }
+#undef FEDM_DR
+    hipLaunchKernelGGL(refine_finish_kernel, dim3(1), dim3(1024), 0, c.stream, c.d_partials, grid, k, c.d_red, coef,
+                       c.h_mail, c.d_mail_seq);
+    if (!c.capturing) ++c.mail_seq;
+    const dim3 g((c.nvp + 255) / 256), b(256);
+#define FEDM_CR(K)                                                                                                  \
+    hipLaunchKernelGGL((cgs_refine_fs_kernel<K, 2>), g, b, 0, c.stream, c.nvp, c.d_red, coef, pk, t, c.d_dinv, g32, b0)
+    switch (j + 1) {
+        case 1: FEDM_CR(1); break;
+        case 2: FEDM_CR(2); break;
+        case 3: FEDM_CR(3); break;
+        default: FEDM_CR(4); break;
+    }
+#undef FEDM_CR
     return true;
 }
 

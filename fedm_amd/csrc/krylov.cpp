@@ -114,7 +114,7 @@ void prepare_preconditioner_and_rhs(Ctx &c) {
 
 void iter_graphs_clear(Ctx &c) {
     for (auto *vec : {&c.iter_graph, &c.iter_graph_interior, &c.iter_graph_pre, &c.iter_graph_pair, &c.iter_graph_last,
-                      &c.iter_graph_pair_last}) {
+                      &c.iter_graph_pair_last, &c.iter_graph_refined}) {
         for (hipGraphExec_t g : *vec)
             if (g) hipGraphExecDestroy(g);
         vec->clear();
@@ -191,7 +191,7 @@ struct DirectOutput {
 
 // w = J z with the dot products {v_0 ... v_j, w}.w: one kernel where it is instantiated, two otherwise
 static void product_and_dots(Ctx &c, const double *z, double *w, const double *const *dotp, int n, bool publish) {
-    if (!launch_spmv_dots(c, z, w, dotp, n, publish)) {
+    if (!launch_spmv_dots(c, z, w, dotp, n, publish ? SPMV_DOTS_PUBLISH : SPMV_DOTS_SUMS)) {
         launch_spmv(c, z, w, false);
         launch_dots_fused(c, dotp, w, n, nullptr, publish);
     }
@@ -352,6 +352,30 @@ static void right_step_one_gpu(Ctx &c, int j, const double *const *vp, double *z
     if (update) krylov_vector_update(c, j + 1, vp, w);
 }
 
+// One GPU, field split on the right, a step whose first Gram-Schmidt pass is expected to cancel (Ctx::KrylovHint): the
+// step with its update, then the second pass in the queue (launch_cgs_refine) -- the first finish writes the flag the
+// three kernels of the second pass read and leaves the step's one publication to them.  The fused product and the
+// fused update must apply (three equations, j < 4, the producers forming the preconditioner's first stage).
+static bool refined_step_applies(const Ctx &c, int j) {
+    return !c.comm && c.iter_graphs_ok && !(c.prof.on && c.prof.all_kinds) && c.fs_first_by_producer &&
+           !fieldsplit_upper(c) && spmv_dots_applicable(c, j + 2) && cgs_refine_applicable(c, j);
+}
+
+static bool iter_graph_launch_right_refined(Ctx &c, int j, const double *const *vp, double *z, double *w) {
+    if (!refined_step_applies(c, j)) return false;
+    return replay(c, c.iter_graph_refined, j, 1, [&] {
+        const bool direct = right_direct_output(c);
+        const std::vector<const double *> dotp = dot_operands(vp, j, w);
+        {
+            DirectOutput out(c, direct, z);
+            fieldsplit_apply(c, *c.amg, vp[j], z, 1.0, !direct);
+        }
+        launch_spmv_dots(c, z, w, dotp.data(), j + 2, SPMV_DOTS_REFINED);
+        krylov_vector_update(c, j + 1, vp, w);
+        launch_cgs_refine(c, j, vp, w, reinterpret_cast<float *>(c.d_fs_g), c.amg->levels[0].b);
+    });
+}
+
 // One GPU, field split on the right: Krylov steps j and j + 1 as ONE graph (a step needs nothing from the host, and
 // when the previous solve says that both will be needed they are launched together anyway; between two graph
 // launches the GPU idles for 8 us, tools/step_sequence.py).  Publishes twice: mail_seq advances by two.
@@ -485,7 +509,8 @@ static bool iter_graph_launch_right(Ctx &c, int j, const double *const *vp, doub
 // solve, and the norm tested is that of the true residual.  delta starts at 0; classical
 // Gram-Schmidt (PETSc's KSPGMRES default).
 int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int *its_out, double *rnorm_out,
-          const double *bvec, double bscale, double bnorm_known, double *u_update, bool *u_updated) {
+          const double *bvec, double bscale, double bnorm_known, double *u_update, bool *u_updated,
+          int newton_iteration) {
     if (restart < 1 || restart > RED_K - 10) {
         set_error("GMRES restart must be between 1 and 30");
         return -2;
@@ -541,6 +566,10 @@ int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int *its_ou
     if (u_updated) *u_updated = false;
     int64_t *ps = c.path_stats;
     ++ps[PS_SOLVES];
+    // what the last solve of this kind took (Ctx::KrylovHint); a slot without history: what the previous solve took
+    Ctx::KrylovHint &hint = c.krylov_hints[newton_iteration < 0 ? Ctx::KRYLOV_HINT_SLOTS
+                                                                : std::min(newton_iteration, Ctx::KRYLOV_HINT_SLOTS - 1)];
+    const int steps_hint = hint.its >= 0 ? hint.its : c.krylov_steps_hint;
     if (scaled) {
         // the weights of the Jacobian as it stands, and |D b|: the norm the caller knows is the unscaled one
         launch_row_scale(c, c.d_kscale2, nullptr);
@@ -635,6 +664,7 @@ int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int *its_ou
         bool done = false;
         std::deque<unsigned long long> queued;
         int update_skipped_for = -1;   // step whose vector has not been orthonormalised yet (launched as 'the last one')
+        uint32_t refined_launched = 0;   // bit q: step q went in with its second Gram-Schmidt pass behind it
         for (; j < m && its < max_it; ++j) {
             double *w = c.d_V + (size_t)(j + 1) * c.np;
             // classical Gram-Schmidt with ONE reduction and ONE host wait per iteration:
@@ -672,14 +702,19 @@ int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int *its_ou
             // launched when the queue has run empty, BEFORE this step's numbers are waited for -- so up to three
             // publications may be unread (MAIL_SLOTS).
             auto wanted = [&](int q) {   // step q is expected to be needed: launch it without waiting for step q - 1
-                return right && !c.comm && q < m && its + (q - j) < max_it && q < c.krylov_steps_hint;
+                return right && !c.comm && q < m && its + (q - j) < max_it && q < steps_hint;
             };
             // The step expected to end the solve (the previous solve's count; early in a run: the second one) goes in
             // WITHOUT the update that would orthonormalise its vector for a next step: 8 us of kernel nobody needs when
             // the guess is right; when it is wrong the update is launched by itself before the solve goes on.
             auto ends_here = [&](int q) {
-                return switches().skip_last_update && right && !c.comm && c.krylov_steps_hint >= 1 && c.krylov_steps_hint <= 4 &&
-                       q + 1 == c.krylov_steps_hint && cycle == 0;
+                return switches().skip_last_update && right && !c.comm && steps_hint >= 1 && steps_hint <= 4 &&
+                       q + 1 == steps_hint && cycle == 0;
+            };
+            // The last solve of this kind needed a second Gram-Schmidt pass at step q: the step goes in by itself with
+            // that pass queued behind it (never 'as the last one': the pass works on the updated vector)
+            auto refine_predicted = [&](int q) {
+                return right && cycle == 0 && q < 32 && ((hint.refine_mask >> q) & 1u) && refined_step_applies(c, q);
             };
             auto launch_from = [&](int q, bool first_is_needed) {
                 if (q > 0 && update_skipped_for == q - 1 && (first_is_needed || wanted(q))) {   // (the guess was wrong)
@@ -688,10 +723,16 @@ int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int *its_ou
                     ++ps[PS_UPDATES_MADE_UP];
                 }
                 const size_t queued_before = queued.size();
-                if ((first_is_needed || wanted(q)) && wanted(q + 1) &&
-                    iter_graph_launch_right_pair(c, q, vp.data(), c.d_Z + (size_t)q * c.np, c.d_V + (size_t)(q + 1) * c.np,
-                                                 c.d_Z + (size_t)(q + 1) * c.np, c.d_V + (size_t)(q + 2) * c.np,
-                                                 ends_here(q + 1))) {
+                if ((first_is_needed || wanted(q)) && refine_predicted(q) &&
+                    iter_graph_launch_right_refined(c, q, vp.data(), c.d_Z + (size_t)q * c.np,
+                                                    c.d_V + (size_t)(q + 1) * c.np)) {
+                    refined_launched |= 1u << q;
+                    ++ps[PS_STEPS_SINGLE];
+                    queued.push_back(c.mail_seq);
+                } else if ((first_is_needed || wanted(q)) && wanted(q + 1) && !refine_predicted(q + 1) &&
+                           iter_graph_launch_right_pair(c, q, vp.data(), c.d_Z + (size_t)q * c.np,
+                                                        c.d_V + (size_t)(q + 1) * c.np, c.d_Z + (size_t)(q + 1) * c.np,
+                                                        c.d_V + (size_t)(q + 2) * c.np, ends_here(q + 1))) {
                     if (ends_here(q + 1)) update_skipped_for = q + 1;
                     ps[PS_STEPS_PAIR] += ends_here(q + 1) ? 1 : 2;
                     ps[PS_STEPS_LAST] += ends_here(q + 1) ? 1 : 0;
@@ -738,15 +779,28 @@ int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int *its_ou
             double hn2 = c.h_red[j + 1];
             const double ww = c.h_red[RED_K - 2];
             double hn;
-            if (!(hn2 > 1e-8 * ww && hn2 > 0.0) && std::isfinite(ww) && ww > 0.0) {
+            // a refined step: 0 the first pass was sound after all, 1 the second pass ran behind it (hcol and hn2 are
+            // the refined ones), 2 it ran and the norm still cancels: the host's pass below, on the vector it left
+            const int refined = ((refined_launched >> j) & 1u) ? (int)c.h_red[RED_REFINE] : -1;
+            if (refined >= 0) {
+                refined_launched &= ~(1u << j);
+                if (refined == 0) hint.refine_mask &= ~(1u << j);
+            }
+            if (refined == 1) {
+                ++ps[PS_SECOND_PASSES];
+                ++ps[PS_SECOND_PASSES_DEVICE];
+                hn = std::sqrt(hn2);
+            } else if ((refined == 2 || !(hn2 > 1e-8 * ww && hn2 > 0.0)) && std::isfinite(ww) && ww > 0.0) {
                 // strong cancellation: w was left unscaled; refine (second CGS pass) and
                 // take the norm explicitly (a step launched ahead used the unrefined vector: let it
                 // finish, its results are dropped and the step is repeated)
                 ++ps[PS_SECOND_PASSES];
+                if (cycle == 0 && j < 32) hint.refine_mask |= 1u << j;   // the next solve of this kind refines in the queue
                 if (!queued.empty()) {
                     wait_red_seq(c, queued.back());
                     ps[PS_STEPS_DROPPED] += (int64_t)queued.size();
                     queued.clear();
+                    refined_launched = 0;
                     // a dropped step that went in 'as the last one' is launched again from scratch: its skipped
                     // update must not be made up for a second time behind the relaunch
                     if (update_skipped_for > j) update_skipped_for = -1;
@@ -818,6 +872,7 @@ int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int *its_ou
         }
     }
     c.krylov_steps_hint = its;
+    hint.its = its;
     ps[PS_STEPS_USED] += its;
     *its_out = its;
     *rnorm_out = rnorm;

@@ -22,7 +22,8 @@ void prepare_preconditioner_and_rhs(Ctx &c);
 void krylov_vector_update(Ctx &c, int k, const double *const *vp, double *w);
 void krylov_vector_scale(Ctx &c, double a, const double *x, double *y);
 int gmres(Ctx &c, int restart, double rtol, double atol, int max_it, int *its_out, double *rnorm_out,
-          const double *bvec, double bscale, double bnorm_known, double *u_update, bool *u_updated);
+          const double *bvec, double bscale, double bnorm_known, double *u_update, bool *u_updated,
+          int newton_iteration = -1);   // which solve of a Newton loop this is (-1: none): the hint slot it reads and writes
 int species_gmres(Ctx &c, int restart, double rtol, double atol, int max_it, double bnorm, int *its_out,
                   double *rnorm_out);
 // Preconditioned CG on the potential rows: the residual in c.d_rhs, the accumulated correction left in c.d_V

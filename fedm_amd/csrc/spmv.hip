@@ -434,6 +434,8 @@ __global__ __launch_bounds__(256) void spmv_dots_kernel(int n_slices, int n_owne
 // reduce_finish_kernel for the partials of spmv_dots_kernel (one per workgroup of the product: thousands, not
 // RED_BLOCKS): the 16 waves share the k <= 8 slots, wave w sums the blocks of chunk w / k of slot w % k, the chunks
 // are added in their order; then the formulae and the publication of cgs_finish_kernel.
+// finish: 0 the local sums only, 1 formulae and publication, 2 (a refined step, krylov.cpp) the formulae and the flag
+// out[RED_REFINE] = 1 when the cancellation was too strong, without a publication.
 __global__ __launch_bounds__(1024) void spmv_dots_finish_kernel(const double *__restrict__ partials, int nblocks,
                                                                int k, double *__restrict__ out, double *mail,
                                                                unsigned long long *seq, int finish) {
@@ -463,9 +465,15 @@ __global__ __launch_bounds__(1024) void spmv_dots_finish_kernel(const double *__
         const double hn2 = ww - hh;
         fin[RED_K - 2] = ww;
         fin[k - 1] = hn2;
-        fin[RED_K - 1] = (hn2 > 1e-8 * ww && hn2 > 0.0) ? 1.0 / sqrt(hn2) : 1.0;
+        const bool sound = hn2 > 1e-8 * ww && hn2 > 0.0;
+        fin[RED_K - 1] = sound ? 1.0 / sqrt(hn2) : 1.0;
+        if (finish == 2) fin[RED_REFINE] = sound ? 0.0 : 1.0;   // what the second pass behind this step reads
     }
     __syncthreads();
+    if (finish == 2) {   // a refined step: its one publication is refine_finish_kernel's
+        if (threadIdx.x < RED_K) out[threadIdx.x] = fin[threadIdx.x];
+        return;
+    }
     if (threadIdx.x < 64) {
         const unsigned long long tag = *seq + 1;
         double *slot_ = mail + (tag & (MAIL_SLOTS - 1)) * (RED_K + 1);
@@ -485,7 +493,7 @@ __global__ __launch_bounds__(1024) void spmv_dots_finish_kernel(const double *__
 // w = J z with the step's k = j + 2 reduction slots (xs[0 .. k-2] . w and w . w), finished and published: one GPU,
 // three species-plus-potential equations, k <= 8, buffers of ensure_spmv_dots.  false: not applicable (nothing was
 // launched; the caller runs launch_spmv + launch_dots_fused).
-static bool spmv_dots_applicable(const Ctx &c, int k) {
+bool spmv_dots_applicable(const Ctx &c, int k) {
     static const bool off = [] {
         const char *e = std::getenv("FEDM_SPMV_DOTS");
         return e && e[0] == '0';
@@ -494,7 +502,7 @@ static bool spmv_dots_applicable(const Ctx &c, int k) {
     return !off && c.neq == 3 && k >= 2 && k <= 8 && c.d_partials_wide;
 }
 
-bool launch_spmv_dots(Ctx &c, const double *x, double *y, const double *const *xs, int k, bool finish) {
+bool launch_spmv_dots(Ctx &c, const double *x, double *y, const double *const *xs, int k, int finish) {
     if (!spmv_dots_applicable(c, k)) return false;
     const int n = c.pat.n_slices;
     const dim3 g((n + 3) / 4), b(256);
@@ -525,8 +533,8 @@ bool launch_spmv_dots(Ctx &c, const double *x, double *y, const double *const *x
 #undef FEDM_SD_K
 #undef FEDM_SD
     hipLaunchKernelGGL(spmv_dots_finish_kernel, dim3(1), dim3(1024), 0, c.stream, c.d_partials_wide, (int)g.x, k,
-                       c.d_red, c.h_mail, c.d_mail_seq, finish ? 1 : 0);
-    if (finish && !c.capturing) ++c.mail_seq;
+                       c.d_red, c.h_mail, c.d_mail_seq, finish);
+    if (finish == SPMV_DOTS_PUBLISH && !c.capturing) ++c.mail_seq;
     return true;
 }
 

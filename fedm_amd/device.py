@@ -380,7 +380,7 @@ SOLVER_PATH_STATS = ("cycles", "steps_single", "steps_pair", "steps_last", "step
                      "second_passes", "fused_updates", "generic_updates", "deferred_norm", "nothing_to_solve",
                      "residual_only_right", "residual_only_wrong", "err_cache_served", "steps_used", "steps_ahead",
                      "steps_ahead_later", "solves", "breakdowns", "exhausted", "newton_max_it", "verified",
-                     "verify_failed")
+                     "verify_failed", "second_passes_device")
 
 # fedm_pattern_info's / fedm_launched_assembly's numbering of the volume-assembly kernels
 _VARIANTS = ("global colouring", "lds-patches/unrolled", "lds-patches", "lds-patches/one-pass",

@@ -524,7 +524,8 @@ int fedm_launched_assembly(fedm_ctx *ctx, int64_t out[8]);
  *  [17] GMRES solves   [18] happy breakdowns   [19] solves stopped by ksp_max_it   [20] Newton solves stopped by max_it
  *  [21] true residuals formed at the start of a cycle: at every restart, and before a solve that ended on the generic
  *       update reports success   [22] ... that contradicted the recurrence's 'converged' (another cycle ran, or the
- *       solve gave up with FEDM_DIVERGED_LINEAR because such a cycle had not halved the residual)   [23] reserved. */
+ *       solve gave up with FEDM_DIVERGED_LINEAR because such a cycle had not halved the residual)
+ *  [23] second Gram-Schmidt passes that ran on the device, queued behind their step ([6] counts them too). */
 int fedm_solver_path_stats(fedm_ctx *ctx, int64_t out[24], int reset);
 /* Test hook: x = the GMRES solution of J x = b with the Jacobian and the preconditioner as the last fedm_jacobian /
  * fedm_newton_solve left them, through the very call fedm_newton_solve makes (same preparation of the preconditioner
