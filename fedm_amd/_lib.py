@@ -12,7 +12,7 @@ MAX_QP, MAX_FQP, MAX_EXT_NODES = 32, 8, 10
 MAX_TABLES, MAX_TABLE_KNOTS = 16, 4096
 
 EQ_TYPES = {"reaction": 0, "diffusion-reaction": 1, "drift-diffusion-reaction": 2}
-BC_KINDS = {"zero flux": 0, "Neumann": 1}
+BC_KINDS = {"zero flux": 0, "Neumann": 1, "flux source": 2}
 DIVERGED = {1: "maximum number of Newton iterations reached",
             2: "NaN or Inf in the residual", 3: "linear solve (GMRES) did not converge"}
 
@@ -43,6 +43,12 @@ class ModelDesc(C.Structure):
         ("ext_B", (C.c_double * MAX_EXT_NODES) * MAX_QP),
         ("linear_representation", C.c_int32), ("pad2_", C.c_int32),
     ]
+
+
+class WallDesc(C.Structure):
+    _fields_ = [("vth", (C.c_double * MAX_SPECIES) * MAX_TAGS), ("ref", (C.c_double * MAX_SPECIES) * MAX_TAGS),
+                ("gamma", C.c_double * MAX_TAGS),
+                ("emits", C.c_int32 * MAX_SPECIES), ("is_ion", C.c_int32 * MAX_SPECIES)]
 
 
 GD_MAX_SPECIES, GD_MAX_REACTIONS = 6, 16
@@ -124,6 +130,8 @@ _SIGNATURES = {
     "fedm_ctx_create": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(ModelDesc), C.c_int, C.POINTER(_P)]),
     "fedm_ctx_create_tabulated": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(ModelDesc), C.c_int, C.POINTER(C.c_int32),
                                             _D, _D, C.c_int, C.POINTER(_P)]),
+    "fedm_ctx_create_walls": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(ModelDesc), C.POINTER(WallDesc), C.c_int,
+                                        C.POINTER(C.c_int32), _D, _D, C.c_int, C.POINTER(_P)]),
     "fedm_ctx_create_gd": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(GdDesc), C.c_int, C.POINTER(_P)]),
     "fedm_gd_set_fields": (C.c_int, [_P, _D]),
     "fedm_gd_get_fields": (C.c_int, [_P, _D]),

@@ -602,7 +602,8 @@ static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
 // =============================================================================================
 // SPECIES_COLS: the species columns only (the segregated step's species assembly: the planes of the potential column
 // are not touched)
-template <int NS, bool ATOMIC, bool SPECIES_COLS = false, bool TAB = false>
+// WALL: the 'flux source' wall terms besides (element.hpp, wall_facet; Ctx::model_walls)
+template <int NS, bool ATOMIC, bool SPECIES_COLS = false, bool TAB = false, bool WALL = false>
 __global__ void boundary_kernel(const fedm_model_desc *__restrict__ md, int n_facets,
                                 const int *__restrict__ facets /* [n][3] = cell, local facet, tag */,
                                 const int *__restrict__ cells, const double *__restrict__ coords,
@@ -633,20 +634,22 @@ __global__ void boundary_kernel(const fedm_model_desc *__restrict__ md, int n_fa
         if (ATOMIC) unsafeAtomicAdd(p, value);
         else *p += value;
     };
-    boundary_facet<NS, TAB>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
+    boundary_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
 }
 
 template <bool ATOMIC>
 static void launch_boundary_range(Ctx &c, bool jacobian, int f0, int n) {
     const dim3 g((n + 127) / 128), b(128);
     const int *fl = c.d_bfacets + 3 * f0;
-#define FEDM_BK(NS_, TAB_)                                                                                          \
-    hipLaunchKernelGGL((boundary_kernel<NS_, ATOMIC, false, TAB_>), g, b, 0, c.stream, c.d_model, n, fl, c.d_cells,  \
-                       c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0)
+#define FEDM_BK(NS_, TAB_, WALL_)                                                                                   \
+    hipLaunchKernelGGL((boundary_kernel<NS_, ATOMIC, false, TAB_, WALL_>), g, b, 0, c.stream, c.d_model, n, fl,      \
+                       c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0)
 #define FEDM_BK_CASE(NS_)                                                                                           \
     case NS_:                                                                                                       \
-        if (c.model_tables) FEDM_BK(NS_, true);                                                                     \
-        else FEDM_BK(NS_, false);                                                                                   \
+        if (c.model_walls && c.model_tables) FEDM_BK(NS_, true, true);                                              \
+        else if (c.model_walls) FEDM_BK(NS_, false, true);                                                          \
+        else if (c.model_tables) FEDM_BK(NS_, true, false);                                                         \
+        else FEDM_BK(NS_, false, false);                                                                            \
         break;
     switch (c.ns) {
         FEDM_BK_CASE(1)
@@ -867,7 +870,7 @@ __global__ void identity_rows_kernel(int nv, int nvp, int neq, int ns_frozen,
 
 // boundary_kernel<NS, true> and dirichlet_kernel in one launch (128-thread blocks: the first ones take the facets, the
 // rest the Dirichlet and padding rows) -- allowed when no row belongs to both (Ctx::boundary_rows_disjoint)
-template <int NS, bool TAB>
+template <int NS, bool TAB, bool WALL = false>
 __global__ __launch_bounds__(128) void boundary_dirichlet_kernel(
     const fedm_model_desc *__restrict__ md, int n_facets, int facet_blocks, const int *__restrict__ facets,
     const int *__restrict__ cells, const double *__restrict__ coords, const uint32_t *__restrict__ cell_slots,
@@ -892,7 +895,7 @@ __global__ __launch_bounds__(128) void boundary_dirichlet_kernel(
             const uint32_t slot = cell_slots[(size_t)c * 9 + a * 3 + b];
             unsafeAtomicAdd(&val[((size_t)(slot >> 6) * NEQ2 + sr * NEQ + scol) * SLICE + (slot & 63)], value);
         };
-        boundary_facet<NS, TAB>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
+        boundary_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
         return;
     }
     // the rows of dirichlet_kernel (one GPU: Dirichlet dofs, then the padding vertices [id_first, id_first + n_id))
@@ -927,14 +930,16 @@ void launch_finalize(Ctx &c, bool jacobian, int mode) {
         if (mode == 0 && jac == jacobian) {
             const int fb = (c.n_bfacets + 127) / 128, n_id = c.nvp - c.nv;
             const int rb = (c.n_dir + n_id + 127) / 128;
-#define FEDM_BD_T(NS_, TAB_)                                                                                      \
-    hipLaunchKernelGGL((boundary_dirichlet_kernel<NS_, TAB_>), dim3(fb + rb), dim3(128), 0, c.stream, c.d_model, c.n_bfacets, fb, \
+#define FEDM_BD_T(NS_, TAB_, WALL_)                                                                               \
+    hipLaunchKernelGGL((boundary_dirichlet_kernel<NS_, TAB_, WALL_>), dim3(fb + rb), dim3(128), 0, c.stream, c.d_model, c.n_bfacets, fb, \
                        c.d_bfacets, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0, c.n_dir, \
                        c.d_dir_dofs, c.d_dir_vals, c.d_slice_boff, c.d_diag_slot, c.nv, n_id)
 #define FEDM_BD(NS_)                                                                                              \
     do {                                                                                                          \
-        if (c.model_tables) FEDM_BD_T(NS_, true);                                                                 \
-        else FEDM_BD_T(NS_, false);                                                                               \
+        if (c.model_walls && c.model_tables) FEDM_BD_T(NS_, true, true);                                          \
+        else if (c.model_walls) FEDM_BD_T(NS_, false, true);                                                      \
+        else if (c.model_tables) FEDM_BD_T(NS_, true, false);                                                     \
+        else FEDM_BD_T(NS_, false, false);                                                                        \
     } while (0)
             if (c.ns == 1) FEDM_BD(1);
             else if (c.ns == 2) FEDM_BD(2);

@@ -84,6 +84,7 @@ struct HostTables {
     const int32_t *ptr = nullptr;
     const double *x = nullptr, *y = nullptr;
     const char *who = "fedm_ctx_create";   // the entry point, for the messages
+    const fedm_wall_desc *walls = nullptr; // fedm_ctx_create_walls (checked by check_walls)
 };
 
 // Every table reference of the model against the tables: 0, or 1 with the message set.  The kernels trust both.
@@ -161,10 +162,74 @@ static int check_tables(const fedm_model_desc &m, const HostTables &t) {
     return 0;
 }
 
-// {fedm_model_desc; ModelTables; x; y} in one device allocation (fedm_internal.hpp, ModelTables)
+// a (tag, species) of the model is a 'flux source' wall
+static bool has_walls(const fedm_model_desc &m) {
+    for (int t = 0; t < m.n_tags; ++t)
+        for (int s = 0; s < m.n_species; ++s)
+            if (m.bc_kind[t][s] == FEDM_BC_FLUX_SOURCE) return true;
+    return false;
+}
+
+// the species of a 'flux source' entry that the facet kernels give an emission term (element.hpp, wall_facet)
+static bool wall_emitter(const fedm_model_desc &m, const fedm_wall_desc &w, int t, int s) {
+    return m.bc_kind[t][s] == FEDM_BC_FLUX_SOURCE && m.eq_type[s] == FEDM_EQ_DRIFT_DIFFUSION_REACTION && w.emits[s] != 0;
+}
+
+// Every 'flux source' entry of the model against the wall description: 0, or 1 with the message set (it names the tag
+// as the mesh numbers it, from 1, and the species).  The kernels trust both.
+static int check_walls(const fedm_model_desc &m, const HostTables &t) {
+    const std::string who = std::string(t.who) + ": ";
+    if (!has_walls(m)) return 0;
+    const fedm_wall_desc *w = t.walls;
+    for (int tg = 0; tg < m.n_tags; ++tg) {
+        const std::string tag = "tag " + std::to_string(tg + 1);
+        bool any = false, emitter = false;
+        for (int s = 0; s < m.n_species; ++s) {
+            if (m.bc_kind[tg][s] != FEDM_BC_FLUX_SOURCE) continue;
+            const std::string at = "'flux source' on " + tag + ", species " + std::to_string(s);
+            any = true;
+            if (!w) {
+                set_error(who + at + " needs a wall description (fedm_ctx_create_walls)");
+                return 1;
+            }
+            if (!m.poisson) {
+                set_error(who + at + ": the model has no Poisson equation (no E; the facet kernels need one)");
+                return 1;
+            }
+            if (!std::isfinite(w->ref[tg][s]) || 1.0 + w->ref[tg][s] == 0.0) {
+                set_error(who + at + ": the reflection coefficient must be finite and not -1");
+                return 1;
+            }
+            if (!std::isfinite(w->vth[tg][s]) || w->vth[tg][s] < 0.0) {
+                set_error(who + at + ": the thermal velocity must be finite and not negative");
+                return 1;
+            }
+            if (m.eq_type[s] == FEDM_EQ_DRIFT_DIFFUSION_REACTION && m.has_drift_w[s]) {
+                set_error(who + at + ": a species with a constant drift velocity (has_drift_w) cannot meet a wall");
+                return 1;
+            }
+            emitter = emitter || wall_emitter(m, *w, tg, s);
+        }
+        if (!any) continue;
+        if (!std::isfinite(w->gamma[tg])) {
+            set_error(who + "the secondary emission coefficient of " + tag + " is not finite");
+            return 1;
+        }
+        if (w->gamma[tg] != 0.0 && !emitter) {
+            set_error(who + "secondary emission on " + tag + " (gamma = " + std::to_string(w->gamma[tg]) +
+                      "), but none of its 'flux source' drift-diffusion species has emits");
+            return 1;
+        }
+    }
+    return 0;
+}
+
+// {fedm_model_desc; ModelTables; x; y; [fedm_wall_desc]} in one device allocation (fedm_internal.hpp, ModelTables)
 static int upload_model(fedm_model_desc *&dst, const fedm_model_desc &m, const HostTables &t) {
     const int total = t.n > 0 ? t.ptr[t.n] : 0;
-    std::vector<unsigned char> buf(sizeof(fedm_model_desc) + sizeof(ModelTables) + sizeof(double) * 2 * (size_t)total);
+    const size_t wall_at = sizeof(fedm_model_desc) + sizeof(ModelTables) + sizeof(double) * 2 * (size_t)total;
+    std::vector<unsigned char> buf(wall_at + (t.walls ? sizeof(fedm_wall_desc) : 0));
+    if (t.walls) std::memcpy(buf.data() + wall_at, t.walls, sizeof(fedm_wall_desc));
     std::memcpy(buf.data(), &m, sizeof(m));
     ModelTables mt{};
     mt.n_tables = t.n;
@@ -241,7 +306,7 @@ static int ctx_create_lfa(const fedm_mesh_desc *mesh, const fedm_model_desc *mod
                   " quadrature points)");
         return -2;
     }
-    if (check_tables(*model, tables)) return -2;
+    if (check_tables(*model, tables) || check_walls(*model, tables)) return -2;
     return ctx_create_guarded(mesh, model, nullptr, tables, device, out);
 }
 
@@ -264,6 +329,24 @@ int fedm_ctx_create_tabulated(const fedm_mesh_desc *mesh, const fedm_model_desc 
         return -2;
     }
     if (n_tables == 0) t.ptr = nullptr;   // (no tables: fedm_ctx_create)
+    return ctx_create_lfa(mesh, model, t, device, out);
+}
+
+int fedm_ctx_create_walls(const fedm_mesh_desc *mesh, const fedm_model_desc *model, const fedm_wall_desc *walls,
+                          int n_tables, const int32_t *tab_ptr, const double *tab_x, const double *tab_y, int device,
+                          fedm_ctx **out) {
+    HostTables t;
+    t.n = n_tables;
+    t.ptr = tab_ptr;
+    t.x = tab_x;
+    t.y = tab_y;
+    t.who = "fedm_ctx_create_walls";
+    t.walls = walls;
+    if (n_tables > 0 && !tab_ptr) {
+        set_error("fedm_ctx_create_walls: null tab_ptr");
+        return -2;
+    }
+    if (n_tables == 0) t.ptr = nullptr;
     return ctx_create_lfa(mesh, model, t, device, out);
 }
 
@@ -405,6 +488,7 @@ static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *mo
         for (int s_ = 0; s_ < model->n_species; ++s_)
             c.model_tables = c.model_tables || model->mu[s_].pad_ != 0 || model->D[s_].pad_ != 0;
         for (int j = 0; j < model->n_reactions; ++j) c.model_tables = c.model_tables || model->k[j].pad_ != 0;
+        c.model_walls = has_walls(*model);
         c.ns = model->n_species;
         c.poisson = model->poisson != 0;
     } else {  // LMEA: energy + (n_species - 1) particle equations + potential
@@ -565,6 +649,11 @@ static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *mo
                     bool coupled = false;
                     for (int j = 0; j < model->n_reactions; ++j)
                         coupled = coupled || (model->net[j][s_] != 0 && model->power[j][i] > 0);
+                    // ... or a wall gives species s the secondary electrons of ion i (element.hpp, wall_facet): the
+                    // facet kernels add to that plane after every volume assembly, so it is neither kept nor skipped
+                    for (int tg = 0; tables.walls && tg < model->n_tags; ++tg)
+                        coupled = coupled || (wall_emitter(*model, *tables.walls, tg, s_) && tables.walls->gamma[tg] != 0.0 &&
+                                              tables.walls->is_ion[i] != 0 && model->eq_type[i] != FEDM_EQ_REACTION);
                     if (!coupled) c.const_plane_mask |= 1u << (s_ * c.neq + i);
                 }
             c.zero_plane_mask = c.const_plane_mask & ~(1u << (c.ns * c.neq + c.ns));

@@ -463,13 +463,123 @@ struct Element {
     }
 };
 
+// The wall description of a model with 'flux source' boundaries (fedm_ctx_create_walls): it follows the tables in the
+// descriptor's device allocation (context.cpp, upload_model), so no kernel signature changes.
+__device__ __forceinline__ const fedm_wall_desc *model_walls(const fedm_model_desc *__restrict__ md) {
+    const ModelTables *mt = reinterpret_cast<const ModelTables *>(md + 1);
+    return reinterpret_cast<const fedm_wall_desc *>(reinterpret_cast<const double *>(mt + 1) + 2 * mt->n_knots);
+}
+
+// 'flux source' wall of one tagged facet (fedm/functions.py:514-522, fedm-gd.py:346-351), per species s of kind 2:
+//   g = (1 - ref)/(1 + ref) (vth/2 [+ |Z mu E.n|]) n_s  [- 2 gamma/(1 + ref) sum_(i: ion) max(Gamma_i.n, 0)]
+//   R[a][s] += 2 pi r_q w_q L phi_a g,      Gamma_i.n = -D_i grad(n_i).n + Z_i mu_i E.n n_i
+// with the cell-constant E and coefficients of the LFA path.  The Jacobian is exact: own species, the potential
+// (through mu, D and E.n) and the ions of an emitting row; d|x| = sign(x) with sign(0) = 1 and max(x, 0) =
+// (x + |x|)/2 as in gd.hip (dabs).  j, k: the facet's vertices; gbn[b] = G_b.n, so that d(E.n)/dPhi_b = -gbn[b].
+template <int NS, bool TAB, class AddR, class AddJ>
+__device__ void wall_facet(const fedm_model_desc *__restrict__ md, const CellGeom &cg, const double Uc[3][NS + 1],
+                           int fi, int j, int k, int tag, double L, double Em, double lnE, double En,
+                           const double dEm[3], const double gbn[3], bool jacobian, AddR addR, AddJ addJ) {
+    const double two_pi = 6.283185307179586476925286766559;
+    const fedm_wall_desc *__restrict__ wd = model_walls(md);
+    const bool lin = md->linear_representation != 0;
+    const double invEm = 1.0 / Em;
+    for (int s = 0; s < NS; ++s) {
+        const int et = md->eq_type[s];
+        if (md->bc_kind[tag - 1][s] != FEDM_BC_FLUX_SOURCE || et == FEDM_EQ_REACTION) continue;
+        const double ref = wd->ref[tag - 1][s], fac = (1.0 - ref) / (1.0 + ref);
+        const bool drift = et == FEDM_EQ_DRIFT_DIFFUSION_REACTION && !md->has_drift_w[s];
+        double absa = 0.0, dabsa[3] = {0.0, 0.0, 0.0};   // |Z mu E.n| and its derivative by Phi_b
+        if (drift) {
+            double muv, mud;
+            termsum_eval<TAB>(md, md->mu[s], Em, invEm, lnE, muv, mud);
+            const double a = md->Z[s] * muv * En, sg = a < 0.0 ? -1.0 : 1.0;
+            absa = sg * a;
+            for (int b = 0; b < 3; ++b) dabsa[b] = sg * md->Z[s] * (mud * dEm[b] * En - muv * gbn[b]);
+        }
+        const double cs = fac * (0.5 * wd->vth[tag - 1][s] + absa);
+        double EM1[3] = {0.0, 0.0, 0.0}, EM2[3][3] = {{0.0}};
+        for (int t = 0; t < md->n_fqp; ++t) {
+            double phi[3] = {0.0, 0.0, 0.0};
+            phi[j] = 1.0 - md->fqp_t[t];
+            phi[k] = md->fqp_t[t];
+            const double rq = cg.rn[0] * phi[0] + cg.rn[1] * phi[1] + cg.rn[2] * phi[2];
+            const double uq = Uc[0][s] * phi[0] + Uc[1][s] * phi[1] + Uc[2][s] * phi[2];
+            const double n = lin ? uq : exp(uq);
+            const double W0 = md->fqp_w[t] * L * two_pi * rq;
+            const double We = W0 * n, Wd = lin ? W0 : We;   // d n / d u_b = phi_b (linear) or n phi_b
+            for (int a = 0; a < 3; ++a) {
+                EM1[a] += We * phi[a];
+                for (int b = 0; b < 3; ++b) EM2[a][b] += Wd * phi[a] * phi[b];
+            }
+        }
+        for (int a = 0; a < 3; ++a) {
+            if (a == fi) continue;  // phi_a vanishes on the facet
+            addR(a, s, cs * EM1[a]);
+            if (!jacobian) continue;
+            for (int b = 0; b < 3; ++b) {
+                addJ(a, b, s, s, cs * EM2[a][b]);
+                if (drift) addJ(a, b, s, NS, fac * dabsa[b] * EM1[a]);
+            }
+        }
+        // secondary emission: - 2 gamma/(1 + ref) sum_i max(Gamma_i.n, 0) in the row of the emitting species
+        const double gam = wd->gamma[tag - 1];
+        if (!drift || !wd->emits[s] || gam == 0.0) continue;
+        const double ce = -2.0 * gam / (1.0 + ref);
+        for (int i = 0; i < NS; ++i) {
+            if (!wd->is_ion[i] || md->eq_type[i] == FEDM_EQ_REACTION) continue;
+            double Dv, Dd, muv = 0.0, mud = 0.0;
+            termsum_eval<TAB>(md, md->D[i], Em, invEm, lnE, Dv, Dd);
+            if (md->eq_type[i] == FEDM_EQ_DRIFT_DIFFUSION_REACTION && !md->has_drift_w[i])
+                termsum_eval<TAB>(md, md->mu[i], Em, invEm, lnE, muv, mud);
+            const double zm = md->Z[i] * muv, zd = md->Z[i] * mud;
+            const double gun = Uc[0][i] * gbn[0] + Uc[1][i] * gbn[1] + Uc[2][i] * gbn[2];   // grad(u_i).n
+            double P1[3] = {0.0, 0.0, 0.0};                    // sum W0 phi_a max(Gamma_i.n, 0)
+            double HU[3][3] = {{0.0}}, HP[3][3] = {{0.0}};     // sum W0 phi_a h dGamma_n/du_i[b], .../dPhi[b]
+            for (int t = 0; t < md->n_fqp; ++t) {
+                double phi[3] = {0.0, 0.0, 0.0};
+                phi[j] = 1.0 - md->fqp_t[t];
+                phi[k] = md->fqp_t[t];
+                const double rq = cg.rn[0] * phi[0] + cg.rn[1] * phi[1] + cg.rn[2] * phi[2];
+                const double uq = Uc[0][i] * phi[0] + Uc[1][i] * phi[1] + Uc[2][i] * phi[2];
+                const double n = lin ? uq : exp(uq);
+                const double gnn = lin ? gun : n * gun;        // grad(n_i).n
+                const double Gn = -Dv * gnn + zm * En * n;
+                const double W0 = md->fqp_w[t] * L * two_pi * rq;
+                const double h = Gn < 0.0 ? 0.0 : 1.0;         // d max(x, 0) = (1 + sign(x))/2
+                for (int a = 0; a < 3; ++a) {
+                    const double Wa = W0 * phi[a];
+                    P1[a] += Wa * h * Gn;
+                    for (int b = 0; b < 3; ++b) {
+                        const double dn = lin ? phi[b] : n * phi[b];
+                        const double dgnn = lin ? gbn[b] : dn * gun + n * gbn[b];
+                        HU[a][b] += Wa * h * (-Dv * dgnn + zm * En * dn);
+                        HP[a][b] += Wa * h * (-Dd * dEm[b] * gnn + (zd * dEm[b] * En - zm * gbn[b]) * n);
+                    }
+                }
+            }
+            for (int a = 0; a < 3; ++a) {
+                if (a == fi) continue;
+                addR(a, s, ce * P1[a]);
+                if (!jacobian) continue;
+                for (int b = 0; b < 3; ++b) {
+                    addJ(a, b, s, i, ce * HU[a][b]);
+                    addJ(a, b, s, NS, ce * HP[a][b]);
+                }
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
-// Neumann boundary flux of one tagged facet (fedm/functions.py:523-524):
+// Neumann boundary flux of one tagged facet (fedm/functions.py:523-524; the 'flux source' wall term: wall_facet):
 //   2*pi * (Z mu E.n) exp(u) v r ds     on the edge opposite local vertex `fi`.
 // Contributions are added with global fp64 atomics (a few thousand facets; adjacent facets
 // share a vertex).  R: [3][NEQ] residual, blocks via `add(a, b, s_row, s_col, value)`.
 // ---------------------------------------------------------------------------------------------
-template <int NS, bool TAB, class AddR, class AddJ>
+// WALL: the model has 'flux source' walls (Ctx::model_walls): a compile-time switch chosen on the host per model, like
+// TAB, so that the kernels of every other model are the ones they were.
+template <int NS, bool TAB, bool WALL, class AddR, class AddJ>
 __device__ void boundary_facet(const fedm_model_desc *__restrict__ md, const double x[3][2],
                                const double Uc[3][NS + 1], int fi, int tag, bool jacobian,
                                AddR addR, AddJ addJ) {
@@ -527,6 +637,11 @@ __device__ void boundary_facet(const fedm_model_desc *__restrict__ md, const dou
                 addJ(a, b, s, NEQ - 1, (zd * dEm[b] * En - zm * gbn) * EM1[a]);
             }
         }
+    }
+    if constexpr (WALL) {
+        double gbn[3];
+        for (int b = 0; b < 3; ++b) gbn[b] = cg.G[b][0] * nrm[0] + cg.G[b][1] * nrm[1];
+        wall_facet<NS, TAB>(md, cg, Uc, fi, j, k, tag, L, Em, lnE, En, dEm, gbn, jacobian, addR, addJ);
     }
 }
 

@@ -58,13 +58,15 @@ void build_pattern(const fedm_mesh_desc &mesh, Pattern &pat, bool allow_rotation
 // The tabulated coefficient factors of an LFA model (fedm_ctx_create_tabulated).  The device copy of the model is one
 // allocation {fedm_model_desc; ModelTables; double x[n_knots]; double y[n_knots]}: whoever holds the descriptor's
 // device pointer reaches the tables (element.hpp, termsum_eval) and no kernel signature changes.  A model without
-// tables carries the header alone (n_tables = 0); nothing reads it then.
+// tables carries the header alone (n_tables = 0); nothing reads it then.  A model with 'flux source' walls carries
+// its fedm_wall_desc behind y (element.hpp, model_walls).
 struct ModelTables {
     int32_t n_tables, n_knots;
     int32_t ptr[FEDM_MAX_TABLES + 1];   // knots of table t: [ptr[t], ptr[t + 1])
     int32_t pad_;
 };
 static_assert(sizeof(fedm_model_desc) % 8 == 0 && sizeof(ModelTables) % 8 == 0, "the knots follow as doubles");
+static_assert(sizeof(fedm_wall_desc) % 8 == 0, "the walls follow the knots");
 
 struct Amg;
 struct Comm;
@@ -110,6 +112,7 @@ struct Ctx {
     int64_t n = 0, np = 0;  // nv*neq, nvp*neq
     fedm_model_desc model{};
     bool model_tables = false;   // some coefficient has a tabulated factor (fedm_ctx_create_tabulated): the TAB kernels
+    bool model_walls = false;    // some (tag, species) is a 'flux source' wall (fedm_ctx_create_walls): the WALL kernels
     int assembly_lean = 3;   // patch assembly generation where it applies: 0 unrolled element, 2 one equation
                              // row at a time (element_lean.hpp), 3 one pass over the cells (assemble3.hip)
     bool xcd_remap = true;   // patch / slice -> workgroup mapping contiguous per XCD

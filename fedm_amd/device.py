@@ -31,6 +31,30 @@ class Reaction:
 
 
 @dataclass
+class Walls:
+    """The 'flux source' walls of an LFA model (Boundary_flux, fedm/functions.py:514-522): thermal velocity and
+    reflection coefficient per (tag, species), secondary emission coefficient per tag, the species that receives the
+    secondary electrons and the ions whose wall flux releases them."""
+    vth: Sequence[Sequence[float]]             # [tag-1][species]
+    ref: Sequence[Sequence[float]]             # [tag-1][species]
+    gamma: Sequence[float]                     # [tag-1]
+    emits: Sequence[bool]                      # [species]
+    is_ion: Sequence[bool]                     # [species]
+
+    def to_c(self, n_species):
+        wd = _lib.WallDesc()
+        if not len(self.vth) == len(self.ref) == len(self.gamma) <= _lib.MAX_TAGS:
+            raise ValueError(f"Walls: vth, ref and gamma need one entry per boundary tag, at most {_lib.MAX_TAGS}")
+        for t in range(len(self.gamma)):
+            wd.gamma[t] = float(self.gamma[t])
+            for s in range(n_species):
+                wd.vth[t][s], wd.ref[t][s] = float(self.vth[t][s]), float(self.ref[t][s])
+        for s in range(n_species):
+            wd.emits[s], wd.is_ion[s] = int(bool(self.emits[s])), int(bool(self.is_ion[s]))
+        return wd
+
+
+@dataclass
 class Model:
     """What fedm.functions' weak-form builders describe (see functions.py)."""
     n_species: int
@@ -46,10 +70,21 @@ class Model:
     ext_source_degree: Sequence[int] = ()      # 0 = none, k = Expression(degree=k) source
     axisymmetric: bool = True
     log_representation: bool = True            # False: the unknowns are the densities (functions.py:350-368)
+    walls: Optional[Walls] = None              # for the 'flux source' entries of bc_kind
 
     @property
     def n_eq(self):
         return self.n_species + (1 if self.poisson else 0)
+
+    def walls_to_c(self):
+        """fedm_wall_desc for fedm_ctx_create_walls, or None for a model without 'flux source' entries."""
+        if not any(k == "flux source" for row in self.bc_kind for k in row):
+            return None
+        if self.walls is None:
+            raise ValueError("a model with 'flux source' boundaries needs walls=Walls(...)")
+        if len(self.walls.gamma) != len(self.bc_kind):
+            raise ValueError(f"Walls describes {len(self.walls.gamma)} boundary tags, bc_kind {len(self.bc_kind)}")
+        return self.walls.to_c(self.n_species)
 
     def to_c_tabulated(self):
         """The descriptor and the model's distinct coefficient tables as fedm_ctx_create_tabulated takes them:
@@ -461,7 +496,13 @@ class DeviceProblem:
             mesh.identity_vertices = self._identity.ctypes.data_as(C.POINTER(C.c_int32))
             mesh.halo_depth = self.halo_depth
         handle = C.c_void_p()
-        if tab is not None:     # tabulated E/N coefficients: looked up in the element routines
+        wd = None if isinstance(model, GdModel) else model.walls_to_c()
+        if wd is not None:      # 'flux source' walls (with or without tables)
+            tab_ptr, tab_x, tab_y = tab if tab is not None else (np.zeros(1, dtype=np.int32), np.zeros(0), np.zeros(0))
+            rc = self.lib.fedm_ctx_create_walls(C.byref(mesh), C.byref(md), C.byref(wd), tab_ptr.size - 1,
+                                                tab_ptr.ctypes.data_as(C.POINTER(C.c_int32)), _dp(tab_x), _dp(tab_y),
+                                                int(device), C.byref(handle))
+        elif tab is not None:   # tabulated E/N coefficients: looked up in the element routines
             tab_ptr, tab_x, tab_y = tab
             rc = self.lib.fedm_ctx_create_tabulated(C.byref(mesh), C.byref(md), tab_ptr.size - 1,
                                                     tab_ptr.ctypes.data_as(C.POINTER(C.c_int32)), _dp(tab_x),

@@ -232,6 +232,83 @@ def _match_manual_flux(gamma, index):
     return float(D), (float(w[0]), float(w[1]))
 
 
+def _lower_walls(bterms, balances, n_tags, mu, Z, poisson):
+    """The 'flux source' boundary terms of an LFA form (fedm/functions.py:514-522) as device.Walls, or None when there
+    are none.  With the discipline of lmea.compile_lmea: only what the facet kernels evaluate is accepted, anything
+    else raises a ValueError that names the term."""
+    from . import forms
+    from .device import Walls
+    from .lmea import IonFlux
+    from .termsum import TermSum
+    wall_terms = [b for b in bterms if b.kind == "flux source"]
+    if not wall_terms:
+        return None
+    ns = len(balances)
+
+    def number(x):
+        if isinstance(x, forms.Constant) and not isinstance(x.value, tuple):
+            x = x.value
+        return float(x) if isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool) else None
+
+    vth = [[0.0] * ns for _ in range(n_tags)]
+    ref = [[1.0] * ns for _ in range(n_tags)]
+    gamma, gamma_set = [0.0] * n_tags, [False] * n_tags
+    emits, is_ion = [False] * ns, [False] * ns
+    ion_sums = []
+    for b in wall_terms:
+        s, t = b.u.index, b.tag - 1
+        where = f"Boundary_flux('flux source') of species {s} on tag {b.tag}"
+        if not poisson:
+            raise ValueError(f"{where}: the device kernels evaluate walls in models with a Poisson equation only")
+        if b.equation_type != balances[s].equation_type:
+            raise ValueError(f"{where}: equation type '{b.equation_type}', but the balance equation of the species "
+                             f"is '{balances[s].equation_type}'")
+        v, r = number(b.vth), number(b.ref)
+        if v is None or r is None:
+            raise ValueError(f"{where}: vth and ref must be numbers")
+        vth[t][s], ref[t][s] = v, r
+        if b.equation_type != "drift-diffusion-reaction":
+            continue                   # the thermal flux alone (functions.py:516)
+        flux = balances[s].Gamma
+        if not isinstance(flux, FluxDesc):
+            raise ValueError(f"{where}: the species needs Gamma = Flux(...) (a constant drift velocity cannot meet a wall)")
+        sign = number(b.sign)
+        try:
+            same_mu = TermSum.coerce(b.mu).same_as(mu[s])
+        except Exception:              # noqa: BLE001 - whatever cannot be read as a coefficient is not the mobility
+            same_mu = False
+        if not same_mu or sign is None or sign != float(flux.sign):
+            raise ValueError(f"{where}: mu and sign must be those of the species' Flux")
+        if b.particle_type != "electrons":
+            continue                   # gamma and Ion_flux are not used (functions.py:519)
+        g = number(b.gamma)
+        if g is None:
+            raise ValueError(f"{where}: gamma must be a number")
+        if gamma_set[t] and gamma[t] != g:
+            raise ValueError(f"{where}: gamma differs from another emitting species' on the same tag ({g}, {gamma[t]})")
+        gamma[t], gamma_set[t] = g, True
+        emits[s] = True
+        if isinstance(b.Ion_flux, IonFlux):
+            ion_sums.append((where, b.Ion_flux))
+        elif not (number(b.Ion_flux) == 0.0 and g == 0.0):
+            raise ValueError(f"{where}: Ion_flux must be the sum of Max(dot(Gamma_ion, normal), 0) over the ions, "
+                             "or 0 with gamma = 0")
+    members = None
+    for where, ion in ion_sums:
+        idx = set()
+        for fl in ion.fluxes:
+            i = getattr(fl.u, "index", None)
+            if i is None or not 0 <= i < ns or balances[i].Gamma is not fl:
+                raise ValueError(f"{where}: Ion_flux must be built from the Flux of the ions' balance equations")
+            idx.add(i)
+        if members is not None and idx != members:
+            raise ValueError(f"{where}: all wall terms must sum Ion_flux over the same ions")
+        members = idx
+    for i in members or ():
+        is_ion[i] = True
+    return Walls(vth=vth, ref=ref, gamma=gamma, emits=emits, is_ion=is_ion)
+
+
 def compile_forms(F, quadrature_degree=None):
     """FormSum -> (device Model, mesh, facet tags).  The compiler of this façade: what
     FFC does for the reference, restricted to the model family of the device kernels."""
@@ -338,6 +415,7 @@ def compile_forms(F, quadrature_degree=None):
     bc_kind = [["zero flux"] * ns for _ in range(n_tags)]
     for b in bterms:
         bc_kind[b.tag - 1][b.u.index] = b.kind
+    walls = _lower_walls(bterms, balances, n_tags, mu, Z, bool(poissons))
     qd = quadrature_degree
     if qd is None:
         qd = forms.parameters["form_compiler"]["quadrature_degree"]
@@ -361,7 +439,7 @@ def compile_forms(F, quadrature_degree=None):
         extra["ext_source_degree"] = degrees
     model = Model(n_species=ns, poisson=bool(poissons), eq_type=eq_type, Z=Z, mu=mu, D=D,
                   reactions=reactions, bc_kind=bc_kind, quadrature_degree=int(qd),
-                  axisymmetric=axis, log_representation=log, **extra)
+                  axisymmetric=axis, log_representation=log, walls=walls, **extra)
     model.expression_sources = ext_sources
     return model, mesh, tags_mf
 

@@ -44,6 +44,7 @@ extern "C" {
 
 #define FEDM_BC_ZERO_FLUX 0                /* 'zero flux'                functions.py:472 */
 #define FEDM_BC_NEUMANN 1                  /* 'Neumann'                  functions.py:523 */
+#define FEDM_BC_FLUX_SOURCE 2              /* 'flux source'              functions.py:514 (fedm_ctx_create_walls) */
 
 #define FEDM_DIVERGED_MAX_IT 1
 #define FEDM_DIVERGED_NAN 2
@@ -92,6 +93,17 @@ typedef struct {
     int32_t linear_representation;
     int32_t pad2_;
 } fedm_model_desc;
+
+/* The walls of an LFA model: what Boundary_flux('flux source', ...) adds to fedm_model_desc for the entries of
+ * bc_kind that hold FEDM_BC_FLUX_SOURCE (fedm/functions.py:514-522, fedm-gd.py:346-351); handed to
+ * fedm_ctx_create_walls next to the model, which does not change. */
+typedef struct {
+    double vth[FEDM_MAX_TAGS][FEDM_MAX_SPECIES];   /* thermal velocity [m/s], >= 0                          */
+    double ref[FEDM_MAX_TAGS][FEDM_MAX_SPECIES];   /* reflection coefficient, 1 + ref != 0                  */
+    double gamma[FEDM_MAX_TAGS];                   /* secondary emission coefficient of the tag             */
+    int32_t emits[FEDM_MAX_SPECIES];               /* 1: receives the secondaries (particle_type 'electrons') */
+    int32_t is_ion[FEDM_MAX_SPECIES];              /* 1: summed into Ion_flux = sum max(Gamma_i . n, 0)     */
+} fedm_wall_desc;
 
 typedef struct {
     int32_t n_vertices;
@@ -227,7 +239,8 @@ const char *fedm_last_error(void);
  * 10: fedm_debug_gd_reduced_field, fedm_debug_get_ext_source; fedm_gd_prep_setup refuses what np.interp refuses (a
  *    looked-up table without entries, a tab_ptr that does not start at 0 or decreases, null table arrays, a program
  *    kind or argument outside its enum).  Additive under 10 (no struct changes size or offsets, no signature changes):
- *    fedm_ctx_create_tabulated; fedm_termsum.pad_, which had to be 0, is the table reference. */
+ *    fedm_ctx_create_tabulated; fedm_termsum.pad_, which had to be 0, is the table reference.  fedm_ctx_create_walls
+ *    with fedm_wall_desc; FEDM_BC_FLUX_SOURCE, a value of bc_kind that the two older creators refuse. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -251,6 +264,23 @@ int fedm_ctx_create(const fedm_mesh_desc *mesh, const fedm_model_desc *model, in
 int fedm_ctx_create_tabulated(const fedm_mesh_desc *mesh, const fedm_model_desc *model, int n_tables,
                               const int32_t *tab_ptr, const double *tab_x, const double *tab_y, int device,
                               fedm_ctx **out);
+/* fedm_ctx_create_tabulated for a model with 'flux source' walls: walls describes every (tag, species) whose bc_kind
+ * is FEDM_BC_FLUX_SOURCE (null: no walls; n_tables = 0: no tables).  On a facet of such a tag, species s adds
+ *   2 pi r v [ (1 - ref)/(1 + ref) (vth/2 + |Z mu(|E|) E.n|) n_s  -  2 gamma/(1 + ref) sum_(i: is_ion) max(Gamma_i.n, 0) ] ds
+ * to its row: the drift part for 'drift-diffusion-reaction' only, the emission part for a drift-diffusion species
+ * with emits, nothing for 'reaction'; Gamma_i.n = -D_i grad(n_i).n + Z_i mu_i E.n n_i.  The Jacobian is the exact
+ * derivative with d|x| = sign(x), sign(0) = 1, and max(x, 0) = (x + |x|)/2, as the LMEA kernels take them.
+ * With gamma != 0 the Jacobian planes (emitting species, ion) count as coupled (fedm_plane_masks).
+ * Refused (-2, nothing allocated, fedm_last_error names tag and species): ref not finite or 1 + ref == 0; vth
+ * negative or not finite; gamma not finite; a 'flux source' entry in a model without the Poisson equation (the facet
+ * kernels exist for models with one; there is no E); a 'flux source' drift-diffusion species with has_drift_w;
+ * gamma != 0 on a tag none of whose 'flux source' species has emits; a 'flux source' entry without walls, which is
+ * what fedm_ctx_create and fedm_ctx_create_tabulated -- this call without walls -- meet.  Wall models run the
+ * second-generation assembly (variants 1, 2 of fedm_pattern_info; 0 by global colouring), never the one-pass
+ * kernels. */
+int fedm_ctx_create_walls(const fedm_mesh_desc *mesh, const fedm_model_desc *model, const fedm_wall_desc *walls,
+                          int n_tables, const int32_t *tab_ptr, const double *tab_x, const double *tab_y, int device,
+                          fedm_ctx **out);
 int fedm_ctx_create_gd(const fedm_mesh_desc *mesh, const fedm_gd_desc *model, int device,
                        fedm_ctx **out);
 int fedm_gd_set_fields(fedm_ctx *ctx, const double *fields /* [n_fields][n_vertices] */);
