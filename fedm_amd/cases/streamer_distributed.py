@@ -26,11 +26,13 @@ class Runner(streamer.Stepper):
 
     def __init__(self, per_gpu_mesh, rank, world, local_rank, grading=4.0, transport="rccl",
                  group=None, n_per_gpu=None, global_n=None, distributed_multigrid=None, mesh=None,
-                 halo_depth=None, **kw):
+                 halo_depth=None, model=None, **kw):
         """Mesh: ``mesh`` (any triangle mesh of the box, e.g. `streamer.refined_mesh`) is the GLOBAL
         mesh, partitioned as it is; else ``global_n`` cells per side of the whole tensor-product mesh
         (strong scaling, e.g. BASELINE configs[4]), else ``n_per_gpu`` (or the size of
-        ``per_gpu_mesh``) cells per side PER GPU."""
+        ``per_gpu_mesh``) cells per side PER GPU.  ``model``: another LFA model of the same box and
+        boundary list (two species and the potential, which carries the electrodes' Dirichlet values)
+        instead of `streamer.model()`."""
         import torch.distributed as dist
         if mesh is not None:
             gmesh, n = mesh, 0
@@ -68,8 +70,10 @@ class Runner(streamer.Stepper):
         # boundary tags and Dirichlet rows from the global mesh, restricted to the local cells
         gtags = Marking_boundaries(gmesh, streamer.BOUNDARIES)
         tags = gtags[lm.cell_global]
+        model = streamer.model() if model is None else model
         ddofs, dvals = streamer.dirichlet(lm.coords)
-        prob = DeviceProblem(lm.coords, lm.cells, streamer.model(), facet_tags=tags,
+        ddofs = ((ddofs // 3) * model.n_eq + model.n_eq - 1).astype(np.int32)     # the potential of the model's n_eq
+        prob = DeviceProblem(lm.coords, lm.cells, model, facet_tags=tags,
                              dirichlet_dofs=ddofs, dirichlet_vals=dvals, device=local_rank,
                              n_owned=lm.n_owned, identity_vertices=lm.identity_vertices if halo_depth > 1 else None,
                              halo_depth=halo_depth)
@@ -127,7 +131,7 @@ class Runner(streamer.Stepper):
         super().__init__(prob, **kw)
         self.world_size = world
         self.transport = transport
-        self.total_dofs = gmesh.num_vertices() * 3
+        self.total_dofs = gmesh.num_vertices() * model.n_eq
         shape = f"{n}x{n}" if n else f"unstructured, {gmesh.num_vertices()} vertices"
         kind = ("multilevel graph partition (heavy-edge matching, FM refinement)" if self.partitioner == "graph"
                 else "RCB vertex partition (cuts severing the fewest edges)")

@@ -833,9 +833,8 @@ __global__ void dirichlet_kernel(int n_dir, const int *__restrict__ dofs,
     }
     const int dof = dofs[t];
     const int vtx = dof / neq, cr = dof % neq;
-    // a ghost's row (one layer: identity with F = 0, written above; deep halos: an assembled row whose
-    // Dirichlet condition applies as on its owner)
-    if (!id_list && n_id > 0 && vtx >= id_first) return;
+    // (n_dir counts the Dirichlet ROWS, Ctx::n_dir_rows: a dof of a vertex with identity rows is not among them;
+    // on an assembled ghost row of a deep halo the Dirichlet condition applies as on its owner)
     F[dof] = u[dof] - vals[t];
     if (!jacobian) return;
     const int slice = vtx >> 6, lane = vtx & 63;
@@ -929,10 +928,10 @@ void launch_finalize(Ctx &c, bool jacobian, int mode) {
         c.boundary_pending = 0;
         if (mode == 0 && jac == jacobian) {
             const int fb = (c.n_bfacets + 127) / 128, n_id = c.nvp - c.nv;
-            const int rb = (c.n_dir + n_id + 127) / 128;
+            const int rb = (c.n_dir_rows + n_id + 127) / 128;   // (no identity vertices here: n_dir_rows == n_dir)
 #define FEDM_BD_T(NS_, TAB_, WALL_)                                                                               \
     hipLaunchKernelGGL((boundary_dirichlet_kernel<NS_, TAB_, WALL_>), dim3(fb + rb), dim3(128), 0, c.stream, c.d_model, c.n_bfacets, fb, \
-                       c.d_bfacets, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0, c.n_dir, \
+                       c.d_bfacets, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0, c.n_dir_rows, \
                        c.d_dir_dofs, c.d_dir_vals, c.d_slice_boff, c.d_diag_slot, c.nv, n_id)
 #define FEDM_BD(NS_)                                                                                              \
     do {                                                                                                          \
@@ -964,10 +963,11 @@ void launch_finalize(Ctx &c, bool jacobian, int mode) {
                            c.d_diag_slot, jacobian ? 1 : 0);
         n_id = deep ? c.n_identity : 0;
     }
-    // (Dirichlet dofs of ghost vertices are left to the identity branch: the row sets are disjoint)
-    if (c.n_dir + n_id > 0)
-        hipLaunchKernelGGL(dirichlet_kernel, dim3((c.n_dir + n_id + 255) / 256), dim3(256), 0, c.stream,
-                           c.n_dir, c.d_dir_dofs, c.d_dir_vals, c.d_u, c.d_F, c.d_val,
+    // (Dirichlet dofs of vertices with identity rows -- one-layer ghosts, the listed layer of a deep halo -- stand
+    // behind the first n_dir_rows entries of the list and are left to the identity branch: the row sets are disjoint)
+    if (c.n_dir_rows + n_id > 0)
+        hipLaunchKernelGGL(dirichlet_kernel, dim3((c.n_dir_rows + n_id + 255) / 256), dim3(256), 0, c.stream,
+                           c.n_dir_rows, c.d_dir_dofs, c.d_dir_vals, c.d_u, c.d_F, c.d_val,
                            c.d_slice_boff, c.d_colidx, c.d_diag_slot, c.neq, jacobian ? 1 : 0,
                            deep ? c.nv : c.n_owned, n_id, c.d_identity, c.n_identity);
 }

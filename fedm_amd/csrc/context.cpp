@@ -677,9 +677,31 @@ static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *mo
     if (upload(c.d_slice_boff, c.pat.slice_boff.data(), c.pat.slice_boff.size())) return -1;
     if (upload(c.d_colidx, c.pat.colidx.data(), c.pat.colidx.size())) return -1;
     if (upload(c.d_diag_slot, c.pat.diag_slot.data(), c.pat.diag_slot.size())) return -1;
-    c.n_dir = mesh->n_dirichlet;
-    if (upload(c.d_dir_dofs, mesh->dirichlet_dofs, (size_t)c.n_dir)) return -1;
-    if (upload(c.d_dir_vals, mesh->dirichlet_vals, (size_t)c.n_dir)) return -1;
+    {
+        // A Dirichlet dof of a vertex with identity rows (a caller may list the Dirichlet dofs of every local vertex)
+        // goes behind the others: dirichlet_kernel writes rows for the first n_dir_rows entries only, so F = 0 and the
+        // unit row of the identity branch have one writer.
+        std::vector<char> identity_vertex((size_t)c.nv, 0);
+        if (c.d_identity)
+            for (int i = 0; i < c.n_identity; ++i) identity_vertex[mesh->identity_vertices[i]] = 1;
+        else
+            for (int v = c.n_owned; v < c.nv; ++v) identity_vertex[v] = 1;
+        c.n_dir = mesh->n_dirichlet;
+        c.dir_perm.clear();
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int k = 0; k < c.n_dir; ++k)
+                if ((identity_vertex[mesh->dirichlet_dofs[k] / c.neq] != 0) == (pass == 1)) c.dir_perm.push_back(k);
+            if (pass == 0) c.n_dir_rows = (int)c.dir_perm.size();
+        }
+        std::vector<int> dofs((size_t)c.n_dir);
+        std::vector<double> vals((size_t)c.n_dir);
+        for (int k = 0; k < c.n_dir; ++k) {
+            dofs[k] = mesh->dirichlet_dofs[c.dir_perm[k]];
+            vals[k] = mesh->dirichlet_vals[c.dir_perm[k]];
+        }
+        if (upload(c.d_dir_dofs, dofs.data(), (size_t)c.n_dir)) return -1;
+        if (upload(c.d_dir_vals, vals.data(), (size_t)c.n_dir)) return -1;
+    }
     const size_t nval = (size_t)c.pat.total_bc * SLICE * c.neq * c.neq;
     if (alloc_zero(c.d_val, nval, c.stream)) return -1;
     if (alloc_zero(c.d_dinv, (size_t)c.nvp * c.neq * c.neq, c.stream)) return -1;
@@ -843,8 +865,11 @@ int fedm_set_step(fedm_ctx *h, double dt, double dt_old) {
 int fedm_set_dirichlet_values(fedm_ctx *h, const double *vals) {
     Ctx &c = h->c;
     FEDM_HIP_CHECK(hipSetDevice(c.device));
-    if (c.n_dir)
-        FEDM_HIP_CHECK(hipMemcpy(c.d_dir_vals, vals, sizeof(double) * c.n_dir, hipMemcpyHostToDevice));
+    if (c.n_dir) {
+        std::vector<double> ordered((size_t)c.n_dir);   // the context's order (Ctx::dir_perm)
+        for (int k = 0; k < c.n_dir; ++k) ordered[k] = vals[c.dir_perm[k]];
+        FEDM_HIP_CHECK(hipMemcpy(c.d_dir_vals, ordered.data(), sizeof(double) * c.n_dir, hipMemcpyHostToDevice));
+    }
     return 0;
 }
 

@@ -180,10 +180,14 @@ struct Ctx {
     bool planes_fused = false, planes_fuse_ok = false, planes_last_fused = false;
     int *d_planes_rows = nullptr;
     int n_planes_rows = 0;
-    // Dirichlet
-    int n_dir = 0;
+    // Dirichlet.  The list is kept in two parts: [0, n_dir_rows) the dofs whose rows are Dirichlet rows, behind them
+    // the dofs of vertices with identity rows (the ghosts of a one-layer halo, the listed outermost layer of a deep
+    // one): their rows belong to the identity branch alone, their values still go into the state
+    // (launch_set_dirichlet_state).  dir_perm[k]: the caller's position of entry k (fedm_set_dirichlet_values).
+    int n_dir = 0, n_dir_rows = 0;
     int *d_dir_dofs = nullptr;
     double *d_dir_vals = nullptr;
+    std::vector<int> dir_perm;
     // vectors (np doubles each)
     double *d_u = nullptr, *d_uold = nullptr, *d_uold1 = nullptr, *d_F = nullptr;
     double *d_delta = nullptr, *d_w = nullptr, *d_rhs = nullptr, *d_tmp = nullptr, *d_fs = nullptr, *d_fs_g = nullptr;

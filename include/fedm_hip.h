@@ -111,7 +111,9 @@ typedef struct {
     const double *coords;        /* [n_vertices][2] = (r, z)                               */
     const int32_t *cells;        /* [n_cells][3]                                           */
     const int8_t *facet_tags;    /* [n_cells][3], facet i opposite vertex i; 0 = none      */
-    int32_t n_dirichlet;         /* DirichletBC rows, fedm-streamer.py:233                 */
+    int32_t n_dirichlet;         /* DirichletBC rows, fedm-streamer.py:233.  A dof of a ghost
+                                    vertex with identity rows (below) may be listed: its row
+                                    stays an identity row with F = 0                        */
     const int32_t *dirichlet_dofs;
     const double *dirichlet_vals;
     int32_t n_owned_vertices;    /* multi-GPU: vertices [0, n_owned) are owned, the rest are
