@@ -1,6 +1,7 @@
-// Volume and boundary assembly of the FEDM hot path (gfx950, fp64, no MFMA): the coloured, the LDS-patch and the
-// row-phase (lean2) element assembly into the sliced block-ELL Jacobian with the host decision between them and the
-// one-pass kernels of assemble3.hip (assembly_path), the Neumann boundary facets, and the Dirichlet / padding rows.
+// Volume assembly of the FEDM hot path (gfx950, fp64, no MFMA): the coloured, the LDS-patch and the row-phase (lean2)
+// element assembly into the sliced block-ELL Jacobian with the host decision between them and the one-pass kernels of
+// assemble3.hip (assembly_path).  What follows the volume kernel -- the boundary facets, the Dirichlet and identity
+// rows -- is boundary.hip.
 #include <cstdlib>
 
 #include "comm.hpp"
@@ -10,7 +11,6 @@
 #include "fedm_internal.hpp"
 
 namespace fedm {
-
 
 // The ghost entries of the state are refreshed lazily: the Newton loop only marks them stale
 // (Ctx::halo_pending) and the next assembly either overlaps the exchange with its interior
@@ -443,10 +443,18 @@ size_t patch_lds_bytes(const Ctx &c, bool jacobian) {
     return sizeof(double) * (acc + SLICE * neq + 2 * mv + (size_t)(neq + c.ns) * mv);
 }
 
+// ... of the row-phase kernels (assemble_lean2_body's arrays): one row of every block, the vertex exponentials besides,
+// and `n_stash` cell constants (LeanStash<NR>::N) for each of the workgroup's threads
+static size_t lean2_lds_bytes(const Ctx &c, bool jacobian, int n_stash, int threads) {
+    const int neq = c.neq, mv = c.pat.max_patch_verts;
+    const size_t acc_row = jacobian ? (size_t)c.pat.max_patch_width * neq * SLICE : 0;
+    return sizeof(double) * (acc_row + SLICE * neq + 2 * mv + (size_t)(neq + 2 * c.ns) * mv + (size_t)n_stash * threads);
+}
+
 // LDS patch assembly can run on this mesh and model at all (else the global colouring: context creation and
 // fedm_set_assembly): 8-bit local indices, the generic kernel's LDS within a workgroup's 160 KiB, the LFA family.
 bool patch_assembly_available(const Ctx &c) {
-    return c.pat.patch_ok && patch_lds_bytes(c) <= 160 * 1024 && c.model_kind != 1;
+    return c.pat.patch_ok && patch_lds_bytes(c) <= WORKGROUP_LDS_BYTES && c.model_kind != 1;
 }
 
 // FIAT's degree-2 rule (points (1/6,1/6), (1/6,2/3), (2/3,1/6), weights 1/6): the kernels take it as constants
@@ -495,185 +503,86 @@ static AssemblyPath assembly_path_upto(const Ctx &c, bool jacobian, int mode, in
 
 AssemblyPath assembly_path(const Ctx &c, bool jacobian, int mode) { return assembly_path_upto(c, jacobian, mode, 3); }
 
+// The generic patch kernel at T threads a workgroup, Jacobian or residual-only: every slice
+template <int NS, bool PO, int NR, int CACHE, int T, bool LIN, bool TAB>
+static void launch_patch(Ctx &c, bool jacobian, const StepCoef &sc, int mode) {
+    constexpr int NEQ = NS + (PO ? 1 : 0);
+    const int acc_doubles = jacobian ? c.pat.max_patch_width * NEQ * NEQ * SLICE : 0;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(c.pat.n_slices), dim3(T), patch_lds_bytes(c, jacobian), c.stream, c.d_model,
+                           c.nv, c.d_slice_boff, c.d_patch_cell_ptr, c.d_patch_cells, c.d_patch_halo_ptr, c.d_patch_halo,
+                           c.d_coords, c.d_u, c.d_uold, c.d_uold1, sc, c.d_ext[0], c.d_ext[1], c.d_ext[2], c.d_ext[3],
+                           c.d_val, c.d_F, mode, acc_doubles, c.pat.max_patch_verts);
+    };
+    if (jacobian) launch(assemble_patch_kernel<NS, PO, NR, CACHE, T, LIN, TAB>);
+    else launch(residual_patch_kernel<NS, PO, NR, CACHE, T, LIN, TAB>);
+    note_assembly_launch(c, jacobian, 1, T, c.pat.n_slices);
+}
+
+// The row-phase kernel at T threads a workgroup: the n patches of `list` (null: the first n slices)
+template <int NS, int NR, int T, bool TAB>
+static void launch_lean2(Ctx &c, bool jacobian, const StepCoef &sc, int mode, uint32_t cmask, const int *list, int n) {
+    if (n <= 0) return;
+    const int acc_row = jacobian ? c.pat.max_patch_width * (NS + 1) * SLICE : 0;
+    const size_t lds_bytes = lean2_lds_bytes(c, jacobian, LeanStash<NR>::N, T);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(n), dim3(T), lds_bytes, c.stream, c.d_model, c.nv, c.d_slice_boff,
+                           c.d_patch_cell_ptr, c.d_patch_cells, c.d_patch_halo_ptr, c.d_patch_halo, c.d_coords, c.d_u,
+                           c.d_uold, c.d_uold1, sc, c.d_ext[0], c.d_ext[1], c.d_ext[2], c.d_ext[3], c.d_val, c.d_F, mode,
+                           acc_row, c.pat.max_patch_verts, c.xcd_remap ? 1 : 0, list, cmask);
+    };
+    if (jacobian) launch(assemble_lean2_kernel<NS, NR, T, TAB>);
+    else launch(residual_lean2_kernel<NS, NR, T, TAB>);
+    note_assembly_launch(c, jacobian, 2, T, n);
+}
+
 template <int NS, bool PO, int NR, int CACHE, bool LIN, bool TAB>
 static void assemble_patch_t(Ctx &c, bool jacobian, int mode) {
-    constexpr int NEQ = NS + (PO ? 1 : 0);
     const StepCoef sc = step_coef(c.dt, c.dt_old);
-    const int acc_doubles = jacobian ? c.pat.max_patch_width * NEQ * NEQ * SLICE : 0;
     const AssemblyPath path = assembly_path(c, jacobian, mode);
     // The single case where "launched" may differ from "predicted": a third-generation launch that fails although it
     // was chosen (its plan not uploaded).  The assembly then takes what the decision gives without that generation:
-    // the second one only where that takes every cell; otherwise `done` turns false and the generic kernel assembles
-    // the whole mesh.
+    // the second one only where that takes every cell; otherwise the generic kernel assembles the whole mesh.
     const AssemblyPath fallback = path.variant == 3 ? assembly_path_upto(c, jacobian, mode, 2) : path;
-#define FEDM_PATCH_LAUNCH(KERNEL, T)                                                              \
-    hipLaunchKernelGGL((KERNEL<NS, PO, NR, CACHE, T, LIN, TAB>), dim3(c.pat.n_slices), dim3(T),         \
-                       patch_lds_bytes(c, jacobian), c.stream, c.d_model, c.nv, c.d_slice_boff,    \
-                       c.d_patch_cell_ptr, c.d_patch_cells, c.d_patch_halo_ptr, c.d_patch_halo,    \
-                       c.d_coords, c.d_u, c.d_uold, c.d_uold1, sc, c.d_ext[0], c.d_ext[1],         \
-                       c.d_ext[2], c.d_ext[3], c.d_val, c.d_F, mode, acc_doubles,                  \
-                       c.pat.max_patch_verts)
     // (the condition is the model predicate's, at compile time: it only keeps the lean kernels from being instantiated
     // for models they do not exist for)
     if constexpr (PO && CACHE == 2 && NS >= 1 && !LIN) {
         if (path.variant >= 2) {
-            const uint32_t cmask = path.cmask;
-            const bool gen3 = path.variant == 3, gen2 = fallback.variant == 2;
-            const int T = fallback.threads;   // of the second generation (unused where it does not take this mesh)
-            const int acc_row = jacobian ? c.pat.max_patch_width * NEQ * SLICE : 0;
-            const size_t lds_bytes = sizeof(double) * ((size_t)acc_row + SLICE * NEQ + 2 * c.pat.max_patch_verts +
-                                                       (size_t)(NEQ + 2 * NS) * c.pat.max_patch_verts +
-                                                       (size_t)LeanStash<NR>::N * T);
-#define FEDM_LEAN2_LAUNCH_T(KERNEL, LIST, N, TT)                                                            \
-    do {                                                                                                    \
-        hipLaunchKernelGGL((KERNEL<NS, NR, TT, TAB>), dim3(N), dim3(TT), lds_bytes, c.stream, c.d_model,         \
-                           c.nv, c.d_slice_boff, c.d_patch_cell_ptr, c.d_patch_cells, c.d_patch_halo_ptr,   \
-                           c.d_patch_halo, c.d_coords, c.d_u, c.d_uold, c.d_uold1, sc, c.d_ext[0],          \
-                           c.d_ext[1], c.d_ext[2], c.d_ext[3], c.d_val, c.d_F, mode, acc_row,               \
-                           c.pat.max_patch_verts, c.xcd_remap ? 1 : 0, LIST, cmask);                        \
-        note_assembly_launch(c, jacobian, 2, TT, N);                                                        \
-    } while (0)
-#define FEDM_LEAN2_LAUNCH(KERNEL, LIST, N)                                                                  \
-    do {                                                                                                    \
-        if (T == 192) FEDM_LEAN2_LAUNCH_T(KERNEL, LIST, N, 192);                                            \
-        else FEDM_LEAN2_LAUNCH_T(KERNEL, LIST, N, 256);                                                     \
-    } while (0)
-#define FEDM_LEAN2_BOTH(LIST, N)                                                                            \
-    do {                                                                                                    \
-        if ((N) <= 0) break;                                                                                \
-        if (jacobian) {                                                                              \
-            FEDM_LEAN2_LAUNCH(assemble_lean2_kernel, LIST, N);                                              \
-        } else {                                                                                            \
-            FEDM_LEAN2_LAUNCH(residual_lean2_kernel, LIST, N);                                              \
-        }                                                                                                   \
-    } while (0)
-            // third generation (assemble3.hip: one pass over the cells, compile-time plane mask) where it is
-            // instantiated; FEDM_ASSEMBLY_LEAN=2 keeps the row-phase kernels below.  (a failed launch: `fallback`)
-            bool done = true;
-#define FEDM_LEAN3_OR_LEAN2(LIST, N)                                                                        \
-    do {                                                                                                    \
-        if (gen3 && launch_assemble_lean3(c, jacobian, LIST, N, cmask)) break;                              \
-        if (gen2) FEDM_LEAN2_BOTH(LIST, N);                                                                 \
-        else done = false;                                                                                  \
-    } while (0)
+            // The patches of `list` (null: all n slices): the third generation (assemble3.hip) where it was chosen and
+            // its launch succeeds, else the second (FEDM_ASSEMBLY_LEAN=2 keeps it) where that takes every cell; false: neither
+            auto lean_launch = [&](const int *list, int n) {
+                if (path.variant == 3 && launch_assemble_lean3(c, jacobian, list, n, path.cmask)) return true;
+                if (fallback.variant != 2) return false;
+                if (fallback.threads == 192) launch_lean2<NS, NR, 192, TAB>(c, jacobian, sc, mode, path.cmask, list, n);
+                else launch_lean2<NS, NR, 256, TAB>(c, jacobian, sc, mode, path.cmask, list, n);
+                return true;
+            };
+            bool done;
             if (c.halo_pending && c.comm && c.comm->d_patch_interior) {
-                // the ghost values of the new state travel on the communication stream while the
-                // patches that stage no ghost vertex are assembled (north_star: "ghost exchange
-                // overlapped with interior assembly"); the patches that do follow the exchange
+                // the ghost values of the new state travel on the communication stream while the patches that stage no
+                // ghost vertex are assembled ("ghost exchange overlapped with interior assembly"); the others follow it
                 Comm &cm = *c.comm;
                 comm_halo_begin(c);
-                FEDM_LEAN3_OR_LEAN2(cm.d_patch_interior, cm.n_patch_interior);
+                done = lean_launch(cm.d_patch_interior, cm.n_patch_interior);
                 comm_halo_exchange(c, c.d_u);
-                if (done) FEDM_LEAN3_OR_LEAN2(cm.d_patch_boundary, cm.n_patch_boundary);
+                if (done) done = lean_launch(cm.d_patch_boundary, cm.n_patch_boundary);
                 c.halo_pending = false;
             } else {
                 flush_pending_halo(c);
-                FEDM_LEAN3_OR_LEAN2((const int *)nullptr, c.pat.n_slices);
+                done = lean_launch(nullptr, c.pat.n_slices);
             }
-#undef FEDM_LEAN3_OR_LEAN2
-#undef FEDM_LEAN2_BOTH
-#undef FEDM_LEAN2_LAUNCH
-#undef FEDM_LEAN2_LAUNCH_T
             if (done) {
                 if (jacobian) c.const_planes_valid = true;
                 return;
             }
         }
     }
+    // the generic kernel, for the whole mesh (variant 1: the decision's threads, or what is left of it)
     flush_pending_halo(c);
-    const int T = fallback.threads;   // (variant 1 here: the decision's, or what is left of it)
-    if (jacobian) {
-        if (T == 192) FEDM_PATCH_LAUNCH(assemble_patch_kernel, 192);
-        else FEDM_PATCH_LAUNCH(assemble_patch_kernel, 320);
-    } else {
-        if (T == 192) FEDM_PATCH_LAUNCH(residual_patch_kernel, 192);
-        else FEDM_PATCH_LAUNCH(residual_patch_kernel, 320);
-    }
-#undef FEDM_PATCH_LAUNCH
-    note_assembly_launch(c, jacobian, 1, T, c.pat.n_slices);
+    if (fallback.threads == 192) launch_patch<NS, PO, NR, CACHE, 192, LIN, TAB>(c, jacobian, sc, mode);
+    else launch_patch<NS, PO, NR, CACHE, 320, LIN, TAB>(c, jacobian, sc, mode);
     // every plane written, the constant ones included (the lean kernels may keep them from here on)
     if (jacobian && mode == 0) c.const_planes_valid = true;
-}
-
-// =============================================================================================
-// Neumann boundary facets (fedm/functions.py:523-524): one thread per tagged facet, one launch
-// per facet colour (facets of a colour share no vertex), plain adds on top of the volume
-// assembly -> fixed summation order.
-// =============================================================================================
-// SPECIES_COLS: the species columns only (the segregated step's species assembly: the planes of the potential column
-// are not touched)
-// WALL: the 'flux source' wall terms besides (element.hpp, wall_facet; Ctx::model_walls)
-template <int NS, bool ATOMIC, bool SPECIES_COLS = false, bool TAB = false, bool WALL = false>
-__global__ void boundary_kernel(const fedm_model_desc *__restrict__ md, int n_facets,
-                                const int *__restrict__ facets /* [n][3] = cell, local facet, tag */,
-                                const int *__restrict__ cells, const double *__restrict__ coords,
-                                const uint32_t *__restrict__ cell_slots,
-                                const double *__restrict__ u, double *__restrict__ val,
-                                double *__restrict__ F, int jacobian) {
-    constexpr int NEQ = NS + 1, NEQ2 = NEQ * NEQ;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_facets) return;
-    const int c = facets[3 * t], fi = facets[3 * t + 1], tag = facets[3 * t + 2];
-    int v[3];
-    double x[3][2], Uc[3][NEQ];
-    for (int a = 0; a < 3; ++a) {
-        v[a] = cells[3 * c + a];
-        x[a][0] = coords[2 * v[a]];
-        x[a][1] = coords[2 * v[a] + 1];
-        for (int s = 0; s < NEQ; ++s) Uc[a][s] = u[(size_t)v[a] * NEQ + s];
-    }
-    auto addR = [&](int a, int s, double value) {
-        double *p = &F[(size_t)v[a] * NEQ + s];
-        if (ATOMIC) unsafeAtomicAdd(p, value);
-        else *p += value;
-    };
-    auto addJ = [&](int a, int b, int sr, int scol, double value) {
-        if (SPECIES_COLS && scol == NEQ - 1) return;
-        const uint32_t slot = cell_slots[(size_t)c * 9 + a * 3 + b];
-        double *p = &val[((size_t)(slot >> 6) * NEQ2 + sr * NEQ + scol) * SLICE + (slot & 63)];
-        if (ATOMIC) unsafeAtomicAdd(p, value);
-        else *p += value;
-    };
-    boundary_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
-}
-
-template <bool ATOMIC>
-static void launch_boundary_range(Ctx &c, bool jacobian, int f0, int n) {
-    const dim3 g((n + 127) / 128), b(128);
-    const int *fl = c.d_bfacets + 3 * f0;
-#define FEDM_BK(NS_, TAB_, WALL_)                                                                                   \
-    hipLaunchKernelGGL((boundary_kernel<NS_, ATOMIC, false, TAB_, WALL_>), g, b, 0, c.stream, c.d_model, n, fl,      \
-                       c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0)
-#define FEDM_BK_CASE(NS_)                                                                                           \
-    case NS_:                                                                                                       \
-        if (c.model_walls && c.model_tables) FEDM_BK(NS_, true, true);                                              \
-        else if (c.model_walls) FEDM_BK(NS_, false, true);                                                          \
-        else if (c.model_tables) FEDM_BK(NS_, true, false);                                                         \
-        else FEDM_BK(NS_, false, false);                                                                            \
-        break;
-    switch (c.ns) {
-        FEDM_BK_CASE(1)
-        FEDM_BK_CASE(2)
-        FEDM_BK_CASE(3)
-        FEDM_BK_CASE(4)
-    }
-#undef FEDM_BK_CASE
-#undef FEDM_BK
-}
-
-static void launch_boundary(Ctx &c, bool jacobian) {
-    if (!c.poisson || c.n_bfacets == 0) return;
-    if (c.assembly_kind == 1) {
-        // the patch assembly already sums in a run-dependent order (LDS atomics): all facets in
-        // one launch with fp64 atomics instead of one launch per colour
-        launch_boundary_range<true>(c, jacobian, 0, c.n_bfacets);
-        return;
-    }
-    const int ncol = (int)c.bfacet_colour_ptr.size() - 1;
-    for (int k = 0; k < ncol; ++k) {
-        const int f0 = c.bfacet_colour_ptr[k], n = c.bfacet_colour_ptr[k + 1] - f0;
-        if (n > 0) launch_boundary_range<false>(c, jacobian, f0, n);
-    }
 }
 
 template <int NS, bool PO, int NR, int CACHE, bool LIN, bool TAB>
@@ -771,11 +680,7 @@ bool launch_assemble_species(Ctx &c, bool jacobian, bool volume_only) {
     if (one_pass && volume_only) return true;
     if (one_pass) {
         c.boundary_pending = 0;
-        if (c.n_bfacets > 0) {
-            const dim3 g((c.n_bfacets + 127) / 128), b(128);
-            hipLaunchKernelGGL((boundary_kernel<2, true, true>), g, b, 0, c.stream, c.d_model, c.n_bfacets, c.d_bfacets,
-                               c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0);
-        }
+        launch_boundary_species_cols(c, jacobian);
     } else {
         launch_assemble(c, jacobian, 0);
         if (volume_only) return false;
@@ -783,205 +688,6 @@ bool launch_assemble_species(Ctx &c, bool jacobian, bool volume_only) {
     launch_finalize(c, jacobian, 0);
     launch_pick_entries(c, 0, 1.0, c.d_F, c.d_F);   // (in place: the kernel's pointers are not restrict-qualified)
     return one_pass;
-}
-
-// =============================================================================================
-// Dirichlet rows (bc.apply(b, x): b_i = x_i - g_i; bc.apply(A): identity row), padding
-// vertices and -- in Poisson-only mode -- frozen species rows.
-// =============================================================================================
-__device__ __forceinline__ void identity_row(double *val, const int *boff, const int *colidx,
-                                             int neq, int vtx, int cr) {
-    const int slice = vtx >> 6, lane = vtx & 63;
-    const int neq2 = neq * neq;
-    for (int bc = boff[slice]; bc < boff[slice + 1]; ++bc) {
-        const int col = colidx[(size_t)bc * SLICE + lane];
-        for (int cc = 0; cc < neq; ++cc)
-            val[((size_t)bc * neq2 + cr * neq + cc) * SLICE + lane] = (col == vtx && cc == cr) ? 1.0 : 0.0;
-    }
-    // padded duplicates of the diagonal column (col == vtx beyond row_len) must stay zero:
-    // they are only ever produced for j >= row_len where the first match already got the 1.
-}
-
-// Dirichlet rows (F = u - value, unit row) and, in the same launch when no species is frozen, the
-// identity rows of the vertices [n_owned, nvp) (ghosts and padding): one kernel boundary less per
-// assembly.  n_id = 0: Dirichlet rows only.
-__global__ void dirichlet_kernel(int n_dir, const int *__restrict__ dofs,
-                                 const double *__restrict__ vals, const double *__restrict__ u,
-                                 double *__restrict__ F, double *__restrict__ val,
-                                 const int *__restrict__ boff, const int *__restrict__ colidx,
-                                 const uint32_t *__restrict__ diag_slot, int neq, int jacobian,
-                                 int id_first, int n_id, const int *__restrict__ id_list, int n_list) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int neq2 = neq * neq;
-    if (t >= n_dir) {
-        if (t - n_dir >= n_id) return;
-        // identity rows: the range [id_first, ...) or, with deep halos, the listed ghost vertices (the
-        // outermost layer) followed by the padding range
-        const int k = t - n_dir;
-        const int vtx = id_list ? (k < n_list ? id_list[k] : id_first + (k - n_list)) : id_first + k;
-        const int slice = vtx >> 6, lane = vtx & 63;
-        for (int cr = 0; cr < neq; ++cr) {
-            F[(size_t)vtx * neq + cr] = 0.0;
-            if (!jacobian) continue;
-            for (int bc = boff[slice]; bc < boff[slice + 1]; ++bc)
-                for (int cc = 0; cc < neq; ++cc)
-                    val[((size_t)bc * neq2 + cr * neq + cc) * SLICE + lane] = 0.0;
-            const uint32_t ds = diag_slot[vtx];
-            val[((size_t)(ds >> 6) * neq2 + cr * neq + cr) * SLICE + (ds & 63)] = 1.0;
-        }
-        return;
-    }
-    const int dof = dofs[t];
-    const int vtx = dof / neq, cr = dof % neq;
-    // (n_dir counts the Dirichlet ROWS, Ctx::n_dir_rows: a dof of a vertex with identity rows is not among them;
-    // on an assembled ghost row of a deep halo the Dirichlet condition applies as on its owner)
-    F[dof] = u[dof] - vals[t];
-    if (!jacobian) return;
-    const int slice = vtx >> 6, lane = vtx & 63;
-    for (int bc = boff[slice]; bc < boff[slice + 1]; ++bc)
-        for (int cc = 0; cc < neq; ++cc)
-            val[((size_t)bc * neq2 + cr * neq + cc) * SLICE + lane] = 0.0;
-    const uint32_t ds = diag_slot[vtx];
-    val[((size_t)(ds >> 6) * neq2 + cr * neq + cr) * SLICE + (ds & 63)] = 1.0;
-}
-
-// rows that are identity by construction: padding vertices (all components) and, in
-// Poisson-only mode, every species component of every vertex
-__global__ void identity_rows_kernel(int nv, int nvp, int neq, int ns_frozen,
-                                     double *__restrict__ F, double *__restrict__ val,
-                                     const int *__restrict__ boff,
-                                     const uint32_t *__restrict__ diag_slot, int jacobian) {
-    const int vtx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (vtx >= nvp) return;
-    const int neq2 = neq * neq;
-    const int slice = vtx >> 6, lane = vtx & 63;
-    const int n_rows = (vtx >= nv) ? neq : ns_frozen;
-    for (int cr = 0; cr < n_rows; ++cr) {
-        F[(size_t)vtx * neq + cr] = 0.0;
-        if (!jacobian) continue;
-        for (int bc = boff[slice]; bc < boff[slice + 1]; ++bc)
-            for (int cc = 0; cc < neq; ++cc)
-                val[((size_t)bc * neq2 + cr * neq + cc) * SLICE + lane] = 0.0;
-        const uint32_t ds = diag_slot[vtx];
-        val[((size_t)(ds >> 6) * neq2 + cr * neq + cr) * SLICE + (ds & 63)] = 1.0;
-    }
-}
-
-// boundary_kernel<NS, true> and dirichlet_kernel in one launch (128-thread blocks: the first ones take the facets, the
-// rest the Dirichlet and padding rows) -- allowed when no row belongs to both (Ctx::boundary_rows_disjoint)
-template <int NS, bool TAB, bool WALL = false>
-__global__ __launch_bounds__(128) void boundary_dirichlet_kernel(
-    const fedm_model_desc *__restrict__ md, int n_facets, int facet_blocks, const int *__restrict__ facets,
-    const int *__restrict__ cells, const double *__restrict__ coords, const uint32_t *__restrict__ cell_slots,
-    const double *__restrict__ u, double *__restrict__ val, double *__restrict__ F, int jacobian, int n_dir,
-    const int *__restrict__ dofs, const double *__restrict__ vals, const int *__restrict__ boff,
-    const uint32_t *__restrict__ diag_slot, int id_first, int n_id) {
-    constexpr int NEQ = NS + 1, NEQ2 = NEQ * NEQ;
-    if ((int)blockIdx.x < facet_blocks) {
-        const int t = blockIdx.x * blockDim.x + threadIdx.x;
-        if (t >= n_facets) return;
-        const int c = facets[3 * t], fi = facets[3 * t + 1], tag = facets[3 * t + 2];
-        int v[3];
-        double x[3][2], Uc[3][NEQ];
-        for (int a = 0; a < 3; ++a) {
-            v[a] = cells[3 * c + a];
-            x[a][0] = coords[2 * v[a]];
-            x[a][1] = coords[2 * v[a] + 1];
-            for (int s = 0; s < NEQ; ++s) Uc[a][s] = u[(size_t)v[a] * NEQ + s];
-        }
-        auto addR = [&](int a, int s, double value) { unsafeAtomicAdd(&F[(size_t)v[a] * NEQ + s], value); };
-        auto addJ = [&](int a, int b, int sr, int scol, double value) {
-            const uint32_t slot = cell_slots[(size_t)c * 9 + a * 3 + b];
-            unsafeAtomicAdd(&val[((size_t)(slot >> 6) * NEQ2 + sr * NEQ + scol) * SLICE + (slot & 63)], value);
-        };
-        boundary_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
-        return;
-    }
-    // the rows of dirichlet_kernel (one GPU: Dirichlet dofs, then the padding vertices [id_first, id_first + n_id))
-    const int t = ((int)blockIdx.x - facet_blocks) * blockDim.x + threadIdx.x;
-    if (t >= n_dir + n_id) return;
-    if (t >= n_dir) {
-        const int vtx = id_first + (t - n_dir), slice = vtx >> 6, lane = vtx & 63;
-        for (int cr = 0; cr < NEQ; ++cr) {
-            F[(size_t)vtx * NEQ + cr] = 0.0;
-            if (!jacobian) continue;
-            for (int bc = boff[slice]; bc < boff[slice + 1]; ++bc)
-                for (int cc = 0; cc < NEQ; ++cc) val[((size_t)bc * NEQ2 + cr * NEQ + cc) * SLICE + lane] = 0.0;
-            const uint32_t ds = diag_slot[vtx];
-            val[((size_t)(ds >> 6) * NEQ2 + cr * NEQ + cr) * SLICE + (ds & 63)] = 1.0;
-        }
-        return;
-    }
-    const int dof = dofs[t], vtx = dof / NEQ, cr = dof % NEQ;
-    F[dof] = u[dof] - vals[t];
-    if (!jacobian) return;
-    const int slice = vtx >> 6, lane = vtx & 63;
-    for (int bc = boff[slice]; bc < boff[slice + 1]; ++bc)
-        for (int cc = 0; cc < NEQ; ++cc) val[((size_t)bc * NEQ2 + cr * NEQ + cc) * SLICE + lane] = 0.0;
-    const uint32_t ds = diag_slot[vtx];
-    val[((size_t)(ds >> 6) * NEQ2 + cr * NEQ + cr) * SLICE + (ds & 63)] = 1.0;
-}
-
-void launch_finalize(Ctx &c, bool jacobian, int mode) {
-    if (c.boundary_pending) {
-        const bool jac = c.boundary_pending == 2;
-        c.boundary_pending = 0;
-        if (mode == 0 && jac == jacobian) {
-            const int fb = (c.n_bfacets + 127) / 128, n_id = c.nvp - c.nv;
-            const int rb = (c.n_dir_rows + n_id + 127) / 128;   // (no identity vertices here: n_dir_rows == n_dir)
-#define FEDM_BD_T(NS_, TAB_, WALL_)                                                                               \
-    hipLaunchKernelGGL((boundary_dirichlet_kernel<NS_, TAB_, WALL_>), dim3(fb + rb), dim3(128), 0, c.stream, c.d_model, c.n_bfacets, fb, \
-                       c.d_bfacets, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0, c.n_dir_rows, \
-                       c.d_dir_dofs, c.d_dir_vals, c.d_slice_boff, c.d_diag_slot, c.nv, n_id)
-#define FEDM_BD(NS_)                                                                                              \
-    do {                                                                                                          \
-        if (c.model_walls && c.model_tables) FEDM_BD_T(NS_, true, true);                                          \
-        else if (c.model_walls) FEDM_BD_T(NS_, false, true);                                                      \
-        else if (c.model_tables) FEDM_BD_T(NS_, true, false);                                                     \
-        else FEDM_BD_T(NS_, false, false);                                                                        \
-    } while (0)
-            if (c.ns == 1) FEDM_BD(1);
-            else if (c.ns == 2) FEDM_BD(2);
-            else if (c.ns == 3) FEDM_BD(3);
-            else FEDM_BD(4);
-#undef FEDM_BD
-#undef FEDM_BD_T
-            return;
-        }
-        launch_boundary(c, jac);   // (not the pair this was deferred for: the facets first, then the rows as usual)
-    }
-    const int ns_frozen = (mode == 1) ? c.ns : 0;
-    const bool deep = c.d_identity != nullptr;
-    // identity rows: padding + ghost vertices (deep halos: padding + the listed outermost ghost layer)
-    int n_id = deep ? c.n_identity + (c.nvp - c.nv) : c.nvp - c.n_owned;
-    if (ns_frozen > 0) {           // frozen species: every vertex has identity rows
-        // (vertices beyond the first argument: all rows -- the ghosts of a one-layer halo and the padding;
-        // deep halos: the padding only, the inner ghost layers keep their potential rows and the
-        // outermost layer is listed)
-        hipLaunchKernelGGL(identity_rows_kernel, dim3((c.nvp + 255) / 256), dim3(256), 0, c.stream,
-                           deep ? c.nv : c.n_owned, c.nvp, c.neq, ns_frozen, c.d_F, c.d_val, c.d_slice_boff,
-                           c.d_diag_slot, jacobian ? 1 : 0);
-        n_id = deep ? c.n_identity : 0;
-    }
-    // (Dirichlet dofs of vertices with identity rows -- one-layer ghosts, the listed layer of a deep halo -- stand
-    // behind the first n_dir_rows entries of the list and are left to the identity branch: the row sets are disjoint)
-    if (c.n_dir_rows + n_id > 0)
-        hipLaunchKernelGGL(dirichlet_kernel, dim3((c.n_dir_rows + n_id + 255) / 256), dim3(256), 0, c.stream,
-                           c.n_dir_rows, c.d_dir_dofs, c.d_dir_vals, c.d_u, c.d_F, c.d_val,
-                           c.d_slice_boff, c.d_colidx, c.d_diag_slot, c.neq, jacobian ? 1 : 0,
-                           deep ? c.nv : c.n_owned, n_id, c.d_identity, c.n_identity);
-}
-
-__global__ void set_dirichlet_state_kernel(int n_dir, const int *__restrict__ dofs,
-                                           const double *__restrict__ vals, double *__restrict__ u) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n_dir) u[dofs[t]] = vals[t];
-}
-
-void launch_set_dirichlet_state(Ctx &c) {
-    if (c.n_dir > 0)
-        hipLaunchKernelGGL(set_dirichlet_state_kernel, dim3((c.n_dir + 255) / 256), dim3(256), 0,
-                           c.stream, c.n_dir, c.d_dir_dofs, c.d_dir_vals, c.d_u);
 }
 
 }  // namespace fedm

@@ -1146,7 +1146,7 @@ static Lean3Classes *lean3_classes(Ctx &c, int n_live_planes) {
         return !(e && e[0] == '1');
     }();
     const Pattern &pat = c.pat;
-    const size_t budget = 160 * 1024 / 4;
+    const size_t budget = WORKGROUP_LDS_BYTES / 4;
     std::vector<int> lists[2];
     for (int S = 0; S < pat.n_slices; ++S) {
         const int w = pat.slice_boff[S + 1] - pat.slice_boff[S];
@@ -1255,7 +1255,7 @@ static bool lean3_launch_one(Ctx &c, bool jacobian, const int *list, int n, int 
     p.planes_upper = 0;
     p.planes_zs = 0u;
     const size_t lds = lean3_lds_bytes(c.neq, c.ns, width, verts, PL::N, jacobian);
-    if (lds > 160 * 1024) return false;
+    if (lds > WORKGROUP_LDS_BYTES) return false;
     constexpr int T = 192;
     p.n_patches = n;
     // one workgroup per patch (default) or the persistent, software-pipelined kernels (FEDM_LEAN3_PERSISTENT=1:
@@ -1382,7 +1382,7 @@ static int lean3_live_planes(uint32_t cmask) {
 // planes) the answer can be no where it is yes for the later ones (the potential plane kept).
 bool lean3_fits(const Ctx &c, bool jacobian, uint32_t cmask) {
     const int planes = jacobian ? lean3_live_planes(cmask) : 0;
-    return lean3_lds_bytes(c.neq, c.ns, c.pat.max_patch_width, c.pat.max_patch_verts, planes, jacobian) <= 160 * 1024;
+    return lean3_lds_bytes(c.neq, c.ns, c.pat.max_patch_width, c.pat.max_patch_verts, planes, jacobian) <= WORKGROUP_LDS_BYTES;
 }
 
 // The species-only assembly of the whole mesh in one launch (one GPU).  The planes it does not write stay as they are
@@ -1422,7 +1422,7 @@ static bool lean3_launch_species(Ctx &c, bool jacobian) {
     p.planes_upper = 0;
     p.planes_zs = 0u;
     const size_t lds = lean3_lds_bytes(c.neq, c.ns, width, verts, PL::N, jacobian);
-    if (lds > 160 * 1024) return false;
+    if (lds > WORKGROUP_LDS_BYTES) return false;
     if (jacobian) {
         grant_dynamic_lds(&assemble_lean3s_kernel<NS, NR, T, CMASK, SIG>, c.device, lds);
         lean3_dispatch(c, true, assemble_lean3s_kernel<NS, NR, T, CMASK, SIG>, n, T, lds, plan, p);

@@ -13,6 +13,7 @@
 namespace fedm {
 
 constexpr int SLICE = 64;  // vertices per matrix slice = one wavefront
+constexpr size_t WORKGROUP_LDS_BYTES = 160 * 1024;  // the LDS one workgroup may have (gfx950: a CU's 160 KiB)
 
 // Sliced block-ELL pattern of the P1 vertex graph (host copy).
 //   slice S holds vertices [64 S, 64 S + 64); its rows are padded to the widest row of
@@ -390,7 +391,12 @@ struct AssemblyPath {
 AssemblyPath assembly_path(const Ctx &c, bool jacobian, int mode);
 bool patch_assembly_available(const Ctx &c);   // LDS patches possible on this mesh and model (else the global colouring)
 size_t patch_lds_bytes(const Ctx &c, bool jacobian = true);
-void launch_finalize(Ctx &c, bool jacobian, int mode);          // Dirichlet + padding rows
+// ---- boundary.hip: what follows the volume kernel ---------------------------------------------
+void launch_boundary(Ctx &c, bool jacobian);                    // the Neumann / wall facets, as launches of their own
+// ... into the species columns only, behind the species-only one-pass kernel (two species, no tables, no walls)
+void launch_boundary_species_cols(Ctx &c, bool jacobian);
+// Dirichlet + identity rows; with Ctx::boundary_pending the facets launch_assemble left to it, in the same launch
+void launch_finalize(Ctx &c, bool jacobian, int mode);
 void launch_set_dirichlet_state(Ctx &c);    // u[dof] = g
 // ---- assemble3.hip, gd.hip, gdprep.hip, segregated.hip --------------------------------------
 bool lean3_applies(const Ctx &c);                                   // assemble3.hip
