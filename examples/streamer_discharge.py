@@ -16,6 +16,8 @@ The mesh is loaded from a DOLFIN XML file like the reference's; as that file is 
 (`fedm_amd.cases.streamer.refined_mesh`).  `--cells N` runs on an N x N graded tensor-product mesh
 instead (the headline bench's mesh).  `--model tabulated_model` takes the deck whose electron coefficients are
 E/N tables (an extension: `fedm.Coefficient_table`, looked up in the element kernels at the cell's own field).
+`--photoionization` adds the non-local source of case 3 of the same paper in the three-term Helmholtz approximation
+(an extension: `fedm.Photoionization_source`); off by default.
 
     python examples/streamer_discharge.py --mesh-spacing 8e-6 --end 1.4e-8 --out streamer_output
 """
@@ -33,6 +35,13 @@ from fedm_amd.physical_constants import elementary_charge, epsilon_0     # noqa:
 from fedm_amd.termsum import parse as deck_expression      # noqa: E402
 
 REPO = Path(__file__).resolve().parent.parent
+# Photoionisation (Bagheri et al. 2018, case 3): the three-term Helmholtz fit of Bourdon et al. 2007 for air and the
+# case's efficiency.  QUOTED FROM MEMORY -- the papers were not at hand when this was written; check them before
+# relying on a run.  No test depends on these numbers.
+PHOTO_A = (1.986e-4, 0.0051, 0.4886)            # [1/(cm^2 Torr^2)]
+PHOTO_LAMBDA = (0.0553, 0.1460, 0.89)           # [1/(cm Torr)]
+PHOTO_P_O2 = 150.0                              # partial pressure of oxygen [Torr]
+PHOTO_EFFICIENCY = 0.075 * 30.0 / (750.0 + 30.0)    # xi * p_q / (p + p_q)
 SEED = "std::log(1e13+5e18*exp(-(pow(x[0], 2)+pow(x[1]-1e-2, 2))/pow(0.4e-3, 2)))"    # ions: background + seed
 BACKGROUND = "std::log(1e13)"                                                           # electrons
 
@@ -160,7 +169,7 @@ def initial_state(case, deck, fl, dx, radius, writers, t):
         target[-1].assign(potential)
 
 
-def coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before):
+def coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before, photoionization=False):
     """Ion and electron balance in logarithmic variables + Poisson, local field approximation."""
     wall_tags = fedm.Marking_boundaries(mesh, list(case.wall_lines().values()))
     ds = fem.Measure("ds", domain=mesh, subdomain_data=wall_tags)
@@ -185,6 +194,12 @@ def coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before):
         ionisation = (1.1944e6 + 4.3666e26 * field_strength ** (-3)) * fem.exp(-2.73e7 / field_strength) - 340.75
     production = ionisation * mobility[1] * field_strength * fem.exp(u[1])            # alpha |mu E| n_e
     sources = [production, production]
+    if photoionization:
+        # every photo-electron leaves an ion behind: both balances receive the source; the Helmholtz solutions
+        # vanish on the two electrodes (tags 1 and 2), zero flux on the axis and the outer wall
+        photo = fedm.Photoionization_source(production, PHOTO_EFFICIENCY, PHOTO_A, PHOTO_LAMBDA, PHOTO_P_O2,
+                                            zero_on=[ds(1), ds(2)])
+        sources = [production + photo, production + photo]
     fluxes = [0.0, fedm.Flux(deck["charge_numbers"][1], u[1], diffusion[1], mobility[1], field_vector,
                              grad_diffusion=False)]
     charge_density = sum(z * fem.exp(u[k]) * elementary_charge / epsilon_0
@@ -207,9 +222,10 @@ def quiet_stdout(quiet):
 
 
 def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_dir=None, output_dir=None,
-         quiet=False, stop_before_device=None, coupling="coupled", model="benchmark_model"):
+         quiet=False, stop_before_device=None, coupling="coupled", model="benchmark_model", photoionization=False):
     """Runs the case; returns (state as (n_vertices, 3) array of ln n_i, ln n_e, Phi; error-log path).
-    `model`: the deck folder under the input directory ("benchmark_model", "tabulated_model")."""
+    `model`: the deck folder under the input directory ("benchmark_model", "tabulated_model").
+    `photoionization`: add the Helmholtz photoionisation source (coupled step only)."""
     case = Case(deck=model) if end_time is None else Case(deck=model, end_time=end_time)
     fem.parameters["form_compiler"]["quadrature_degree"] = 2
     deck = read_deck(case, input_dir)
@@ -234,7 +250,7 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
     t = 0.0
     file_io.log("initial time", file_io.files.model_log, t)
     initial_state(case, deck, fl, dx, radius, writers, t)
-    form, wall_tags = coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before)
+    form, wall_tags = coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before, photoionization)
     fem.File(str(out / "mesh" / "boundary_mesh_function.pvd")) << wall_tags
     fl.join.assign(fl.before, list(fl.parts_before))
     fl.join.assign(fl.now, list(fl.parts_now))
@@ -289,7 +305,9 @@ if __name__ == "__main__":
                     help="one Newton solve on the mixed space, or the segregated step")
     ap.add_argument("--model", default="benchmark_model",
                     help="deck folder: benchmark_model (closed-form coefficients) or tabulated_model (E/N tables)")
+    ap.add_argument("--photoionization", action="store_true",
+                    help="add the three-term Helmholtz photoionisation source (coefficients quoted from memory, see the source)")
     a = ap.parse_args()
     state, log_path = main(cells=a.cells, mesh_spacing=a.mesh_spacing, mesh_file=a.mesh, end_time=a.end,
-                           output_dir=a.out, coupling=a.coupling, model=a.model)
+                           output_dir=a.out, coupling=a.coupling, model=a.model, photoionization=a.photoionization)
     print(open(log_path).read())

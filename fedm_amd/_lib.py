@@ -116,6 +116,22 @@ class Csr(C.Structure):
                 ("values", C.POINTER(C.c_double))]
 
 
+PHOTO_MAX_TERMS = 4
+
+
+class PhotoDesc(C.Structure):
+    _fields_ = [("n_terms", C.c_int32), ("n_src", C.c_int32),
+                ("c", C.c_double * PHOTO_MAX_TERMS), ("kappa", C.c_double * PHOTO_MAX_TERMS),
+                ("efficiency", C.c_double), ("src_reaction", C.c_int32 * MAX_REACTIONS),
+                ("target_species_mask", C.c_uint32), ("zero_tag_mask", C.c_uint32)]
+
+
+class PhotoHierarchy(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("nu", C.c_int32),
+                ("A", C.POINTER(Csr)), ("P", C.POINTER(Csr)), ("R", C.POINTER(Csr)),
+                ("coarse_inverse", C.POINTER(C.c_double)), ("omega", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_int32, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_void_p)
 
@@ -167,6 +183,10 @@ _SIGNATURES = {
     "fedm_debug_species_assembly": (C.c_int, [_P, C.c_int]),
     "fedm_debug_block_product": (C.c_int, [_P, C.c_int, _D, _D]),
     "fedm_debug_species_linear_solve": (C.c_int, [_P, _D, C.POINTER(NewtonOpts), _D, C.POINTER(C.c_int), _D]),
+    "fedm_photo_setup": (C.c_int, [_P, C.POINTER(PhotoDesc), C.POINTER(PhotoHierarchy)]),
+    "fedm_photo_update": (C.c_int, [_P, C.c_double, C.c_int, C.POINTER(C.c_int)]),
+    "fedm_photo_get": (C.c_int, [_P, _D, _D]),
+    "fedm_photo_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
     "fedm_block_nnz": (C.c_int64, [_P]),
     "fedm_block_csr": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _D]),
     "fedm_jacobian_poisson_only": (C.c_int, [_P]),

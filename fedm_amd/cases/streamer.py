@@ -121,13 +121,34 @@ def initial_log_densities(coords):
     return u_ion, np.full_like(u_ion, np.log(1e13))
 
 
-def device_problem(coords, cells, device=0, deck_model=None, **model_kw):
+# Photoionisation (Bagheri et al. 2018, case 3): the three-term Helmholtz fit of Bourdon et al. 2007 and the case's
+# efficiency, quoted from memory (check the papers before relying on a run; no test depends on these numbers):
+# A [1/(cm^2 Torr^2)], lambda [1/(cm Torr)], p_O2 [Torr], efficiency xi p_q / (p + p_q)
+PHOTO_A, PHOTO_LAMBDA, PHOTO_P_O2 = (1.986e-4, 0.0051, 0.4886), (0.0553, 0.1460, 0.89), 150.0
+PHOTO_EFFICIENCY = 0.075 * 30.0 / (750.0 + 30.0)
+
+
+def default_photoionization(**overrides):
+    """The case's photoionisation source for ``device_problem(..., photoionization=...)``: the ionisation reaction
+    (reaction 0) feeds it, ions and electrons receive it, the Helmholtz solutions vanish on the two electrodes
+    (tags 1, 2)."""
+    from ..device import Photoionization
+    kw = dict(reactions=[0], efficiency=PHOTO_EFFICIENCY, c=[1e4 * a * PHOTO_P_O2 ** 2 for a in PHOTO_A],
+              kappa=[1e2 * v * PHOTO_P_O2 for v in PHOTO_LAMBDA], targets=[0, 1], zero_tags=[1, 2])
+    kw.update(overrides)
+    return Photoionization(**kw)
+
+
+def device_problem(coords, cells, device=0, deck_model=None, photoionization=None, **model_kw):
     """``deck_model``: the model of that deck folder (``model_from_deck``: "benchmark_model", "tabulated_model")
-    instead of the built-in strings."""
+    instead of the built-in strings.  ``photoionization``: a :class:`fedm_amd.device.Photoionization` (``True``: the
+    case's own, :func:`default_photoionization`); None: none, as the benchmark's case 1."""
     msh = Mesh(coords, cells)
     tags = Marking_boundaries(msh, BOUNDARIES)
     dofs, vals = dirichlet(msh.coords)
     lfa = model_from_deck(model_name=deck_model, **model_kw) if deck_model else model(**model_kw)
+    if photoionization is not None and photoionization is not False:
+        lfa.photoionization = default_photoionization() if photoionization is True else photoionization
     return DeviceProblem(msh.coords, msh.cells, lfa, facet_tags=tags,
                          dirichlet_dofs=dofs, dirichlet_vals=vals, device=device)
 

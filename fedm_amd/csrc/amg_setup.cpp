@@ -97,9 +97,7 @@ HostCsr csr_identity(int n) {
 
 using namespace fedm;
 
-extern "C" {
-
-int fedm_amg_clear(fedm_ctx *h) {
+extern "C" int fedm_amg_clear(fedm_ctx *h) {
     Ctx &c = h->c;
     if (c.amg || c.amg_alt) {
         hipSetDevice(c.device);
@@ -116,10 +114,10 @@ int fedm_amg_clear(fedm_ctx *h) {
     return 0;
 }
 
-// shared by the rank-local hierarchy and the replicated global one (several GPUs)
-static int build_amg(Ctx &c, int n_first_rows, int n_levels, const fedm_csr *A, const fedm_csr *P,
-                     const fedm_csr *R, const double *coarse_inverse, int nu, double omega, Amg **out,
-                     int composite_from, const double *poly_w = nullptr /* [n_levels - 1][nu] */) {
+// shared by the rank-local hierarchy, the replicated global one (several GPUs) and the photoionisation terms (solver.hpp)
+int fedm::build_amg(Ctx &c, int n_first_rows, int n_levels, const fedm_csr *A, const fedm_csr *P,
+                    const fedm_csr *R, const double *coarse_inverse, int nu, double omega, Amg **out,
+                    int composite_from, const double *poly_w) {
     // the hierarchy's matrices in single precision (FEDM_MG_F32=0: double); see EllMat::single
     const char *mg_env = std::getenv("FEDM_MG_F32");
     const bool mg_single = !(mg_env && mg_env[0] == '0');
@@ -323,6 +321,8 @@ static int build_amg(Ctx &c, int n_first_rows, int n_levels, const fedm_csr *A, 
     *out = amg;
     return 0;
 }
+
+extern "C" {
 
 int fedm_amg_setup(fedm_ctx *h, int n_levels, const fedm_csr *A, const fedm_csr *P,
                    const fedm_csr *R, const double *coarse_inverse, int nu, double omega) {

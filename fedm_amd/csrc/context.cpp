@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "photo.hpp"
 #include "solver.hpp"
 
 namespace fedm {
@@ -755,6 +756,7 @@ void fedm_ctx_destroy(fedm_ctx *h) {
         delete c.comm;
     }
     gd_prep_release(c);
+    photo_release(c);
     fs_tiles_release(c);
     for (auto &e : c.prof.ev) hipEventDestroy(e);
     iter_graphs_clear(c);
@@ -893,6 +895,10 @@ int fedm_ext_source_program(fedm_ctx *h, int species, int n_ops, const int32_t *
     Ctx &c = h->c;
     if (species < 0 || species >= c.ns || !c.d_ext[species]) {
         set_error("species has no Expression source");
+        return -2;
+    }
+    if (c.photo && ((c.photo->desc.target_species_mask >> species) & 1u)) {
+        set_error("species receives the photoionisation source: one source table cannot hold an Expression program as well");
         return -2;
     }
     const int nodes = c.model.ext_nodes[species];

@@ -73,6 +73,7 @@ struct Amg;
 struct Comm;
 struct GdPrep;
 struct FsTiles;
+struct Photo;
 
 // Optional in-run kernel timing with HIP events on the library's stream (bench.py roofline).
 // kinds: 0 assembly F+J, 1 Jacobian SpMV, 2 assembly F only, 3 multigrid V-cycle
@@ -308,6 +309,7 @@ struct Ctx {
     double *d_seg_dinv = nullptr;
     int seg_newton_its_hint = -1;     // Newton iterations of the previous converged species solve (its final check is residual-only)
     bool seg_jacobian_done = false;   // fedm_poisson_update has assembled a Jacobian itself (contexts whose assembly never sets const_planes_valid)
+    Photo *photo = nullptr;   // photoionisation: Helmholtz sources into the targets' source tables (photo.hpp; fedm_photo_setup)
 };
 
 // Indices of Ctx::path_stats, in the order fedm_solver_path_stats documents (include/fedm_hip.h)
@@ -423,6 +425,8 @@ void launch_species_sweep(Ctx &c, double w, const double *r, const double *t, do
 void launch_potential_jacobi(Ctx &c, const double *r, double *z);   // z_phi = r_phi / diag(J_phiphi), z_u = 0
 // y = a x on the species entries (which = 0) or the potential entries (which = 1), 0 on the others
 void launch_pick_entries(Ctx &c, int which, double a, const double *x, double *y);
+// ---- photo.hip (photo.hpp has the rest) -------------------------------------------------------
+void photo_release(Ctx &c);
 // ---- spmv.hip -------------------------------------------------------------------------------
 void launch_block_inverse(Ctx &c);                              // d_dinv from diagonal blocks
 void launch_row_scale(Ctx &c, double *d2, double *d_out);       // d^2 (and d, unless null) of the rows' equilibration

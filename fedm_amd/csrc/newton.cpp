@@ -102,6 +102,11 @@ int segregated_refusal(Ctx &c, const char *who, bool species) {
         set_error(std::string(who) + ": the segregated step runs on one GPU (this context has a transport or ghost vertices)");
         return -2;
     }
+    if (c.photo) {
+        set_error(std::string(who) + ": this context has photoionisation set up, whose source tables the segregated step has "
+                  "not been tried with (coupled step only: fedm_newton_solve)");
+        return -2;
+    }
     if (species && c.krylov_scaling != 0) {
         set_error(std::string(who) + ": krylov scaling 'rows' is not defined for the species block (its own equilibration "
                   "is not implemented): set the krylov scaling to 'none'");

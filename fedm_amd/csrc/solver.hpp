@@ -35,6 +35,13 @@ struct CgResult {
 };
 CgResult preconditioned_cg(Ctx &c, CgMatrix matrix, double rtol, int max_it);
 
+// amg_setup.cpp: a hierarchy of n_first_rows unknowns built and uploaded into *out (the potential block's, the
+// replicated global one, a photoionisation term's).  composite_from: the first level that may fold its smoother into
+// composite operators (beyond the last level: plain sweeps everywhere).
+int build_amg(Ctx &c, int n_first_rows, int n_levels, const fedm_csr *A, const fedm_csr *P, const fedm_csr *R,
+              const double *coarse_inverse, int nu, double omega, Amg **out, int composite_from,
+              const double *poly_w = nullptr /* [n_levels - 1][nu] */);
+
 // newton.cpp
 void set_hard_mode(Ctx &c, bool hard);
 int segregated_refusal(Ctx &c, const char *who, bool species);

@@ -19,6 +19,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, quadrature
+from .photo import Photoionization
 from .physical_constants import elementary_charge, epsilon_0
 from .termsum import TermSum
 
@@ -71,10 +72,24 @@ class Model:
     axisymmetric: bool = True
     log_representation: bool = True            # False: the unknowns are the densities (functions.py:350-368)
     walls: Optional[Walls] = None              # for the 'flux source' entries of bc_kind
+    # Helmholtz photoionisation source (fedm_amd.photo): its targets get degree-1 source tables, which the device fills
+    photoionization: Optional[Photoionization] = None
 
     @property
     def n_eq(self):
         return self.n_species + (1 if self.poisson else 0)
+
+    def source_table_degrees(self):
+        """``ext_source_degree`` with the degree-1 tables that ``photoionization`` implies on its targets."""
+        ext = list(self.ext_source_degree) or [0] * self.n_species
+        if self.photoionization is not None:
+            self.photoionization.check(self)
+            for s in self.photoionization.targets:
+                if ext[s] not in (0, 1):
+                    raise ValueError(f"species {s} receives the photoionisation source through a degree-1 source table; "
+                                     f"it has an Expression source of degree {ext[s]}")
+                ext[s] = 1
+        return ext
 
     def walls_to_c(self):
         """fedm_wall_desc for fedm_ctx_create_walls, or None for a model without 'flux source' entries."""
@@ -148,7 +163,7 @@ class Model:
         md.n_fqp = len(wt)
         for q in range(len(wt)):
             md.fqp_t[q], md.fqp_w[q] = tq[q], wt[q]
-        ext = list(self.ext_source_degree) or [0] * ns
+        ext = self.source_table_degrees()
         degs = {k for k in ext if k}
         if len(degs) > 1:
             raise ValueError("all Expression sources must share one degree")
@@ -513,6 +528,15 @@ class DeviceProblem:
         if rc != 0:
             raise RuntimeError(f"fedm_ctx_create failed ({rc}): {_lib.last_error()}")
         self._h = handle
+        # photoionisation: the Helmholtz operators and their hierarchies, once (host); the source is stale until the
+        # first update, and again after everything that changes u_old
+        self._photo_stale = False
+        photo = None if isinstance(model, GdModel) else model.photoionization
+        if photo is not None:
+            from . import photo as photo_setup
+            self.photo_levels = photo_setup.install(self.lib, self._h, photo, self._coords_dev, self._cells_dev,
+                                                    self._tags, model.axisymmetric, model.quadrature_degree)
+            self._photo_stale = True
 
     # -- lifetime ----------------------------------------------------------
     def close(self):
@@ -550,6 +574,7 @@ class DeviceProblem:
         vs = [self._vec(v) for v in (u_new, u_old, u_old1)]
         self._check(self.lib.fedm_set_state(self._h, *[_dp(v) if v is not None else None for v in vs]),
                     "fedm_set_state")
+        self._photo_stale = self._has_photo()
 
     def get_state(self):
         out = np.empty(self.n)
@@ -558,9 +583,11 @@ class DeviceProblem:
 
     def shift_state(self):
         self._check(self.lib.fedm_shift_state(self._h), "fedm_shift_state")
+        self._photo_stale = self._has_photo()
 
     def reset_state(self):
         self._check(self.lib.fedm_reset_state(self._h), "fedm_reset_state")
+        self._photo_stale = self._has_photo()
 
     def snapshot_state(self):
         """u, u_old, u_old1 into a device-side copy (fedm_state_snapshot)."""
@@ -568,6 +595,7 @@ class DeviceProblem:
 
     def restore_state(self):
         self._check(self.lib.fedm_state_restore(self._h), "fedm_state_restore")
+        self._photo_stale = self._has_photo()
 
     def set_step(self, dt, dt_old):
         self._check(self.lib.fedm_set_step(self._h, float(dt), float(dt_old)), "fedm_set_step")
@@ -664,11 +692,52 @@ class DeviceProblem:
 
     def get_ext_source(self, species):
         """The species' source table as it stands on the device, (n_cells, nodes) (``fedm_debug_get_ext_source``)."""
-        degrees = list(getattr(self.model, "ext_source_degree", ()))
+        degrees = (self.model.source_table_degrees() if hasattr(self.model, "source_table_degrees")
+                   else list(getattr(self.model, "ext_source_degree", ())))
         k = degrees[int(species)] if 0 <= int(species) < len(degrees) else 0
         out = np.empty((self.nc, (k + 1) * (k + 2) // 2))          # (no source: the library refuses, nothing is written)
         self._check(self.lib.fedm_debug_get_ext_source(self._h, int(species), _dp(out)), "fedm_debug_get_ext_source")
         return out
+
+    # -- photoionisation (Helmholtz sources, csrc/photo.hip) ---------------------------
+    def _has_photo(self):
+        return getattr(self.model, "photoionization", None) is not None
+
+    def photo_update(self):
+        """The photoionisation source of the state as it stands (``fedm_photo_update``): the ionisation rate at
+        ``u_old``, one warm-started CG solve per Helmholtz term, the targets' source tables.  Explicit lag: it is
+        frozen until ``u_old`` changes (``shift_state``, ``set_state``, ``reset_state``, ``restore_state`` mark it
+        stale; :meth:`newton_solve` updates a stale source first), so a step retried with a smaller ``dt`` reuses it.
+        Returns the CG iterations per term, kept in ``last_photo_iterations`` too."""
+        if not self._has_photo():
+            raise RuntimeError("the model has no photoionisation source")
+        ph = self.model.photoionization
+        its = (C.c_int * _lib.PHOTO_MAX_TERMS)()
+        rc = self.lib.fedm_photo_update(self._h, float(ph.rtol), int(ph.max_it), its)
+        self.last_photo_iterations = [int(v) for v in its[:len(ph.c)]]
+        if rc == 3:
+            raise RuntimeError(f"fedm_photo_update: conjugate gradients stopped at max_it = {ph.max_it} "
+                               f"(iterations per term {self.last_photo_iterations})")
+        self._check(rc, "fedm_photo_update")
+        self._photo_stale = False
+        return self.last_photo_iterations
+
+    def get_photo(self):
+        """``(y, g)`` of the last update: the Helmholtz solutions ``y[n_terms, n_vertices]`` and the load vector
+        ``g[n_vertices]``, caller's vertex numbering (``fedm_photo_get``)."""
+        n_terms = len(self.model.photoionization.c) if self._has_photo() else 1
+        y, g = np.empty((n_terms, self.nv)), np.empty(self.nv)
+        self._check(self.lib.fedm_photo_get(self._h, _dp(y), _dp(g)), "fedm_photo_get")
+        return np.ascontiguousarray(y[:, self._inv]), np.ascontiguousarray(g[self._inv])
+
+    PHOTO_STATS = ("updates", "cg_iterations_0", "cg_iterations_1", "cg_iterations_2", "cg_iterations_3", "vcycles",
+                   "exhausted", "reserved")
+
+    def photo_stats(self, reset=False):
+        """Counters of the photoionisation updates since the set-up or the last reset (``fedm_photo_stats``)."""
+        out = (C.c_int64 * 8)()
+        self._check(self.lib.fedm_photo_stats(self._h, out, 1 if reset else 0), "fedm_photo_stats")
+        return dict(zip(self.PHOTO_STATS, (int(v) for v in out)))
 
     # -- Problem.F / Problem.J ------------------------------------------------
     def residual(self, download=True):
@@ -967,6 +1036,8 @@ class DeviceProblem:
         o = _lib.NewtonOpts(rtol, atol, stol, max_it, ksp_restart, ksp_rtol, ksp_atol, ksp_max_it,
                             0 if watch is None else int(watch) + 1)
         r = _lib.NewtonReport()
+        if self._photo_stale:      # the source of this step, from the accepted state u_old; a retried step keeps it
+            self.photo_update()
         rc = self.lib.fedm_newton_solve(self._h, C.byref(o), C.byref(r))
         self.last_report = NewtonReport(r.iterations, bool(r.converged), r.linear_iterations,
                                         r.fnorm0, r.fnorm)

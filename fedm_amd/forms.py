@@ -37,6 +37,8 @@ def near(a, b, eps=DOLFIN_EPS):
 # ---------------------------------------------------------------------------------------
 class _Ops:
     def __add__(self, o):
+        if isinstance(o, PhotoSource):          # joins a source term of densities, or is refused (LFA models only)
+            return o.__radd__(self)
         return Sym("add", self, o)
 
     def __radd__(self, o):
@@ -376,7 +378,7 @@ class Function(_Ops):
 
     def __add__(self, o):
         # a zero Function used as an accumulator of source terms (fedm-streamer.py:164,246)
-        if isinstance(o, (RateSum, Rate, Density)):
+        if isinstance(o, (RateSum, Rate, Density, PhotoSource)):
             return NotImplemented
         if isinstance(o, (Sym, Unknown)) and not np.any(self._v) and o_is_source(o):
             return RateSum.coerce(o)                  # zero Function + densities written with bare unknowns
@@ -687,14 +689,43 @@ class Rate:
         raise ValueError("exp() of a density product is not a supported expression")
 
 
+class PhotoSource:
+    """The term ``fedm_amd.functions.Photoionization_source`` returns: added to a species' source
+    (``f[i] = alpha*mu[1]*E_m*exp(u[1]) + S_ph``) it rides along in the RateSum as its ``photo``."""
+
+    def __init__(self, ionization, efficiency, c, kappa, zero_tags):
+        self.ionization, self.efficiency = ionization, float(efficiency)
+        self.c, self.kappa, self.zero_tags = list(c), list(kappa), list(zero_tags)
+        self.subdomain_data = None      # the boundary MeshFunction of the zero_on measures
+
+    def __add__(self, o):
+        if isinstance(o, Expression):
+            raise ValueError("fedm.Photoionization_source: a species cannot have both an Expression source and the "
+                             "photoionisation source (one source table per species)")
+        try:
+            return RateSum.coerce(o) + RateSum([], photo=self)
+        except TypeError as exc:                # nodal coefficients, LMEA source objects: not the LFA family
+            raise ValueError("fedm.Photoionization_source: LFA models only -- it is added to a source term made of "
+                             f"coefficients of |E| and densities exp(u[i]), not to {type(o).__name__}") from exc
+
+    __radd__ = __add__
+
+
 class RateSum:
-    def __init__(self, terms=()):
+    def __init__(self, terms=(), photo=None):
         self.terms = list(terms)
+        self.photo = photo          # a PhotoSource added to the sum, or None
+
+    def _no_photo(self, what):
+        if self.photo is not None:
+            raise ValueError(f"fedm.Photoionization_source can only be added to a source term, not {what}")
 
     @staticmethod
     def coerce(x):
         if isinstance(x, RateSum):
             return x
+        if isinstance(x, PhotoSource):
+            return RateSum([], photo=x)
         if isinstance(x, Rate):
             return RateSum([x])
         if isinstance(x, (Real, TermSum)):
@@ -725,11 +756,17 @@ class RateSum:
         raise TypeError(f"cannot use {type(x).__name__} in a source-term expression")
 
     def __add__(self, o):
-        return RateSum(self.terms + RateSum.coerce(o).terms)
+        if isinstance(o, Expression) and self.photo is not None:
+            return self.photo + o               # (raises: one source table per species)
+        o = RateSum.coerce(o)
+        if self.photo is not None and o.photo is not None and self.photo is not o.photo:
+            raise ValueError("fedm.Photoionization_source: two different photoionisation sources in one form")
+        return RateSum(self.terms + o.terms, photo=self.photo if self.photo is not None else o.photo)
 
     __radd__ = __add__
 
     def __neg__(self):
+        self._no_photo("negated")
         return RateSum([Rate(-t.coef, t.powers, t.bare) for t in self.terms])
 
     def __sub__(self, o):
@@ -740,6 +777,8 @@ class RateSum:
 
     def __mul__(self, o):
         o = RateSum.coerce(o)
+        self._no_photo("multiplied")
+        o._no_photo("multiplied")
         out = []
         for a in self.terms:
             for b in o.terms:
@@ -752,6 +791,7 @@ class RateSum:
     __rmul__ = __mul__
 
     def __truediv__(self, o):
+        self._no_photo("divided")
         o = TermSum.coerce(float(o) if isinstance(o, (Constant, Sym)) else o)
         return RateSum([Rate(t.coef / o, t.powers, t.bare) for t in self.terms])
 

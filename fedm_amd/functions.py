@@ -355,7 +355,13 @@ def compile_forms(F, quadrature_degree=None):
                 raise ValueError(f"{where}: densities must enter as " + ("exp(u[i])" if log else "u[i]")
                                  + f" in the {'logarithmic' if log else 'non-logarithmic'} representation")
     drift_w, ext_sources = [None] * ns, []
+    photo, photo_targets = None, []
     for s, p in enumerate(balances):
+        if isinstance(p.f, (forms.RateSum, forms.PhotoSource)) and forms.RateSum.coerce(p.f).photo is not None:
+            if photo is not None and forms.RateSum.coerce(p.f).photo is not photo:
+                raise ValueError("fedm.Photoionization_source: two different photoionisation sources in one form")
+            photo = forms.RateSum.coerce(p.f).photo
+            photo_targets.append(s)
         if isinstance(p.f, forms.Expression):
             # a source given as a spatial Expression of degree d (fedm-tof.py:116): interpolated at the
             # P_d lattice nodes of every cell and refreshed before each solve (Problem.before_solve)
@@ -397,6 +403,9 @@ def compile_forms(F, quadrature_degree=None):
         ps = poissons[0]
         if ps.u.index != ns:
             raise ValueError("the potential must be the last component of the mixed space")
+        if forms.RateSum.coerce(ps.f).photo is not None:
+            raise ValueError("fedm.Photoionization_source belongs to the source of a balance equation, not to the "
+                             "right-hand side of the Poisson equation")
         check_densities(forms.RateSum.coerce(ps.f).terms, "Poisson source")
         for term in forms.RateSum.coerce(ps.f).terms:
             if len(term.powers) != 1 or list(term.powers.values()) != [1] or not term.coef.is_const():
@@ -408,8 +417,13 @@ def compile_forms(F, quadrature_degree=None):
             if Z[i] not in (0.0,) and abs(Z[i] - zi) > 1e-9 * max(1.0, abs(zi)):
                 raise ValueError("charge in the Poisson source differs from the flux sign")
             Z[i] = zi
-    n_tags = max([b.tag for b in bterms], default=0)
+    n_tags = max([b.tag for b in bterms] + (list(photo.zero_tags) if photo is not None else []), default=0)
     tags_mf = next((b.ds.subdomain_data for b in bterms if b.ds.subdomain_data is not None), None)
+    if tags_mf is None and photo is not None:
+        tags_mf = photo.subdomain_data
+    if photo is not None and photo.zero_tags and tags_mf is None:
+        raise ValueError("fedm.Photoionization_source: zero_on needs measures of a marked boundary, "
+                         "ds = Measure('ds', domain=mesh, subdomain_data=boundary_mesh_function)")
     if tags_mf is not None:
         n_tags = max(n_tags, int(np.max(tags_mf)))
     bc_kind = [["zero flux"] * ns for _ in range(n_tags)]
@@ -437,6 +451,19 @@ def compile_forms(F, quadrature_degree=None):
                 raise NotImplementedError("Expression sources of degree 1 or 2")
             degrees[s] = int(e.degree)
         extra["ext_source_degree"] = degrees
+    if photo is not None:
+        from .device import Photoionization
+        check_densities(photo.ionization.terms, "ionisation rate of Photoionization_source")
+        src = []
+        for k, term in enumerate(photo.ionization.terms):
+            power = [int(term.powers.get(i, 0)) for i in range(ns)]
+            hit = [j for j, rc in enumerate(reactions) if rc.k.same_as(term.coef) and list(rc.power) == power]
+            if not hit or any(i >= ns for i in term.powers):
+                raise ValueError(f"fedm.Photoionization_source: term {k} of the ionisation rate (densities to the powers "
+                                 f"{dict(term.powers)}) is not a reaction of the model's source terms")
+            src.append(hit[0])
+        extra["photoionization"] = Photoionization(reactions=src, efficiency=photo.efficiency, c=photo.c,
+                                                   kappa=photo.kappa, targets=photo_targets, zero_tags=photo.zero_tags)
     model = Model(n_species=ns, poisson=bool(poissons), eq_type=eq_type, Z=Z, mu=mu, D=D,
                   reactions=reactions, bc_kind=bc_kind, quadrature_degree=int(qd),
                   axisymmetric=axis, log_representation=log, walls=walls, **extra)
@@ -877,6 +904,44 @@ def Coefficient_table(E_m, kx, ky, N0):
     if not (isinstance(E_m, TermSum) and not E_m.tables and E_m.terms == TermSum.field().terms):
         raise TypeError("fedm.Coefficient_table: E_m must be the field magnitude sqrt(inner(-grad(u[n]), -grad(u[n])))")
     return TermSum.table(np.asarray(kx, dtype=np.float64) * float(N0) * 1e-21, ky)
+
+
+def Photoionization_source(ionization, efficiency, A, lam, p_O2, zero_on=()):
+    """Extension (no counterpart in fedm/functions.py): photoionisation in the Helmholtz approximation of Bourdon et
+    al. 2007, ``S_ph = sum_m c_m y_m`` with ``(-lap + kappa_m^2) y_m = efficiency * ionization``, as a term that is
+    added to the source of every species that receives it: ``f[i] = alpha*mu[1]*E_m*exp(u[1]) + S_ph``.
+
+    ``ionization``: the ionisation rate itself (``alpha*mu[1]*E_m*exp(u[1])``); its terms must be reactions that the
+    model's sources contain.  ``A`` [1/(cm^2 Torr^2)], ``lam`` [1/(cm Torr)] and ``p_O2`` [Torr] as published:
+    ``c = 1e4 A p_O2^2`` [1/m^2], ``kappa = 1e2 lam p_O2`` [1/m].  ``zero_on``: the ``ds(tag)`` on whose vertices
+    ``y_m = 0`` (zero flux on the rest of the boundary).
+
+    Explicit lag: the device evaluates the rate at ``u_old`` once per accepted step, solves the Helmholtz problems and
+    keeps ``S_ph`` frozen during the Newton solve (first order in dt; ``DeviceProblem.photo_update``).  LFA models,
+    coupled step, one GPU."""
+    from . import forms
+    A, lam = [float(a) for a in np.atleast_1d(A)], [float(v) for v in np.atleast_1d(lam)]
+    if len(A) != len(lam) or not 1 <= len(A) <= 4:
+        raise ValueError("fedm.Photoionization_source: one A per lam, 1 to 4 Helmholtz terms")
+    p = float(p_O2)
+    if not p > 0.0 or any(not v > 0.0 for v in lam):
+        raise ValueError("fedm.Photoionization_source: p_O2 and every lam must be positive")
+    tags = []
+    for m in (zero_on if isinstance(zero_on, (list, tuple)) else [zero_on]):
+        if not isinstance(m, forms.Measure) or m.kind != "ds" or m.tag is None:
+            raise ValueError("fedm.Photoionization_source: zero_on takes boundary measures ds(tag)")
+        tags.append(int(m.tag))
+    try:
+        rate = forms.RateSum.coerce(ionization)
+    except TypeError as exc:
+        raise ValueError("fedm.Photoionization_source: LFA models only -- the ionisation rate must be a sum of "
+                         "coefficients of |E| times densities exp(u[i])") from exc
+    if not rate.terms or rate.photo is not None:
+        raise ValueError("fedm.Photoionization_source: the ionisation rate has no terms")
+    src = forms.PhotoSource(rate, efficiency, [1e4 * a * p * p for a in A], [1e2 * v * p for v in lam], tags)
+    measures = zero_on if isinstance(zero_on, (list, tuple)) else [zero_on]
+    src.subdomain_data = next((m.subdomain_data for m in measures if m.subdomain_data is not None), None)
+    return src
 
 
 def semi_implicit_coefficients(dependences, mean_energy_new, mean_energy_old, coefficients,

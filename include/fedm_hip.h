@@ -242,7 +242,8 @@ const char *fedm_last_error(void);
  *    looked-up table without entries, a tab_ptr that does not start at 0 or decreases, null table arrays, a program
  *    kind or argument outside its enum).  Additive under 10 (no struct changes size or offsets, no signature changes):
  *    fedm_ctx_create_tabulated; fedm_termsum.pad_, which had to be 0, is the table reference.  fedm_ctx_create_walls
- *    with fedm_wall_desc; FEDM_BC_FLUX_SOURCE, a value of bc_kind that the two older creators refuse. */
+ *    with fedm_wall_desc; FEDM_BC_FLUX_SOURCE, a value of bc_kind that the two older creators refuse.
+ *    fedm_photo_setup with fedm_photo_desc and fedm_photo_hierarchy, fedm_photo_update, fedm_photo_get, fedm_photo_stats. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -405,6 +406,63 @@ int fedm_debug_block_product(fedm_ctx *ctx, int which, const double *x, double *
  * residual norm |b_u - J_uu x_u|_2 it reports. */
 int fedm_debug_species_linear_solve(fedm_ctx *ctx, const double *b, const fedm_newton_opts *opts, double *x, int *its,
                                     double *rnorm);
+
+/* ---- photoionisation: Helmholtz sources on the device -----------------------------------------
+ * The three-term Helmholtz approximation of the photoionisation integral (Bourdon et al. 2007; case 3 of Bagheri et
+ * al. 2018): with R = sum_(j in src_reaction) k_j(|E|) prod_i n_i^power[j][i], the rate of the designated reactions,
+ *     S_ph = sum_m c[m] y_m,      (-lap + kappa[m]^2) y_m = efficiency R,
+ * weak form  int (grad y . grad v + kappa^2 y v) w dx = int efficiency R v w dx  with w = x[0] for an axisymmetric model
+ * and 1 otherwise, y = 0 on the vertices of the facets whose tag is in zero_tag_mask (bit tag - 1), zero flux elsewhere.
+ * S_ph goes into the degree-1 source tables (ext_nodes = 3) of the species in target_species_mask, which the element
+ * routines add to those species' rows as they add an Expression source.
+ * Explicit lag: R is evaluated at u_old -- densities exp(u_old) (u_old itself in the linear representation), |E| of
+ * u_old's potential, rate coefficients once per cell as the element routines evaluate them, the model's quadrature
+ * rule -- so the source is frozen during a Newton solve and the Jacobian stays exact.  First order in dt.  The mass
+ * matrix is the consistent one: S_ph may undershoot zero slightly where kappa h is large; it enters the balance
+ * linearly and is neither lumped nor clipped.
+ * One GPU, LFA family, coupled step (fedm_newton_solve): fedm_poisson_update and fedm_newton_solve_species refuse a
+ * context with photoionisation set up. */
+typedef struct {
+    int32_t n_terms;                             /* 1..4                                                    */
+    int32_t n_src;                               /* 1..FEDM_MAX_REACTIONS designated ionisation reactions   */
+    double c[4];                                 /* [1/m^2]                                                 */
+    double kappa[4];                             /* [1/m], > 0                                              */
+    double efficiency;
+    int32_t src_reaction[FEDM_MAX_REACTIONS];    /* indices into fedm_model_desc.k                          */
+    uint32_t target_species_mask;                /* bit s: species s receives S_ph                          */
+    uint32_t zero_tag_mask;                      /* bit t - 1: y = 0 on the vertices of the facets tagged t */
+} fedm_photo_desc;
+/* One term's preconditioner, as fedm_amg_setup takes the potential block's: A[0] is the term's operator
+ * K_w + kappa^2 M_w in the context's vertex numbering with the rows and columns of the zero vertices eliminated
+ * symmetrically (unit diagonal), kept in double precision as the operator of the conjugate gradients; the levels
+ * below precondition them with plain V(nu,nu) cycles of damped Jacobi (nu > 0).  n_levels = 1: Jacobi alone (P, R and
+ * coarse_inverse are not read). */
+typedef struct {
+    int32_t n_levels, nu;
+    const fedm_csr *A, *P, *R;
+    const double *coarse_inverse;
+    double omega;
+} fedm_photo_hierarchy;
+/* Refused (-2, nothing installed, fedm_last_error says why): an LMEA context; a context with ghost vertices or a
+ * transport; n_terms outside 1..4; kappa <= 0 or not finite; n_src outside 1..FEDM_MAX_REACTIONS or a reaction index
+ * outside the model's; no target species, a target beyond the model's species, one without a degree-1 source table or
+ * one with an Expression program; a tag bit beyond the model's tags; a hierarchy that fedm_amg_setup would refuse.
+ * Replaces an earlier set-up; every y_m starts at 0. */
+int fedm_photo_setup(fedm_ctx *ctx, const fedm_photo_desc *desc, const fedm_photo_hierarchy *terms /* [n_terms] */);
+/* Load vector g_a = int efficiency R phi_a w from u_old (once for all terms; summed per vertex in a fixed order, no
+ * atomics: bitwise reproducible), then per term conjugate gradients warm-started from the previous update's y_m until
+ * |r|_2 <= rtol |g|_2 on the recurrence's residual (0 iterations when the start already satisfies it), then the
+ * targets' tables ext[cell][a] = sum_m c[m] y_m[vertex a of cell].  iterations (unless NULL): CG steps per term.
+ * Returns 0, FEDM_DIVERGED_LINEAR (a term stopped at max_it; the tables are written all the same) or FEDM_DIVERGED_NAN
+ * (a state that is not finite, or an operator that is not positive definite: the terms it met are set back to 0, so the
+ * tables written are finite and the next update starts clean; no new set-up is needed). */
+int fedm_photo_update(fedm_ctx *ctx, double rtol, int max_it, int iterations[4]);
+/* Test hook: the solutions y[n_terms][n_vertices] and the load vector g[n_vertices] of the last update (either may be
+ * NULL), in the context's vertex numbering. */
+int fedm_photo_get(fedm_ctx *ctx, double *y, double *g);
+/* out = {updates, CG iterations of term 0, 1, 2, 3, V-cycles, terms that stopped at max_it, reserved} since the set-up
+ * (or the last call with reset != 0; out may be NULL then). */
+int fedm_photo_stats(fedm_ctx *ctx, int64_t out[8], int reset);
 
 /* ---- linear solver set-up -----------------------------------------------------------------
  * The reference hands J dx = -F to MUMPS (examples) or to PETSc GMRES + default PC (test
