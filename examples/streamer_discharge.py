@@ -18,6 +18,9 @@ instead (the headline bench's mesh).  `--model tabulated_model` takes the deck w
 E/N tables (an extension: `fedm.Coefficient_table`, looked up in the element kernels at the cell's own field).
 `--photoionization` adds the non-local source of case 3 of the same paper in the three-term Helmholtz approximation
 (an extension: `fedm.Photoionization_source`); off by default.
+`--diagnostics FILE` writes one row per accepted step (every N-th with `--diagnostics-every N`): head position, field
+maximum in the channel, particle numbers, net charge, electrode charges and the induced current, computed on the
+device without downloading the state (an extension: `fedm.Discharge_diagnostics`); off by default.
 
     python examples/streamer_discharge.py --mesh-spacing 8e-6 --end 1.4e-8 --out streamer_output
 """
@@ -42,6 +45,9 @@ PHOTO_A = (1.986e-4, 0.0051, 0.4886)            # [1/(cm^2 Torr^2)]
 PHOTO_LAMBDA = (0.0553, 0.1460, 0.89)           # [1/(cm Torr)]
 PHOTO_P_O2 = 150.0                              # partial pressure of oxygen [Torr]
 PHOTO_EFFICIENCY = 0.075 * 30.0 / (750.0 + 30.0)    # xi * p_q / (p + p_q)
+CHANNEL_RADIUS = 0.9e-3        # cells nearer to the axis than this mark the streamer's head (the mesh's finest region)
+DIAGNOSTICS_COLUMNS = ("t", "z_head", "E_max", "N_e", "N_i", "net_charge", "surface_charge_cathode",
+                       "surface_charge_anode", "current")
 SEED = "std::log(1e13+5e18*exp(-(pow(x[0], 2)+pow(x[1]-1e-2, 2))/pow(0.4e-3, 2)))"    # ions: background + seed
 BACKGROUND = "std::log(1e13)"                                                           # electrons
 
@@ -222,10 +228,12 @@ def quiet_stdout(quiet):
 
 
 def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_dir=None, output_dir=None,
-         quiet=False, stop_before_device=None, coupling="coupled", model="benchmark_model", photoionization=False):
+         quiet=False, stop_before_device=None, coupling="coupled", model="benchmark_model", photoionization=False,
+         diagnostics=None, diagnostics_every=1):
     """Runs the case; returns (state as (n_vertices, 3) array of ln n_i, ln n_e, Phi; error-log path).
     `model`: the deck folder under the input directory ("benchmark_model", "tabulated_model").
-    `photoionization`: add the Helmholtz photoionisation source (coupled step only)."""
+    `photoionization`: add the Helmholtz photoionisation source (coupled step only).
+    `diagnostics`: a file that receives DIAGNOSTICS_COLUMNS per accepted step (every `diagnostics_every`-th)."""
     case = Case(deck=model) if end_time is None else Case(deck=model, end_time=end_time)
     fem.parameters["form_compiler"]["quadrature_degree"] = 2
     deck = read_deck(case, input_dir)
@@ -260,6 +268,15 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
     build_problem = stop_before_device or fedm.Problem
     problem = build_problem(jacobian, residual, electrode_conditions(case, fl.mixed.sub(deck["n_equations"] - 1)))
     problem.device.setup_multigrid(nu=1)                 # preconditioner of the device's GMRES (no script counterpart)
+    diagnose = rows = None
+    if diagnostics is not None:
+        # electrodes: tags 1 (cathode) and 2 (anode) of wall_lines(); psi = z / gap is exact for the planar gap
+        diagnose = fedm.Discharge_diagnostics(problem, boundary_tags=(1, 2),
+                                              window=(0.0, CHANNEL_RADIUS, 0.0, case.side),
+                                              weighting_potential=mesh.coords[:, 1] / case.side)
+        rows = open(diagnostics, "w")
+        rows.write("# " + " ".join(DIAGNOSTICS_COLUMNS) + "\n")
+    accepted = 0
     newton = fedm.PETScSNESSolver()
     newton.parameters["relative_tolerance"] = case.newton_rtol
     newton.parameters["maximum_iterations"] = case.newton_max_it
@@ -288,9 +305,18 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
         dt.time_step = fedm.adaptive_timestep(dt.time_step, recent_errors, case.step_tolerance, case.shortest_step,
                                               case.longest_step)
         recent_errors[1:] = recent_errors[:2]
+        accepted += 1
+        if diagnose is not None and accepted % max(1, int(diagnostics_every)) == 0:
+            d = diagnose()
+            row = (t, d.z_head, d.window_max, d.species_integral[1], d.species_integral[0], d.net_charge,
+                   d.surface_charge[0], d.surface_charge[1], d.current)
+            rows.write(" ".join(f"{x:.17g}" for x in row) + "\n")
+            rows.flush()
         window, stride = file_io.file_output(t, t_before, window, stride, list(case.output_windows),
                                              list(case.output_windows), ["pvd"] * len(order), out_files, out_names,
                                              out_now, out_before)
+    if rows is not None:
+        rows.close()
     return problem.device.get_state(), file_io.files.error_file
 
 
@@ -307,7 +333,11 @@ if __name__ == "__main__":
                     help="deck folder: benchmark_model (closed-form coefficients) or tabulated_model (E/N tables)")
     ap.add_argument("--photoionization", action="store_true",
                     help="add the three-term Helmholtz photoionisation source (coefficients quoted from memory, see the source)")
+    ap.add_argument("--diagnostics", metavar="FILE",
+                    help="write t, z_head, E_max, N_e, N_i, net charge, electrode charges and current per accepted step")
+    ap.add_argument("--diagnostics-every", type=int, default=1, metavar="N", help="... every N-th accepted step")
     a = ap.parse_args()
     state, log_path = main(cells=a.cells, mesh_spacing=a.mesh_spacing, mesh_file=a.mesh, end_time=a.end,
-                           output_dir=a.out, coupling=a.coupling, model=a.model, photoionization=a.photoionization)
+                           output_dir=a.out, coupling=a.coupling, model=a.model, photoionization=a.photoionization,
+                           diagnostics=a.diagnostics, diagnostics_every=a.diagnostics_every)
     print(open(log_path).read())

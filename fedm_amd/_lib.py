@@ -132,6 +132,25 @@ class PhotoHierarchy(C.Structure):
                 ("coarse_inverse", C.POINTER(C.c_double)), ("omega", C.c_double)]
 
 
+DIAG_MAX_GROUPS = 8
+
+
+class DiagOpts(C.Structure):
+    _fields_ = [("state", C.c_int32), ("pad_", C.c_int32),
+                ("r_lo", C.c_double), ("r_hi", C.c_double), ("z_lo", C.c_double), ("z_hi", C.c_double)]
+
+
+class DiagOut(C.Structure):
+    _fields_ = [("species_integral", C.c_double * MAX_SPECIES), ("group_sum", C.c_double * DIAG_MAX_GROUPS),
+                ("induced_current", C.c_double),
+                ("field_max", C.c_double), ("field_max_centroid", C.c_double * 2),
+                ("window_max", C.c_double), ("window_max_centroid", C.c_double * 2),
+                ("nodal_max", C.c_double * MAX_SPECIES),
+                ("field_max_cell", C.c_int32), ("window_max_cell", C.c_int32),
+                ("nodal_max_vertex", C.c_int32 * MAX_SPECIES),
+                ("finite", C.c_int32), ("pad_", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_int32, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_void_p)
 
@@ -187,6 +206,8 @@ _SIGNATURES = {
     "fedm_photo_update": (C.c_int, [_P, C.c_double, C.c_int, C.POINTER(C.c_int)]),
     "fedm_photo_get": (C.c_int, [_P, _D, _D]),
     "fedm_photo_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
+    "fedm_diag_setup": (C.c_int, [_P, _D, C.POINTER(C.c_int8), C.c_int]),
+    "fedm_diagnostics": (C.c_int, [_P, C.POINTER(DiagOpts), C.POINTER(DiagOut)]),
     "fedm_block_nnz": (C.c_int64, [_P]),
     "fedm_block_csr": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _D]),
     "fedm_jacobian_poisson_only": (C.c_int, [_P]),

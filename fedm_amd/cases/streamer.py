@@ -153,6 +153,19 @@ def device_problem(coords, cells, device=0, deck_model=None, photoionization=Non
                          dirichlet_dofs=dofs, dirichlet_vals=vals, device=device)
 
 
+def diagnostics(prob):
+    """The case's own diagnostics set-up on ``prob`` (``fedm_amd.functions.Discharge_diagnostics``): the head is the
+    field maximum among the cells nearer to the axis than the channel radius the refinement uses, psi = z / BOX (exact
+    for the planar gap), group 0 the cathode (tag 1), group 1 the anode (tag 2).  Returns the callable."""
+    from ..functions import Discharge_diagnostics
+    return Discharge_diagnostics(prob, boundary_tags=(1, 2), window=(0.0, CHANNEL[1], 0.0, BOX),
+                                 weighting_potential=prob.coords[:, 1] / BOX)
+
+
+DIAGNOSTIC_COLUMNS = ("t", "z_head", "E_max_axis", "E_max", "N_i", "N_e", "net_charge", "surface_charge_cathode",
+                      "surface_charge_anode", "current", "ni_max", "ne_max")
+
+
 # V(1,1): as effective as V(2,2) here at 75 % of the cost; Jacobi damping 0.85 instead of the
 # default 2/3: the same 6 Krylov steps per time step early in the run, 35 instead of 38 later
 # (tools/omega_sweep.py; 0.95: 40)
@@ -253,6 +266,19 @@ class Stepper:
         self.max_error[1] = self.max_error[0]
         self.steps += 1
         return self.t
+
+    def diagnose(self):
+        """One row of DIAGNOSTIC_COLUMNS from the device-resident state (no download); the set-up is made at the
+        first call."""
+        if getattr(self, "_diagnose", None) is None:
+            self._diagnose = diagnostics(self.prob)
+        d = self._diagnose()
+        if not d.finite:
+            raise RuntimeError("diagnostics: the state is not finite")
+        dens = d.density_max
+        return dict(zip(DIAGNOSTIC_COLUMNS, (
+            self.t, d.z_head, d.window_max, d.field_max, d.species_integral[0], d.species_integral[1], d.net_charge,
+            d.surface_charge[0], d.surface_charge[1], d.current, dens[0], dens[1])))
 
     def snapshot(self):
         """Checkpoint of the time loop: the three states stay on the device (fedm_state_snapshot), the

@@ -139,6 +139,46 @@ class Runner(streamer.Stepper):
                                f"{lm.n_owned} owned + {lm.n_ghost} ghost vertices in {halo_depth} layer(s) on rank {rank}, "
                                f"{len(lm.neighbours)} neighbours, transport {transport}")
 
+    def diagnose(self):
+        """Stepper.diagnose over all ranks: every rank's share from its device (``fedm_diagnostics`` weighs a cell by
+        its owned vertices' basis functions, so the shares add up), one all-reduce of the sums and one all-gather of
+        the maxima; the largest value wins, ties go to the lower global cell or vertex.  Every rank returns the same
+        row; ``cell`` / ``vertex`` entries are global ids."""
+        import torch
+        import torch.distributed as dist
+        if getattr(self, "_diagnose", None) is None:
+            self._diagnose = streamer.diagnostics(self.prob)
+        d, lm = self._diagnose(), self.lm
+        sums = torch.tensor([*d.species_integral, *d.group_sum, d.induced_current, 0.0 if d.finite else 1.0],
+                            dtype=torch.float64)
+        if dist.get_backend(self._group) == "nccl":
+            sums = sums.to(f"cuda:{torch.cuda.current_device()}")
+        dist.all_reduce(sums, group=self._group)
+        sums = sums.cpu().numpy()
+        if sums[-1] != 0.0:
+            raise RuntimeError("diagnostics: the state is not finite")
+
+        def mine(value, index, to_global, extra=None):
+            return (float(value), int(to_global[index]) if index >= 0 else -1, extra)
+        maxima = [mine(d.field_max, d.field_max_cell, lm.cell_global, d.field_max_centroid),
+                  mine(d.window_max, d.window_max_cell, lm.cell_global, d.window_max_centroid)]
+        maxima += [mine(d.nodal_max[s], int(d.nodal_max_vertex[s]), lm.vertex_global) for s in range(2)]
+        seen = [None] * self.world
+        dist.all_gather_object(seen, maxima, group=self._group)
+        best = []
+        for k in range(len(maxima)):
+            have = [r[k] for r in seen if r[k][1] >= 0]
+            best.append(min(have, key=lambda m: (-m[0], m[1])) if have else (0.0, -1, (0.0, 0.0)))
+        from ..physical_constants import elementary_charge, epsilon_0
+        Z = d.Z
+        row = dict(zip(streamer.DIAGNOSTIC_COLUMNS, (
+            self.t, best[1][2][1], best[1][0], best[0][0], sums[0], sums[1], float(Z[0] * sums[0] + Z[1] * sums[1]),
+            epsilon_0 * sums[2], epsilon_0 * sums[3], elementary_charge * sums[4],
+            float(np.exp(best[2][0])), float(np.exp(best[3][0])))))
+        row.update(field_max_cell=best[0][1], window_max_cell=best[1][1], ni_max_vertex=best[2][1],
+                   ne_max_vertex=best[3][1])
+        return row
+
     def initialise(self):
         """As Stepper.initialise, with the multigrid whose coarsest level spans all ranks."""
         from ..device import chebyshev_weights

@@ -74,6 +74,7 @@ struct Comm;
 struct GdPrep;
 struct FsTiles;
 struct Photo;
+struct Diag;
 
 // Optional in-run kernel timing with HIP events on the library's stream (bench.py roofline).
 // kinds: 0 assembly F+J, 1 Jacobian SpMV, 2 assembly F only, 3 multigrid V-cycle
@@ -310,6 +311,7 @@ struct Ctx {
     int seg_newton_its_hint = -1;     // Newton iterations of the previous converged species solve (its final check is residual-only)
     bool seg_jacobian_done = false;   // fedm_poisson_update has assembled a Jacobian itself (contexts whose assembly never sets const_planes_valid)
     Photo *photo = nullptr;   // photoionisation: Helmholtz sources into the targets' source tables (photo.hpp; fedm_photo_setup)
+    Diag *diag = nullptr;     // discharge diagnostics: psi, groups and the reductions' buffers (diag.hpp; allocated at first use)
 };
 
 // Indices of Ctx::path_stats, in the order fedm_solver_path_stats documents (include/fedm_hip.h)
@@ -427,6 +429,8 @@ void launch_potential_jacobi(Ctx &c, const double *r, double *z);   // z_phi = r
 void launch_pick_entries(Ctx &c, int which, double a, const double *x, double *y);
 // ---- photo.hip (photo.hpp has the rest) -------------------------------------------------------
 void photo_release(Ctx &c);
+// ---- diag.hip (diag.hpp has the rest) ---------------------------------------------------------
+void diag_release(Ctx &c);
 // ---- spmv.hip -------------------------------------------------------------------------------
 void launch_block_inverse(Ctx &c);                              // d_dinv from diagonal blocks
 void launch_row_scale(Ctx &c, double *d2, double *d_out);       // d^2 (and d, unless null) of the rows' equilibration

@@ -265,6 +265,82 @@ class NewtonReport:
     fnorm: float
 
 
+@dataclass
+class Diagnostics:
+    """One call of :meth:`DeviceProblem.diagnostics` (``fedm_diagnostics``, include/fedm_hip.h has the formulae).
+    Indices in the caller's numbering, -1 where there is none; lengths in m."""
+    species_integral: np.ndarray      # N_s = int n_s (2 pi r) dx per species: particles, or per metre of depth (planar)
+    group_sum: np.ndarray             # q_g: the unconstrained Poisson rows summed over vertex group g  [V m]
+    induced_current: float            # I_psi = sum_s Z_s int Gamma_s . (-grad psi)  [1/s]; 0 without a psi
+    field_max: float                  # max over the cells of |grad Phi|  [V/m]
+    field_max_cell: int
+    field_max_centroid: Tuple[float, float]
+    window_max: float                 # the same over the cells whose centroid lies in the window
+    window_max_cell: int
+    window_max_centroid: Tuple[float, float]
+    nodal_max: np.ndarray             # max_v u_s(v): bitwise a value of the state (ln n_s, or n_s when linear)
+    nodal_max_vertex: np.ndarray
+    finite: bool                      # False: a value met on the way was not finite; the rest is unspecified
+    Z: np.ndarray                     # the species' charge numbers
+    linear_representation: bool = False
+
+    @property
+    def net_charge(self):
+        """sum_s Z_s N_s in elementary charges."""
+        return float(np.dot(self.Z, self.species_integral))
+
+    @property
+    def surface_charge(self):
+        """eps0 q_g [C; C/m planar]: the charge on electrode g, BoundaryGradient in integrated form."""
+        return epsilon_0 * self.group_sum
+
+    @property
+    def current(self):
+        """e I_psi [A; A/m planar]."""
+        return elementary_charge * self.induced_current
+
+    @property
+    def density_max(self):
+        """the densities at the nodal maxima."""
+        return self.nodal_max.copy() if self.linear_representation else np.exp(self.nodal_max)
+
+    @property
+    def z_head(self):
+        """z of the window's field maximum: the head position when the window is the channel."""
+        return self.window_max_centroid[1]
+
+
+def boundary_vertex_groups(cells, facet_tags, n_vertices, dirichlet_vertices, boundary_tags):
+    """``int8 group[n_vertices]`` for :meth:`DeviceProblem.diagnostics_setup`: group ``g + 1`` holds the vertices of the
+    facets tagged ``boundary_tags[g]`` (facet i lies opposite vertex i) that are in ``dirichlet_vertices``.  Host only.
+    A vertex that would fall into two groups raises ``ValueError``."""
+    boundary_tags = [int(t) for t in boundary_tags]
+    if len(boundary_tags) > _lib.DIAG_MAX_GROUPS:
+        raise ValueError(f"at most {_lib.DIAG_MAX_GROUPS} vertex groups, got {len(boundary_tags)}")
+    group = np.zeros(int(n_vertices), dtype=np.int8)
+    if not boundary_tags:
+        return group
+    if facet_tags is None:
+        raise ValueError("vertex groups by boundary tag need the mesh's facet tags")
+    cells = np.asarray(cells).reshape(-1, 3)
+    tags = np.asarray(facet_tags).reshape(-1, 3)
+    fixed = np.zeros(int(n_vertices), dtype=bool)
+    fixed[np.asarray(dirichlet_vertices, dtype=np.int64)] = True
+    for g, tag in enumerate(boundary_tags):
+        member = np.zeros(int(n_vertices), dtype=bool)
+        for i in range(3):
+            hit = tags[:, i] == tag
+            member[cells[hit, (i + 1) % 3]] = True
+            member[cells[hit, (i + 2) % 3]] = True
+        member &= fixed
+        clash = np.nonzero(member & (group != 0))[0]
+        if clash.size:
+            raise ValueError(f"vertex {int(clash[0])} lies on boundary {tag} and on boundary "
+                             f"{boundary_tags[int(group[clash[0]]) - 1]}: a vertex belongs to one group")
+        group[member] = g + 1
+    return group
+
+
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
@@ -738,6 +814,74 @@ class DeviceProblem:
         out = (C.c_int64 * 8)()
         self._check(self.lib.fedm_photo_stats(self._h, out, 1 if reset else 0), "fedm_photo_stats")
         return dict(zip(self.PHOTO_STATS, (int(v) for v in out)))
+
+    # -- discharge diagnostics (csrc/diag.hip) ------------------------------------------
+    def dirichlet_vertices(self, component=None):
+        """The caller's vertices with a Dirichlet row of ``component`` (default: the last one, the potential)."""
+        comp = self.n_eq - 1 if component is None else int(component)
+        d = self._ddofs.astype(np.int64)
+        return np.unique(self._order[d[d % self.n_eq == comp] // self.n_eq])
+
+    def diagnostics_setup(self, weighting_potential=None, vertex_groups=None, n_groups=None):
+        """What :meth:`diagnostics` needs once (``fedm_diag_setup``), both in the caller's numbering:
+        ``weighting_potential``: nodal P1 psi ``[n_vertices]`` of the induced current (None: no current);
+        ``vertex_groups``: ``int8 [n_vertices]``, 0 or the group 1..8 whose Poisson rows are summed
+        (:func:`boundary_vertex_groups`; None: no groups); ``n_groups``: how many sums come back (default: the largest
+        group present).  Replaces an earlier set-up."""
+        if isinstance(self.model, GdModel):
+            raise RuntimeError("diagnostics: LFA models only (the LMEA family is not covered)")
+        psi = grp = None
+        n_groups = int(n_groups or 0)
+        if weighting_potential is not None:
+            psi = np.asarray(weighting_potential, dtype=np.float64).reshape(-1)
+            if psi.size != self.nv:
+                raise ValueError(f"weighting_potential must have {self.nv} entries, got {psi.size}")
+            psi = np.ascontiguousarray(psi[self._order])
+        if vertex_groups is not None:
+            grp = np.asarray(vertex_groups).reshape(-1)
+            if grp.size != self.nv:
+                raise ValueError(f"vertex_groups must have {self.nv} entries, got {grp.size}")
+            if grp.size and (grp.min() < 0 or grp.max() > _lib.DIAG_MAX_GROUPS):
+                raise ValueError(f"vertex_groups holds 0 or a group 1..{_lib.DIAG_MAX_GROUPS}")
+            n_groups = max(int(grp.max()) if grp.size else 0, n_groups)
+            if n_groups > _lib.DIAG_MAX_GROUPS:
+                raise ValueError(f"at most {_lib.DIAG_MAX_GROUPS} vertex groups")
+            grp = np.ascontiguousarray(grp[self._order], dtype=np.int8) if n_groups else None
+        else:
+            n_groups = 0
+        self._check(self.lib.fedm_diag_setup(self._h, _dp(psi) if psi is not None else None,
+                                             grp.ctypes.data_as(C.POINTER(C.c_int8)) if grp is not None else None,
+                                             n_groups), "fedm_diag_setup")
+        self._diag_groups = n_groups
+
+    def diagnostics(self, window=None, state="new"):
+        """The discharge's observables from the resident state (``fedm_diagnostics``): one pass over the cells, one
+        over the vertices, a read-back of a few hundred bytes.  ``window``: ``(r_lo, r_hi, z_lo, z_hi)`` of the second
+        field maximum (None: the whole mesh); ``state``: "new" or "old".  Returns a :class:`Diagnostics`."""
+        if isinstance(self.model, GdModel):
+            raise RuntimeError("diagnostics: LFA models only (the LMEA family is not covered)")
+        if state not in ("new", "old"):
+            raise ValueError('diagnostics: state is "new" or "old"')
+        opts = _lib.DiagOpts()
+        opts.state = 0 if state == "new" else 1
+        opts.r_lo, opts.r_hi, opts.z_lo, opts.z_hi = ((-np.inf, np.inf, -np.inf, np.inf) if window is None
+                                                      else [float(w) for w in window])
+        out = _lib.DiagOut()
+        self._check(self.lib.fedm_diagnostics(self._h, C.byref(opts), C.byref(out)), "fedm_diagnostics")
+        ns = self.model.n_species
+        vert = np.array(out.nodal_max_vertex[:ns], dtype=np.int64)
+        return Diagnostics(
+            species_integral=np.array(out.species_integral[:ns]),
+            group_sum=np.array(out.group_sum[:getattr(self, "_diag_groups", 0)]),
+            induced_current=float(out.induced_current),
+            field_max=float(out.field_max), field_max_cell=int(out.field_max_cell),
+            field_max_centroid=tuple(out.field_max_centroid),
+            window_max=float(out.window_max), window_max_cell=int(out.window_max_cell),
+            window_max_centroid=tuple(out.window_max_centroid),
+            nodal_max=np.array(out.nodal_max[:ns]),
+            nodal_max_vertex=np.where(vert >= 0, self._order[np.maximum(vert, 0)], -1),
+            finite=bool(out.finite), Z=np.asarray(self.model.Z, dtype=np.float64)[:ns],
+            linear_representation=not self.model.log_representation)
 
     # -- Problem.F / Problem.J ------------------------------------------------
     def residual(self, download=True):

@@ -944,6 +944,38 @@ def Photoionization_source(ionization, efficiency, A, lam, p_O2, zero_on=()):
     return src
 
 
+def Discharge_diagnostics(problem, boundary_tags=(), window=None, weighting_potential=None):
+    """Extension (the integrated form of ``BoundaryGradient``, fedm/functions.py, plus what a streamer run reports per
+    step): the observables of the device-resident state without downloading it.  ``problem``: a :class:`Problem` (or
+    its device problem) of an LFA model.  ``boundary_tags[g]``: the boundary whose surface charge is wanted -- group
+    ``g`` holds the vertices of the facets with that tag whose potential dof is a Dirichlet dof, and
+    ``surface_charge[g] = eps0 * sum of their unconstrained Poisson rows``; a vertex that would fall into two groups
+    raises ``ValueError``.  ``window``: ``(r_lo, r_hi, z_lo, z_hi)`` of the cells whose field maximum marks the head
+    (``z_head``).  ``weighting_potential``: nodal values [n_vertices] of the Shockley-Ramo psi of ``current`` (for a
+    planar gap ``z / d``).
+
+    Returns a callable: ``diag(state="new")`` gives a :class:`fedm_amd.device.Diagnostics` -- ``species_integral``,
+    ``net_charge``, ``field_max``, ``window_max``, ``z_head``, ``nodal_max``, ``density_max``, ``surface_charge``,
+    ``current``, ``finite`` -- from one pass over the cells on the device."""
+    from .device import GdModel, boundary_vertex_groups
+    dev = getattr(problem, "device", problem)
+    if isinstance(dev.model, GdModel):
+        raise ValueError("fedm.Discharge_diagnostics: LFA models only (the LMEA family is not covered)")
+    boundary_tags = list(boundary_tags)
+    groups = None
+    if boundary_tags:
+        if not dev.model.poisson:
+            raise ValueError("fedm.Discharge_diagnostics: surface charges need the Poisson equation")
+        groups = boundary_vertex_groups(dev.cells, dev._tags, dev.nv, dev.dirichlet_vertices(), boundary_tags)
+    if window is not None and len(window) != 4:
+        raise ValueError("fedm.Discharge_diagnostics: window is (r_lo, r_hi, z_lo, z_hi)")
+    dev.diagnostics_setup(weighting_potential=weighting_potential, vertex_groups=groups, n_groups=len(boundary_tags))
+
+    def diagnose(state="new"):
+        return dev.diagnostics(window=window, state=state)
+    return diagnose
+
+
 def semi_implicit_coefficients(dependences, mean_energy_new, mean_energy_old, coefficients,
                                coefficient_diffs):
     """fedm/functions.py:753-774: c + c' (mean_energy_new - mean_energy_old) for the entries that

@@ -243,7 +243,8 @@ const char *fedm_last_error(void);
  *    kind or argument outside its enum).  Additive under 10 (no struct changes size or offsets, no signature changes):
  *    fedm_ctx_create_tabulated; fedm_termsum.pad_, which had to be 0, is the table reference.  fedm_ctx_create_walls
  *    with fedm_wall_desc; FEDM_BC_FLUX_SOURCE, a value of bc_kind that the two older creators refuse.
- *    fedm_photo_setup with fedm_photo_desc and fedm_photo_hierarchy, fedm_photo_update, fedm_photo_get, fedm_photo_stats. */
+ *    fedm_photo_setup with fedm_photo_desc and fedm_photo_hierarchy, fedm_photo_update, fedm_photo_get, fedm_photo_stats.
+ *    fedm_diag_setup and fedm_diagnostics with fedm_diag_opts and fedm_diag. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -672,6 +673,63 @@ int fedm_debug_species_planes_check(fedm_ctx *ctx, double *out);
 
 /* |new - old + eps| / |old + eps| on one component        fedm/functions.py:1062-1064 */
 int fedm_field_error(fedm_ctx *ctx, int component, double *rel_err);
+
+/* ---- discharge diagnostics on the device ------------------------------------------------------
+ * What a streamer run reports per step (Bagheri et al. 2018: head position, maximal field, particle numbers) and the
+ * integrated form of BoundaryGradient (fedm/functions.py), from the resident state in one pass over the cells and one
+ * over the vertices; one small read-back per call.  LFA family (fedm_ctx_create, _tabulated, _walls; with or without
+ * photoionisation); densities n_s = exp(u_s), or u_s with linear_representation.  Throughout
+ *     W_q = qp_w[q] |det J| 2 pi w(x_q),   w = r (axisymmetric) or 1/(2 pi),
+ * the weight of the residual, at the model's own quadrature points; |E|, mu_s and D_s once per cell, as the element
+ * routines have them.  Every sum and maximum is reduced in a fixed order without floating-point atomics: two calls on
+ * the same state return the same bytes.
+ * Several ranks (n_owned_vertices < n_vertices): every quadrature term of an integral is multiplied by
+ * sum_(a owned) phi_a(x_q), so the ranks' shares add up to the global integral; group sums run over owned group
+ * vertices, field maxima over the cells with an owned vertex, nodal maxima over the owned vertices.  The call makes no
+ * reduction over the ranks.  On one GPU the factor is exactly 1. */
+#define FEDM_DIAG_MAX_GROUPS 8
+typedef struct {
+    int32_t state;                /* 0: u_new, 1: u_old                                                          */
+    int32_t pad_;
+    double r_lo, r_hi, z_lo, z_hi; /* closed window [r_lo, r_hi] x [z_lo, z_hi] of cell centroids [m]; -inf / +inf
+                                      bounds make it the whole mesh                                              */
+} fedm_diag_opts;
+typedef struct {
+    /* N_s = sum_cells sum_q W_q n_s(x_q): particles (axisymmetric) or particles per metre of depth (planar)      */
+    double species_integral[FEDM_MAX_SPECIES];
+    /* q_g = sum_(i in group g + 1) R_Phi,i with the unconstrained Poisson row
+     *   R_Phi,i = sum_cells sum_q W_q (grad Phi . grad phi_i - (e/eps0) sum_s Z_s n_s phi_i)   [V m; V planar]:
+     * eps0 q_g is the charge on the electrode [C; C/m planar]                                                    */
+    double group_sum[FEDM_DIAG_MAX_GROUPS];
+    /* I_psi = sum_s Z_s sum_cells sum_q W_q Gamma_s(x_q) . (-grad psi)  [1/s; 1/(s m) planar], Shockley-Ramo with the
+     * residual's own flux: Gamma_s = n_s (-D_s grad u_s + Z_s mu_s E), linear representation -D_s grad u_s +
+     * Z_s mu_s E u_s; drift_w in place of Z mu E where has_drift_w; 0 for 'reaction' species, and without a psi.
+     * e I_psi is the current [A]                                                                                 */
+    double induced_current;
+    /* max over the cells of |E| = |grad Phi| [V/m], its cell (the caller's index; lowest on a tie) and that cell's
+     * centroid (x_0 + x_1 + x_2)/3 [m]; 0 and -1 without a Poisson equation                                      */
+    double field_max, field_max_centroid[2];
+    /* the same over the cells whose centroid lies in the window; 0 and -1 when there is none                     */
+    double window_max, window_max_centroid[2];
+    /* max_v u_s(v), bitwise a value of the state (exp is the caller's), and its vertex in the CONTEXT's numbering
+     * (lowest on a tie; -1 when the rank owns no vertex)                                                         */
+    double nodal_max[FEDM_MAX_SPECIES];
+    int32_t field_max_cell, window_max_cell;
+    int32_t nodal_max_vertex[FEDM_MAX_SPECIES];
+    /* 0: a state value visited or a cell quantity formed was not finite; the other fields are then unspecified   */
+    int32_t finite;
+    int32_t pad_;
+} fedm_diag;
+/* psi: nodal P1 weighting potential [n_vertices] (dimensionless, 1 on the electrode whose current is asked for) or NULL;
+ * group: [n_vertices] values 0 (none) or 1..n_groups, or NULL with n_groups = 0; both in the context's numbering, copied.
+ * Replaces an earlier set-up.  Refused (-2, fedm_last_error says why): an LMEA context; n_groups outside
+ * 0..FEDM_DIAG_MAX_GROUPS or without an array; a group value outside 0..n_groups; groups in a model without a Poisson
+ * equation; a psi that is not finite. */
+int fedm_diag_setup(fedm_ctx *ctx, const double *psi, const int8_t *group, int n_groups);
+/* The quantities above of the chosen state; works without fedm_diag_setup (no psi, no groups).  The state is not
+ * touched.  Returns 0 also when out->finite is 0; the next call is unaffected.  Refused (-2): an LMEA context, a null
+ * argument, a state selector other than 0 or 1, a window bound that is NaN. */
+int fedm_diagnostics(fedm_ctx *ctx, const fedm_diag_opts *opts, fedm_diag *out);
 
 /* timed micro-benchmarks on the resident state (HIP events on the library's stream):
  * kind 0 = residual+Jacobian assembly, 1 = SpMV, 2 = residual only, 3 = one multigrid cycle on the

@@ -32,21 +32,10 @@ sz = prob.sizes()
 print(dict(vertices=msh.num_vertices(), cells=msh.num_cells(), dofs=prob.n, hmin=msh.hmin(), hmax=msh.hmax(),
            mesh_s=round(t_mesh, 1), setup_s=round(t_setup, 1), **sz), flush=True)
 
-x = msh.coords
-c = msh.cells
-a, b, d = x[c[:, 0]], x[c[:, 1]], x[c[:, 2]]
-det = (b[:, 0] - a[:, 0]) * (d[:, 1] - a[:, 1]) - (b[:, 1] - a[:, 1]) * (d[:, 0] - a[:, 0])
-G = np.stack([np.stack([b[:, 1] - d[:, 1], d[:, 0] - b[:, 0]], 1), np.stack([d[:, 1] - a[:, 1], a[:, 0] - d[:, 0]], 1),
-              np.stack([a[:, 1] - b[:, 1], b[:, 0] - a[:, 0]], 1)], 1) / det[:, None, None]
-zc = x[c].mean(axis=1)[:, 1]
-near_axis = x[c].mean(axis=1)[:, 0] < 2.0 * h_fine
-
-
-def field_stats(U):
-    E = -np.einsum("ca,cad->cd", U[c, 2], G)
-    Em = np.linalg.norm(E, axis=1)
-    k = np.argmax(np.where(near_axis, Em, 0.0))
-    return float(Em[k]), float(zc[k])
+# E_max_axis, z_head and the density maxima come from the device (fedm_diagnostics): the state stays there.  The head is
+# the field maximum among the cells whose centroid is nearer to the axis than two fine spacings.
+from fedm_amd.functions import Discharge_diagnostics
+diagnose = Discharge_diagnostics(prob, window=(-np.inf, np.nextafter(2.0 * h_fine, 0.0), -np.inf, np.inf))
 
 
 hist, t_run = [], time.time()
@@ -59,13 +48,14 @@ while st.t < T_final * (1 - 1e-9):
         status = f"stopped: {type(exc).__name__}: {exc}"
         break
     if st.steps % every == 0 or st.t >= T_final * (1 - 1e-9):
-        U = prob.get_state()
         rows = st.log_rows()
-        Emax, zhead = field_stats(U)
+        d = diagnose()
+        Emax, zhead = d.window_max, d.z_head
+        ne_max, ni_max = (float(v) if d.finite else float("nan") for v in (d.density_max[1], d.density_max[0]))
         span = max(st.steps - s0, 1)
         hist.append(dict(step=st.steps, t=st.t, dt=st.dt.time_step, newton_per_step=(st.newton_iterations - n0) / span,
                          gmres_per_step=(st.linear_iterations - l0) / span, attempts=len(rows) - a0,
-                         ne_max=float(np.exp(U[:, 1].max())), ni_max=float(np.exp(U[:, 0].max())),
+                         ne_max=ne_max, ni_max=ni_max,
                          E_max_axis=Emax, z_head=zhead, wall=round(time.time() - t_run, 2)))
         n0, l0, a0, s0 = st.newton_iterations, st.linear_iterations, len(rows), st.steps
         print(hist[-1], flush=True)
