@@ -21,6 +21,9 @@ E/N tables (an extension: `fedm.Coefficient_table`, looked up in the element ker
 `--diagnostics FILE` writes one row per accepted step (every N-th with `--diagnostics-every N`): head position, field
 maximum in the channel, particle numbers, net charge, electrode charges and the induced current, computed on the
 device without downloading the state (an extension: `fedm.Discharge_diagnostics`); off by default.
+`--fields LIST` writes derived fields (`E_norm,charge,rate:0,flux_z:1,...`) as VTU series at the output times (every
+N-th of them with `--fields-every N`), projected and blended to the output time on the device; `--axis-profile FILE`
+writes one row of `E_z` and `n_e` on `r = 0` per accepted step (an extension: `fedm.Field_output`); off by default.
 
     python examples/streamer_discharge.py --mesh-spacing 8e-6 --end 1.4e-8 --out streamer_output
 """
@@ -48,6 +51,7 @@ PHOTO_EFFICIENCY = 0.075 * 30.0 / (750.0 + 30.0)    # xi * p_q / (p + p_q)
 CHANNEL_RADIUS = 0.9e-3        # cells nearer to the axis than this mark the streamer's head (the mesh's finest region)
 DIAGNOSTICS_COLUMNS = ("t", "z_head", "E_max", "N_e", "N_i", "net_charge", "surface_charge_cathode",
                        "surface_charge_anode", "current")
+AXIS_POINTS = 64               # points of --axis-profile on r = 0, from the cathode to the anode
 SEED = "std::log(1e13+5e18*exp(-(pow(x[0], 2)+pow(x[1]-1e-2, 2))/pow(0.4e-3, 2)))"    # ions: background + seed
 BACKGROUND = "std::log(1e13)"                                                           # electrons
 
@@ -229,11 +233,14 @@ def quiet_stdout(quiet):
 
 def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_dir=None, output_dir=None,
          quiet=False, stop_before_device=None, coupling="coupled", model="benchmark_model", photoionization=False,
-         diagnostics=None, diagnostics_every=1):
+         diagnostics=None, diagnostics_every=1, fields=None, fields_every=1, axis_profile=None):
     """Runs the case; returns (state as (n_vertices, 3) array of ln n_i, ln n_e, Phi; error-log path).
     `model`: the deck folder under the input directory ("benchmark_model", "tabulated_model").
     `photoionization`: add the Helmholtz photoionisation source (coupled step only).
-    `diagnostics`: a file that receives DIAGNOSTICS_COLUMNS per accepted step (every `diagnostics_every`-th)."""
+    `diagnostics`: a file that receives DIAGNOSTICS_COLUMNS per accepted step (every `diagnostics_every`-th).
+    `fields`: names of derived fields (fedm.Field_output) written as VTU series under `<output>/fields/` at the output
+    times (every `fields_every`-th of them).  `axis_profile`: a file that receives, per accepted step, t followed by
+    E_z and then n_e at the AXIS_POINTS points of the axis (the first row holds their z)."""
     case = Case(deck=model) if end_time is None else Case(deck=model, end_time=end_time)
     fem.parameters["form_compiler"]["quadrature_degree"] = 2
     deck = read_deck(case, input_dir)
@@ -276,7 +283,23 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
                                               weighting_potential=mesh.coords[:, 1] / case.side)
         rows = open(diagnostics, "w")
         rows.write("# " + " ".join(DIAGNOSTICS_COLUMNS) + "\n")
-    accepted = 0
+    field_out = field_files = profile = profile_rows = None
+    if fields:
+        fields = [name.strip() for name in (fields.split(",") if isinstance(fields, str) else fields) if name.strip()]
+        field_out = fedm.Field_output(problem, fields, species_names=[r.lower() for r in case.roles])
+        field_files = file_io.output_files("pvd", "fields", [name.replace(":", "_") for name in fields])
+        for writer in field_files:
+            writer.mesh = mesh
+    if axis_profile is not None:
+        # its own set-up on the same problem: fedm_fields takes the requests per call, the points belong to the context
+        import numpy as np
+        z_axis = np.linspace(0.0, case.side, AXIS_POINTS)
+        profile = fedm.Field_output(problem, ["E_z", "density:electrons"], probes=np.column_stack([0.0 * z_axis, z_axis]),
+                                    species_names=[r.lower() for r in case.roles])
+        profile_rows = open(axis_profile, "w")
+        profile_rows.write("# t, E_z[%d], n_e[%d] on r = 0; first row: nan and the points' z twice\n" % (AXIS_POINTS, AXIS_POINTS))
+        profile_rows.write(" ".join(f"{x:.17g}" for x in [float("nan"), *z_axis, *z_axis]) + "\n")
+    accepted = outputs = 0
     newton = fedm.PETScSNESSolver()
     newton.parameters["relative_tolerance"] = case.newton_rtol
     newton.parameters["maximum_iterations"] = case.newton_max_it
@@ -312,11 +335,26 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
                    d.surface_charge[0], d.surface_charge[1], d.current)
             rows.write(" ".join(f"{x:.17g}" for x in row) + "\n")
             rows.flush()
+        if profile is not None:
+            p = profile()["probes"]
+            profile_rows.write(" ".join(f"{x:.17g}" for x in [t, *p[0], *p[1]]) + "\n")
+            profile_rows.flush()
+        if field_out is not None:
+            from fedm_amd.mesh_io import output_times
+            for t_out in output_times(t, window, stride, list(case.output_windows), list(case.output_windows))[0]:
+                outputs += 1
+                if outputs % max(1, int(fields_every)):
+                    continue
+                values = field_out(t_out, t_before, t)
+                for name, writer in zip(fields, field_files):
+                    writer.write(values[name], name, t_out)
         window, stride = file_io.file_output(t, t_before, window, stride, list(case.output_windows),
                                              list(case.output_windows), ["pvd"] * len(order), out_files, out_names,
                                              out_now, out_before)
     if rows is not None:
         rows.close()
+    if profile_rows is not None:
+        profile_rows.close()
     return problem.device.get_state(), file_io.files.error_file
 
 
@@ -336,8 +374,18 @@ if __name__ == "__main__":
     ap.add_argument("--diagnostics", metavar="FILE",
                     help="write t, z_head, E_max, N_e, N_i, net charge, electrode charges and current per accepted step")
     ap.add_argument("--diagnostics-every", type=int, default=1, metavar="N", help="... every N-th accepted step")
+    ap.add_argument("--fields", metavar="LIST",
+                    help="comma-separated derived fields written at the output times: E_norm, E_r, E_z, charge, "
+                         "density:electrons, rate:0, flux_r:1, flux_z:1, state:2")
+    ap.add_argument("--fields-every", type=int, default=1, metavar="N", help="... at every N-th output time")
+    ap.add_argument("--axis-profile", metavar="FILE", help="write E_z and n_e on r = 0 per accepted step")
+    ap.add_argument("--save-state", metavar="FILE", help="write the final state (n_vertices, 3) as a .npy file")
     a = ap.parse_args()
     state, log_path = main(cells=a.cells, mesh_spacing=a.mesh_spacing, mesh_file=a.mesh, end_time=a.end,
                            output_dir=a.out, coupling=a.coupling, model=a.model, photoionization=a.photoionization,
-                           diagnostics=a.diagnostics, diagnostics_every=a.diagnostics_every)
+                           diagnostics=a.diagnostics, diagnostics_every=a.diagnostics_every, fields=a.fields,
+                           fields_every=a.fields_every, axis_profile=a.axis_profile)
+    if a.save_state:
+        import numpy
+        numpy.save(a.save_state, state)
     print(open(log_path).read())

@@ -151,7 +151,19 @@ class DiagOut(C.Structure):
                 ("finite", C.c_int32), ("pad_", C.c_int32)]
 
 
-ALLREDUCE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_int32, C.c_void_p)
+FIELDS_MAX_REQ = 8
+
+
+class FieldReq(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("index", C.c_int32)]
+
+
+class FieldOpts(C.Structure):
+    _fields_ = [("num", C.c_double), ("den", C.c_double), ("projection", C.c_int32), ("max_it", C.c_int32),
+                ("rtol", C.c_double)]
+
+
+ALLREDUCE_FN =C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_int32, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_void_p)
 
 # FEDM_HIP_LIB points at another build of the same C ABI (kernel experiments, system installs)
@@ -208,6 +220,10 @@ _SIGNATURES = {
     "fedm_photo_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
     "fedm_diag_setup": (C.c_int, [_P, _D, C.POINTER(C.c_int8), C.c_int]),
     "fedm_diagnostics": (C.c_int, [_P, C.POINTER(DiagOpts), C.POINTER(DiagOut)]),
+    "fedm_fields_setup": (C.c_int, [_P, C.POINTER(Csr)]),
+    "fedm_probe_setup": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), _D]),
+    "fedm_fields": (C.c_int, [_P, C.POINTER(FieldOpts), C.c_int, C.POINTER(FieldReq), _D, _D, C.POINTER(C.c_int32),
+                              C.POINTER(C.c_int32)]),
     "fedm_block_nnz": (C.c_int64, [_P]),
     "fedm_block_csr": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _D]),
     "fedm_jacobian_poisson_only": (C.c_int, [_P]),

@@ -162,6 +162,8 @@ def diagnostics(prob):
                                  weighting_potential=prob.coords[:, 1] / BOX)
 
 
+SPECIES_NAMES = ("ions", "electrons")        # the model's species order (fedm-streamer.py:60)
+
 DIAGNOSTIC_COLUMNS = ("t", "z_head", "E_max_axis", "E_max", "N_i", "N_e", "net_charge", "surface_charge_cathode",
                       "surface_charge_anode", "current", "ni_max", "ne_max")
 
@@ -279,6 +281,18 @@ class Stepper:
         return dict(zip(DIAGNOSTIC_COLUMNS, (
             self.t, d.z_head, d.window_max, d.field_max, d.species_integral[0], d.species_integral[1], d.net_charge,
             d.surface_charge[0], d.surface_charge[1], d.current, dens[0], dens[1])))
+
+    def fields(self, names, t_out=None, t_old=None, probes=None, projection="lumped"):
+        """Derived nodal fields of the device-resident state (``fedm_amd.functions.Field_output``; no download): a dict
+        name -> nodal array, blended to ``t_out`` between ``t_old`` and the current time when both are given.
+        ``probes``: points [n, 2], evaluated as well (``"probes"``).  The set-up is made at the first call and again
+        when the names, the points or the projection change."""
+        key = (tuple(names), None if probes is None else np.asarray(probes, dtype=np.float64).tobytes(), projection)
+        if getattr(self, "_fields_key", None) != key:
+            self._fields = self.ff.Field_output(self.prob, list(names), probes=probes, projection=projection,
+                                                species_names=SPECIES_NAMES)
+            self._fields_key = key
+        return self._fields(t_out, t_old, None if t_out is None else self.t)
 
     def snapshot(self):
         """Checkpoint of the time loop: the three states stay on the device (fedm_state_snapshot), the

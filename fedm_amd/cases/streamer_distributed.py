@@ -63,6 +63,7 @@ class Runner(streamer.Stepper):
             raise ValueError(f"FEDM_PARTITIONER={self.partitioner}: 'rcb' or 'graph'")
         lm = partition.local_mesh(gmesh.coords, gmesh.cells, part, rank, depth=halo_depth)
         self.lm, self.world, self.rank = lm, world, rank
+        self._gmesh = gmesh          # (Runner.fields glues the ranks' values and interpolates probes on it)
         # (True with one rank: the several-GPU solver -- distributed finest level, replicated coarse
         # levels, their all-reduces -- on a single rank: how the tests reach that code with RCCL)
         self.distributed_multigrid = world > 1 if distributed_multigrid is None else bool(distributed_multigrid)
@@ -178,6 +179,34 @@ class Runner(streamer.Stepper):
         row.update(field_max_cell=best[0][1], window_max_cell=best[1][1], ni_max_vertex=best[2][1],
                    ne_max_vertex=best[3][1])
         return row
+
+    def fields(self, names, t_out=None, t_old=None, probes=None, projection="lumped"):
+        """Stepper.fields over all ranks: every rank's owned values from its device (pointwise kinds and the lumped
+        projection are exact on owned vertices without communication), gathered on rank 0 in the global numbering;
+        ``probes``: points [n, 2] of the global mesh, interpolated on rank 0 on the host (the device's probes and the
+        consistent projection do not cross ranks).  Rank 0 returns the dict, the others None."""
+        import torch.distributed as dist
+        if projection != "lumped":
+            raise ValueError("Runner.fields: the lumped projection only (the consistent one does not cross ranks)")
+        names, lm = list(names), self.lm
+        res = self.prob.fields(names, t_out=t_out, t_old=t_old, t=None if t_out is None else self.t,
+                               species_names=streamer.SPECIES_NAMES)
+        mine = (lm.vertex_global[:lm.n_owned], res.nodal[:, :lm.n_owned], res.finite)
+        seen = [None] * self.world if self.rank == 0 else None
+        dist.gather_object(mine, seen, dst=0, group=self._group)
+        if self.rank != 0:
+            return None
+        glued = np.zeros((len(names), self._gmesh.coords.shape[0]))
+        for gids, values, _ in seen:
+            glued[:, gids] = values
+        out = {name: glued[k] for k, name in enumerate(names)}
+        if probes is not None:
+            from .. import field_output
+            cell, w = field_output.locate_points(self._gmesh.coords, self._gmesh.cells, probes)
+            at = self._gmesh.cells[cell]
+            out["probes"] = np.stack([(w * g[at]).sum(axis=1) for g in glued])
+        out["finite"] = all(f for _, _, f in seen)
+        return out
 
     def initialise(self):
         """As Stepper.initialise, with the multigrid whose coarsest level spans all ranks."""

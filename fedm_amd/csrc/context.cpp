@@ -758,6 +758,7 @@ void fedm_ctx_destroy(fedm_ctx *h) {
     gd_prep_release(c);
     photo_release(c);
     diag_release(c);
+    fields_release(c);
     fs_tiles_release(c);
     for (auto &e : c.prof.ev) hipEventDestroy(e);
     iter_graphs_clear(c);

@@ -75,6 +75,7 @@ struct GdPrep;
 struct FsTiles;
 struct Photo;
 struct Diag;
+struct Fields;
 
 // Optional in-run kernel timing with HIP events on the library's stream (bench.py roofline).
 // kinds: 0 assembly F+J, 1 Jacobian SpMV, 2 assembly F only, 3 multigrid V-cycle
@@ -312,6 +313,7 @@ struct Ctx {
     bool seg_jacobian_done = false;   // fedm_poisson_update has assembled a Jacobian itself (contexts whose assembly never sets const_planes_valid)
     Photo *photo = nullptr;   // photoionisation: Helmholtz sources into the targets' source tables (photo.hpp; fedm_photo_setup)
     Diag *diag = nullptr;     // discharge diagnostics: psi, groups and the reductions' buffers (diag.hpp; allocated at first use)
+    Fields *fields = nullptr; // field output: the vertex lists, the lumped mass, the results' buffers (fields.hpp; fedm_fields_setup)
 };
 
 // Indices of Ctx::path_stats, in the order fedm_solver_path_stats documents (include/fedm_hip.h)
@@ -431,6 +433,8 @@ void launch_pick_entries(Ctx &c, int which, double a, const double *x, double *y
 void photo_release(Ctx &c);
 // ---- diag.hip (diag.hpp has the rest) ---------------------------------------------------------
 void diag_release(Ctx &c);
+// ---- fields.hip (fields.hpp has the rest) -----------------------------------------------------
+void fields_release(Ctx &c);
 // ---- spmv.hip -------------------------------------------------------------------------------
 void launch_block_inverse(Ctx &c);                              // d_dinv from diagonal blocks
 void launch_row_scale(Ctx &c, double *d2, double *d_out);       // d^2 (and d, unless null) of the rows' equilibration

@@ -310,6 +310,22 @@ class Diagnostics:
         return self.window_max_centroid[1]
 
 
+@dataclass
+class FieldValues:
+    """One call of :meth:`DeviceProblem.fields` (``fedm_fields``): ``nodal[k]`` the nodal values of request ``k`` in the
+    caller's vertex order (None with ``nodal=False``), ``probes[k]`` its values at the probe points (None without
+    ``probes=True``), ``finite`` False when a state value or a result was not finite, ``cg_iterations[k]`` the
+    conjugate-gradient steps of a consistent projection (0 otherwise)."""
+    names: list
+    nodal: Optional[np.ndarray]
+    probes: Optional[np.ndarray]
+    finite: bool
+    cg_iterations: np.ndarray
+
+    def __getitem__(self, name):
+        return self.nodal[self.names.index(name)]
+
+
 def boundary_vertex_groups(cells, facet_tags, n_vertices, dirichlet_vertices, boundary_tags):
     """``int8 group[n_vertices]`` for :meth:`DeviceProblem.diagnostics_setup`: group ``g + 1`` holds the vertices of the
     facets tagged ``boundary_tags[g]`` (facet i lies opposite vertex i) that are in ``dirichlet_vertices``.  Host only.
@@ -882,6 +898,91 @@ class DeviceProblem:
             nodal_max_vertex=np.where(vert >= 0, self._order[np.maximum(vert, 0)], -1),
             finite=bool(out.finite), Z=np.asarray(self.model.Z, dtype=np.float64)[:ns],
             linear_representation=not self.model.log_representation)
+
+    # -- field output (csrc/fields.hip) ---------------------------------------------------
+    def fields_setup(self, consistent=False):
+        """What :meth:`fields` needs once (``fedm_fields_setup``): the vertex lists, the lumped mass and the results'
+        buffers on the device; ``consistent``: the P1 mass matrix of the plain measure as well, assembled here once (the
+        way ``photo.install`` assembles its operators), for ``projection="consistent"``.  Replaces an earlier set-up and
+        drops its probe points."""
+        if isinstance(self.model, GdModel):
+            raise RuntimeError("fields: LFA models only (the LMEA family is not covered)")
+        mass = None
+        if consistent:
+            from . import amg, field_output
+            keep = []
+            mass = amg._csr_struct(field_output.mass_matrix(self._coords_dev, self._cells_dev), keep)
+        self._check(self.lib.fedm_fields_setup(self._h, C.byref(mass) if mass is not None else None), "fedm_fields_setup")
+        self._fields_ready, self._n_probe_points = True, 0
+
+    def probe_setup(self, points):
+        """Probe points ``[n, 2]`` for :meth:`fields` (``fedm_probe_setup``): the cell that contains each point and its
+        barycentric weights there are found here (``field_output.locate_points``: ties on an edge or a vertex go to the
+        lowest cell index; a point outside the mesh is a ``ValueError`` naming it).  Returns ``(cells, weights)``."""
+        from . import field_output
+        if not getattr(self, "_fields_ready", False):
+            self.fields_setup()
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+        cell, w = field_output.locate_points(self.coords, self.cells, pts)
+        verts = np.ascontiguousarray(self._inv[self.cells[cell]], dtype=np.int32)
+        w = np.ascontiguousarray(w)
+        self._check(self.lib.fedm_probe_setup(self._h, int(pts.shape[0]), verts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              _dp(w)), "fedm_probe_setup")
+        self._n_probe_points = int(pts.shape[0])
+        return cell, w
+
+    def fields(self, requests, t_out=None, t_old=None, t=None, projection="lumped", rtol=1e-10, nodal=True,
+               probes=False, max_it=10000, species_names=None):
+        """Derived fields of the resident state (``fedm_fields``; include/fedm_hip.h has the definitions).
+        ``requests``: up to 8 names (``"E_norm"``, ``"E_r"``, ``"E_z"``, ``"charge"``, ``"state:e"``, ``"density:s"``,
+        ``"rate:j"``, ``"flux_r:s"``, ``"flux_z:s"``) or ``(kind, index)`` pairs.  With ``t_out``, ``t_old`` and ``t``
+        the result is ``X(u_old) + (t_out - t_old) (X(u_new) - X(u_old)) / (t - t_old)``, ``file_output``'s blend;
+        without them ``X(u_new)``.  ``projection``: "lumped" or "consistent" (after ``fields_setup(consistent=True)``;
+        conjugate gradients to ``rtol``).  Returns a :class:`FieldValues`: ``nodal [n_req, n_vertices]`` in the caller's
+        vertex order (ghost entries 0) unless ``nodal=False``, ``probes [n_req, n_points]`` with ``probes=True``."""
+        from . import field_output
+        if isinstance(self.model, GdModel):
+            raise RuntimeError("fields: LFA models only (the LMEA family is not covered)")
+        if not getattr(self, "_fields_ready", False):
+            self.fields_setup(consistent=projection == "consistent")
+        if projection not in ("lumped", "consistent"):
+            raise ValueError('fields: projection is "lumped" or "consistent"')
+        names = species_names if species_names is not None else getattr(self, "species_names", None)
+        pairs = [field_output.parse_request(r, self.model.n_species, self.n_eq, len(self.model.reactions), names)
+                 for r in requests]
+        if not 1 <= len(pairs) <= _lib.FIELDS_MAX_REQ:
+            raise ValueError(f"fields: 1 to {_lib.FIELDS_MAX_REQ} requests a call, got {len(pairs)}")
+        req = (_lib.FieldReq * len(pairs))()
+        for k, (kind, index) in enumerate(pairs):
+            req[k].kind, req[k].index = kind, index
+        opts = _lib.FieldOpts()
+        if t_out is None:
+            opts.num = opts.den = 1.0
+        else:
+            if t_old is None or t is None:
+                raise ValueError("fields: t_out goes with t_old and t")
+            opts.num, opts.den = float(t_out) - float(t_old), float(t) - float(t_old)
+        opts.projection, opts.max_it, opts.rtol = (1 if projection == "consistent" else 0), int(max_it), float(rtol)
+        n_points = getattr(self, "_n_probe_points", 0)
+        if probes and not n_points:
+            raise RuntimeError("fields: probes=True needs probe_setup(points) first")
+        out_n = np.empty((len(pairs), self.nv)) if nodal else None
+        out_p = np.empty((len(pairs), n_points)) if probes else None
+        finite = C.c_int32(0)
+        its = (C.c_int32 * len(pairs))()
+        import time
+        t0 = time.perf_counter()
+        rc = self.lib.fedm_fields(self._h, C.byref(opts), len(pairs), req, _dp(out_n) if nodal else None,
+                                  _dp(out_p) if probes else None, C.byref(finite), its)
+        self.last_fields_call_seconds = time.perf_counter() - t0     # (the library's share; the rest is the reordering here)
+        if rc == 3:
+            raise RuntimeError(f"fedm_fields: conjugate gradients stopped at max_it = {max_it} "
+                               f"(iterations per request {[int(v) for v in its]})")
+        self._check(rc, "fedm_fields")
+        return FieldValues(names=[r if isinstance(r, str) else tuple(r) for r in requests],
+                           # (np.take along the rows: five times faster than out_n[:, self._inv] at 341 k vertices)
+                           nodal=np.take(out_n, self._inv, axis=1) if nodal else None, probes=out_p,
+                           finite=bool(finite.value), cg_iterations=np.array([int(v) for v in its]))
 
     # -- Problem.F / Problem.J ------------------------------------------------
     def residual(self, download=True):

@@ -976,6 +976,39 @@ def Discharge_diagnostics(problem, boundary_tags=(), window=None, weighting_pote
     return diagnose
 
 
+def Field_output(problem, fields, probes=None, projection="lumped", species_names=None):
+    """Extension (what the reference's scripts do with ``project(...)`` and ``file_output``, fedm-gd.py:309,432): derived
+    nodal fields of the device-resident state, blended to an output time, without downloading the state.  ``problem``:
+    a :class:`Problem` (or its device problem) of an LFA model.  ``fields``: up to 8 names -- ``"E_norm"``, ``"E_r"``,
+    ``"E_z"`` (the cell-constant field, projected), ``"charge"``, ``"density:s"``, ``"state:e"`` (pointwise),
+    ``"rate:j"``, ``"flux_r:s"``, ``"flux_z:s"`` (projected); ``s`` an index or one of ``species_names``.  ``probes``:
+    points ``[n, 2]`` at which every field is interpolated as well.  ``projection``: "lumped" or "consistent".
+
+    Returns a callable: ``out(t_out=None, t_old=None, t=None)`` gives a dict name -> nodal array [n_vertices] at
+    ``t_out`` (``file_output``'s blend of the old and the new state; without times the new state), with
+    ``"probes"`` -> ``[n_fields, n_points]`` when points were given and ``"finite"``."""
+    from .device import GdModel
+    dev = getattr(problem, "device", problem)
+    if isinstance(dev.model, GdModel):
+        raise ValueError("fedm.Field_output: LFA models only (the LMEA family is not covered)")
+    fields = list(fields)
+    if isinstance(projection, str) and projection not in ("lumped", "consistent"):
+        raise ValueError('fedm.Field_output: projection is "lumped" or "consistent"')
+    dev.fields_setup(consistent=projection == "consistent")
+    if probes is not None:
+        dev.probe_setup(probes)
+
+    def output(t_out=None, t_old=None, t=None):
+        res = dev.fields(fields, t_out=t_out, t_old=t_old, t=t, projection=projection, probes=probes is not None,
+                         species_names=species_names)
+        out = {name: res.nodal[k] for k, name in enumerate(fields)}
+        if probes is not None:
+            out["probes"] = res.probes
+        out["finite"] = res.finite
+        return out
+    return output
+
+
 def semi_implicit_coefficients(dependences, mean_energy_new, mean_energy_old, coefficients,
                                coefficient_diffs):
     """fedm/functions.py:753-774: c + c' (mean_energy_new - mean_energy_old) for the entries that

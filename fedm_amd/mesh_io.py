@@ -221,6 +221,25 @@ def read_checkpoint(path, key):
     return coords, cells, fields
 
 
+def output_times(t, t_out, step, t_out_list, step_list):
+    """The output times :func:`file_output` writes when it is called with these arguments, in order, and the
+    ``(t_out, step)`` it returns: its stepping without its writing (for output that is formed elsewhere, such as the
+    device's fields)."""
+    if t > max(t_out_list):
+        index = len(t_out_list) - 1
+    else:
+        index = next(x for x, val in enumerate(t_out_list) if val > t)
+    times = []
+    while t_out <= t:
+        times.append(t_out)
+        if t_out >= 0.999 * t_out_list[index - 1] and t_out < 0.999 * t_out_list[index]:
+            step = step_list[index - 1]
+        elif t_out >= 0.999 * t_out_list[index]:
+            step = step_list[index]
+        t_out += step
+    return times, (t_out, step)
+
+
 def file_output(t, t_old, t_out, step, t_out_list, step_list, file_type, output_file_list,
                 particle_name, u_old, u_old1, unit="s"):
     """Linear interpolation of the solution to the output times, fedm/file_io.py:538-616: same

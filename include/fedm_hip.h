@@ -244,7 +244,8 @@ const char *fedm_last_error(void);
  *    fedm_ctx_create_tabulated; fedm_termsum.pad_, which had to be 0, is the table reference.  fedm_ctx_create_walls
  *    with fedm_wall_desc; FEDM_BC_FLUX_SOURCE, a value of bc_kind that the two older creators refuse.
  *    fedm_photo_setup with fedm_photo_desc and fedm_photo_hierarchy, fedm_photo_update, fedm_photo_get, fedm_photo_stats.
- *    fedm_diag_setup and fedm_diagnostics with fedm_diag_opts and fedm_diag. */
+ *    fedm_diag_setup and fedm_diagnostics with fedm_diag_opts and fedm_diag.
+ *    fedm_fields_setup, fedm_probe_setup and fedm_fields with fedm_field_req and fedm_field_opts. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -730,6 +731,75 @@ int fedm_diag_setup(fedm_ctx *ctx, const double *psi, const int8_t *group, int n
  * touched.  Returns 0 also when out->finite is 0; the next call is unaffected.  Refused (-2): an LMEA context, a null
  * argument, a state selector other than 0 or 1, a window bound that is NaN. */
 int fedm_diagnostics(fedm_ctx *ctx, const fedm_diag_opts *opts, fedm_diag *out);
+
+/* ---- field output on the device ---------------------------------------------------------------
+ * Derived nodal fields and point probes from the resident state, blended in time the way file_output blends
+ * (fedm/file_io.py:538-616), without downloading the state.  LFA family (fedm_ctx_create, _tabulated, _walls; with or
+ * without photoionisation), logarithmic or linear representation.  Kinds, in the caller's units:
+ *   STATE    index = equation e   u_e(v): a value of the state, no arithmetic but the blend
+ *   DENSITY  index = species s    exp(u_s(v)), or u_s(v) with linear_representation
+ *   CHARGE   -                    e sum_s Z_s n_s(v), e = FEDM_ELEMENTARY_CHARGE, species in ascending order
+ *   E_R, E_Z -                    the cell-constant -dPhi/dr, -dPhi/dz, projected
+ *   E_NORM   -                    the cell-constant |E| = |grad Phi|, projected
+ *   RATE     index = reaction j   R_j = k_j(|E|) prod_i n_i^p_ji, k_j once per cell, the densities at the quadrature
+ *                                 points (the source photoionisation integrates), projected
+ *   FLUX_R, FLUX_Z  index = species s   the residual's own flux n_s (-D_s grad u_s + Z_s mu_s E), linear
+ *                                 representation -D_s grad u_s + Z_s mu_s E u_s; drift_w in place of Z mu E where
+ *                                 has_drift_w; 0 for 'reaction' species (what fedm_diagnostics integrates), projected
+ * The first three are pointwise.  Projection uses the plain measure dx (no r weight, no 2 pi; DOLFIN's project):
+ *   b_v = sum_(c with v) sum_q qp_w[q] |det J_c| f(x_q) phi_v(x_q)   at the model's own quadrature points,
+ *   m_v = sum_(c with v) |det J_c| / 6,
+ *   lumped X_v = b_v / m_v;  consistent: M X = b with the P1 mass matrix of fedm_fields_setup, conjugate gradients with
+ *   Jacobi from X = 0 until the recurrence's |r|_2 <= rtol |b|_2.
+ * b_v and m_v add their cells' entries in ascending (cell, corner) order and nothing adds with floating-point atomics:
+ * two calls on one state return the same bytes.  Without a Poisson equation the coefficients are taken at |E| = 1, as
+ * the element routines take them.
+ * Several ranks (n_owned_vertices < n_vertices): every cell of an owned vertex is local, so pointwise kinds and the
+ * lumped projection are exact on the owned vertices without communication; ghost entries are written as 0.  The
+ * consistent projection and probes are refused there. */
+#define FEDM_FIELD_STATE 0
+#define FEDM_FIELD_DENSITY 1
+#define FEDM_FIELD_CHARGE 2
+#define FEDM_FIELD_E_R 3
+#define FEDM_FIELD_E_Z 4
+#define FEDM_FIELD_E_NORM 5
+#define FEDM_FIELD_RATE 6
+#define FEDM_FIELD_FLUX_R 7
+#define FEDM_FIELD_FLUX_Z 8
+#define FEDM_FIELDS_MAX_REQ 8
+#define FEDM_ELEMENTARY_CHARGE 1.6021766208e-19   /* fedm/physical_constants.py:5 */
+typedef struct {
+    int32_t kind, index;
+} fedm_field_req;
+typedef struct {
+    double num, den;      /* out = X(u_old) + num * (X(u_new) - X(u_old)) / den, the expression of file_output (num =
+                             t_out - t_old, den = t - t_old), rounded operation by operation; num == den: X(u_new)
+                             alone, num == 0: X(u_old) alone (one evaluation, no arithmetic)                      */
+    int32_t projection;   /* 0 lumped, 1 consistent                                                                */
+    int32_t max_it;       /* conjugate-gradient steps at the most (consistent)                                     */
+    double rtol;
+} fedm_field_opts;
+/* Once per context; replaces an earlier set-up (and drops its probes).  mass: the P1 mass matrix of the plain measure
+ * in the context's numbering, n_vertices x n_vertices, copied; NULL: lumped projection only.  Allocates every buffer
+ * fedm_fields uses.  Refused (-2): an LMEA context; a mass matrix of another size, or on a context with ghosts. */
+int fedm_fields_setup(fedm_ctx *ctx, const fedm_csr *mass);
+/* n_points points, each three vertices of the context's numbering and three weights: probe = sum_a w_a X[v_a], added
+ * in that order.  Replaces earlier points; n_points = 0 drops them.  Refused (-2): before fedm_fields_setup; a context
+ * with ghosts; a vertex out of range; a weight that is not finite. */
+int fedm_probe_setup(fedm_ctx *ctx, int n_points, const int32_t *vertices, const double *weights);
+/* n_req <= FEDM_FIELDS_MAX_REQ fields of the resident state.  nodal: [n_req][n_vertices] in the context's numbering, or
+ * NULL; probes: [n_req][n_points], or NULL (with nodal NULL only n_req * n_points doubles come back); finite: 0 when a
+ * state value of an owned vertex or a result was not finite (the call still returns 0, the next call is unaffected);
+ * cg_iterations: [n_req] or NULL, 0 for requests without a solve.  Allocates nothing; the lumped and pointwise kinds
+ * synchronise once, for the read-back (a consistent projection reads its reductions as it goes).
+ * Returns FEDM_DIVERGED_LINEAR when a consistent projection stopped at max_it.  Refused (-2, fedm_last_error names the
+ * cause): before fedm_fields_setup; an LMEA context; n_req outside 1..FEDM_FIELDS_MAX_REQ; an unknown kind; an index out
+ * of range; E_R, E_Z, E_NORM without a Poisson equation, and FLUX_* of a drift-diffusion species without drift_w there
+ * (a species with drift_w, or a diffusion-reaction species, has its flux as fedm_diagnostics has it); projection other
+ * than 0 or 1, 1 without a mass matrix or with ghosts, 1 with max_it < 1 or rtol <= 0; den == 0; a num, den or rtol that
+ * is not finite; probes asked for without points. */
+int fedm_fields(fedm_ctx *ctx, const fedm_field_opts *opts, int n_req, const fedm_field_req *req, double *nodal,
+                double *probes, int32_t *finite, int32_t *cg_iterations);
 
 /* timed micro-benchmarks on the resident state (HIP events on the library's stream):
  * kind 0 = residual+Jacobian assembly, 1 = SpMV, 2 = residual only, 3 = one multigrid cycle on the
