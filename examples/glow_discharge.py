@@ -16,7 +16,13 @@ Newton solves run on the device.  `fedm_amd.cases.glow_discharge.Case` is the va
 whole per-step pipeline on the GPU.
 
     python examples/glow_discharge.py gd_output
+
+`--balance FILE` writes one row per accepted step (every N-th with `--balance-every N`): time, the contents, the
+conduction currents into the two electrodes, Joule power, collision loss, the imbalances of the energy and particle
+balances and the Shockley-Ramo current with psi = z / gap, all formed on the device without downloading the state (an
+extension: `fedm.Discharge_balance`); off by default.
 """
+import argparse
 import contextlib
 import io
 import sys
@@ -222,8 +228,20 @@ def coupled_form(dis, deck, mesh, r, dt, dt_before, wall_tags):
     return form
 
 
+def balance_columns(names):
+    """The columns of a `--balance` row for the species `names` (the gas first; its place is the energy's)."""
+    what = ["energy"] + list(names[1:])
+    return (["t"] + [f"content_{n}" for n in what] + ["current_powered", "current_grounded", "power_joule",
+            "collision_loss"] + [f"imbalance_{n}" for n in what] + ["current_ramo"])
+
+
+def balance_row(t, b):
+    """One `--balance` row from a `fedm_amd.device.Balance`: SI units, currents in A, power in W, the loss in eV/s."""
+    return [t, *b.content, b.wall_current[0], b.wall_current[1], b.power_joule, b.collision_loss, *b.imbalance, b.current]
+
+
 def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", quiet=True, ttol=2e-3,
-         stop_before_device=None):
+         stop_before_device=None, balance=None, balance_every=1):
     fem.parameters["form_compiler"]["quadrature_degree"] = 4
     deck = read_deck(input_dir)
     file_io.files.output_folder_path = Path(output_dir)
@@ -273,6 +291,11 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
     out_names = ["Phi"] + deck["file_names"][1:]
     out_now, out_before = [dis.phi] + dis.dens_now[1:], [dis.phi_before] + dis.dens_before[1:]
     window, stride = OUTPUT_WINDOWS[0], OUTPUT_STRIDES[0]
+    balance_of, rows = None, None
+    if balance is not None:
+        balance_of = fedm.Discharge_balance(problem, boundary_tags=(1, 2), weighting_potential=problem.device.coords[:, 1] / GAP)
+        rows = open(balance, "w")
+        rows.write("# " + " ".join(balance_columns(deck["file_names"])) + "\n")
     step_errors, recent_errors, steps = [0.0] * (ns + 1), [1] * 3, 0
     while t < T_final:
         t_before = t
@@ -289,6 +312,10 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
                                      dis.split, step_errors, file_io.files.error_file, recent_errors, ttol,
                                      dt_limits["dt_min"], time_dependent_arguments=[voltage], approximation="LMEA")
         file_io.log("time", file_io.files.model_log, t)
+        if balance_of is not None and steps % max(1, int(balance_every)) == 0:
+            # (here, before anything of the next step reaches the device: the balance of the residual just solved)
+            rows.write(" ".join(repr(float(v)) for v in balance_row(t, balance_of())) + "\n")
+            rows.flush()
         dis.energy.vector()[:] = np.exp(dis.w_now.vector()[:] - dis.dens_now[ns - 1].vector()[:])
         window, stride = file_io.file_output(t, t_before, window, stride, OUTPUT_WINDOWS, OUTPUT_STRIDES,
                                              ["pvd"] + ["xdmf"] * (ns - 1), out_files, out_names, out_now, out_before,
@@ -297,10 +324,17 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
         dt.time_step = fedm.adaptive_timestep(dt.time_step, recent_errors, ttol, **dt_limits)
         recent_errors[1:] = recent_errors[:2]
         steps += 1
+    if rows is not None:
+        rows.close()
     return dict(t=t, steps=steps, output=str(file_io.files.output_folder_path), species=deck["file_names"],
                 error_file=str(file_io.files.error_file), problem=problem)
 
 
 if __name__ == "__main__":
-    result = main(output_dir=sys.argv[1] if len(sys.argv) > 1 else "gd_output", quiet=False)
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("out", nargs="?", default="gd_output")
+    ap.add_argument("--balance", metavar="FILE", help="write the particle and energy balance per accepted step")
+    ap.add_argument("--balance-every", type=int, default=1, metavar="N", help="... every N-th accepted step")
+    a = ap.parse_args()
+    result = main(output_dir=a.out, quiet=False, balance=a.balance, balance_every=a.balance_every)
     print({k: v for k, v in result.items() if k != "problem"})

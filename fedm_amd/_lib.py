@@ -151,6 +151,21 @@ class DiagOut(C.Structure):
                 ("finite", C.c_int32), ("pad_", C.c_int32)]
 
 
+GD_BAL_MAX_GROUPS = 8
+
+
+class GdBalanceOut(C.Structure):
+    _fields_ = [("content", C.c_double * GD_MAX_SPECIES), ("rate_of_change", C.c_double * GD_MAX_SPECIES),
+                ("reaction", C.c_double * GD_MAX_REACTIONS),
+                ("collision_loss", C.c_double), ("joule", C.c_double),
+                ("wall", (C.c_double * GD_MAX_SPECIES) * MAX_TAGS), ("ion_flux", C.c_double * MAX_TAGS),
+                ("induced_current", C.c_double), ("group_sum", C.c_double * GD_BAL_MAX_GROUPS),
+                ("field_max", C.c_double), ("field_max_centroid", C.c_double * 2),
+                ("nodal_max", C.c_double * (GD_MAX_SPECIES + 1)),
+                ("field_max_cell", C.c_int32), ("nodal_max_vertex", C.c_int32 * (GD_MAX_SPECIES + 1)),
+                ("finite", C.c_int32), ("pad_", C.c_int32)]
+
+
 FIELDS_MAX_REQ = 8
 
 
@@ -220,6 +235,8 @@ _SIGNATURES = {
     "fedm_photo_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
     "fedm_diag_setup": (C.c_int, [_P, _D, C.POINTER(C.c_int8), C.c_int]),
     "fedm_diagnostics": (C.c_int, [_P, C.POINTER(DiagOpts), C.POINTER(DiagOut)]),
+    "fedm_gd_balance_setup": (C.c_int, [_P, _D, C.POINTER(C.c_int8), C.c_int]),
+    "fedm_gd_balance": (C.c_int, [_P, C.POINTER(GdBalanceOut)]),
     "fedm_fields_setup": (C.c_int, [_P, C.POINTER(Csr)]),
     "fedm_probe_setup": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), _D]),
     "fedm_fields": (C.c_int, [_P, C.POINTER(FieldOpts), C.c_int, C.POINTER(FieldReq), _D, _D, C.POINTER(C.c_int32),

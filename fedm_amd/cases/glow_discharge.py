@@ -30,7 +30,8 @@ class Case:
 
     def __init__(self, nx=100, ny=100, file_input=DECK, device=0, T_final=1e-11,
                  relative_tolerance=1e-4, maximum_iterations=20, quiet=True, error_file=None,
-                 device_pipeline=True, mesh=None, energy_loss=None, energy_Ei=0.0, quadrature_degree=4):
+                 device_pipeline=True, mesh=None, energy_loss=None, energy_Ei=0.0, quadrature_degree=4,
+                 keep_balance=False):
         import tempfile
         self.quiet = quiet
         model = "4_particles"
@@ -140,6 +141,8 @@ class Case:
         open(self.error_file, "w").close()
         self.t, self.t_output, self.snapshot = 0.0, 1e-11, None
         self.newton_iterations = self.linear_iterations = 0
+        # keep_balance: every step leaves the balance of the residual it solved in last_balance
+        self.keep_balance, self.last_balance = keep_balance, None
 
     def dirichlet_values(self, t):
         return np.concatenate([np.full(self.powered.size, self.U_w * (1.0 - np.exp(-t / 1e-9))),
@@ -245,6 +248,8 @@ class Case:
                                         time_dependent_arguments=[self.Phi_powered], approximation="LMEA")
         self.newton_iterations += prob.last_report.iterations
         self.linear_iterations += prob.last_report.linear_iterations
+        if self.keep_balance:
+            self.last_balance = self.balance()
         self.U = prob.get_state()
         self.mean_energy.vector()[:] = np.exp(self.U[:, 0] - self.U[:, ns - 1])      # :452
         if self.snapshot is None and self.t_output <= self.t:        # file_output, file_io.py:582-587
@@ -272,6 +277,8 @@ class Case:
         prob = self.prob
         prob.gd_prep_step()
         self._solve()
+        if self.keep_balance:       # before the mean-energy field moves on to the next step
+            self.last_balance = self.balance()
         prob.gd_update_mean_energy()
         if self.snapshot is None and self.t_output <= self.t:
             U_old, U = prob.get_state_old(), prob.get_state()
@@ -282,6 +289,19 @@ class Case:
         self.max_error[2] = self.max_error[1]
         self.max_error[1] = self.max_error[0]
         return self.t
+
+    def balance(self):
+        """The particle and energy balance on the device (``fedm.Discharge_balance``) of the state and the field table as
+        they stand: surface charges of the powered and the grounded electrode, the Shockley-Ramo current with
+        psi = z / gap.  Set up at the first call.  Returns a :class:`fedm_amd.device.Balance`.
+        The balance of the residual a step solved is the one taken between its solve and its mean-energy update:
+        ``keep_balance=True`` makes every ``step()`` leave that one in ``last_balance``.  Called after ``step()`` of the
+        device pipeline, the mean-energy field is already the next step's (the electrons' thermal velocity at the walls
+        with it), and the energy and electron rows are off by that much."""
+        if getattr(self, "_balance", None) is None:
+            self._balance = ff.Discharge_balance(self.prob, boundary_tags=(1, 2),
+                                                 weighting_potential=self.mesh.coords[:, 1] / self.gap)
+        return self._balance()
 
     def run(self):
         while self.t < self.T_final:

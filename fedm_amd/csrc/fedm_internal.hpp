@@ -76,6 +76,7 @@ struct FsTiles;
 struct Photo;
 struct Diag;
 struct Fields;
+struct GdBalance;
 
 // Optional in-run kernel timing with HIP events on the library's stream (bench.py roofline).
 // kinds: 0 assembly F+J, 1 Jacobian SpMV, 2 assembly F only, 3 multigrid V-cycle
@@ -314,6 +315,7 @@ struct Ctx {
     Photo *photo = nullptr;   // photoionisation: Helmholtz sources into the targets' source tables (photo.hpp; fedm_photo_setup)
     Diag *diag = nullptr;     // discharge diagnostics: psi, groups and the reductions' buffers (diag.hpp; allocated at first use)
     Fields *fields = nullptr; // field output: the vertex lists, the lumped mass, the results' buffers (fields.hpp; fedm_fields_setup)
+    GdBalance *gd_balance = nullptr;   // LMEA balance: psi, groups, the tags' facet lists and the reductions' buffers (gd_balance.hpp; allocated at first use)
 };
 
 // Indices of Ctx::path_stats, in the order fedm_solver_path_stats documents (include/fedm_hip.h)
@@ -435,6 +437,8 @@ void photo_release(Ctx &c);
 void diag_release(Ctx &c);
 // ---- fields.hip (fields.hpp has the rest) -----------------------------------------------------
 void fields_release(Ctx &c);
+// ---- gd_balance.hip (gd_balance.hpp has the rest) ---------------------------------------------
+void gd_balance_release(Ctx &c);
 // ---- spmv.hip -------------------------------------------------------------------------------
 void launch_block_inverse(Ctx &c);                              // d_dinv from diagonal blocks
 void launch_row_scale(Ctx &c, double *d2, double *d_out);       // d^2 (and d, unless null) of the rows' equilibration

@@ -311,6 +311,69 @@ class Diagnostics:
 
 
 @dataclass
+class Balance:
+    """One call of :meth:`DeviceProblem.balance` (``fedm_gd_balance``, include/fedm_hip.h has the formulae): the particle
+    and energy balance of an LMEA model at the state the residual of the current step sees.  Component 0 is the energy
+    equation, 1..ns-1 the species (the last the electrons).  Axisymmetric: totals; planar: per metre of depth.  Indices in
+    the caller's numbering (on an exact tie of the field maximum the lowest cell in the device's order)."""
+    content: np.ndarray               # [ns] int exp(u_c): particles; [0] the electrons' energy [eV]
+    rate_of_change: np.ndarray        # [ns] int of the residual's BDF2 term  [1/s; eV/s]
+    reaction: np.ndarray              # [nr] int R_j  [1/s]
+    collision_loss: float             # int sum_j loss_j R_j  [eV/s]
+    joule: float                      # int -Gamma_e . E  [eV/s]
+    wall: np.ndarray                  # [n_tags, ns] the walls' facet integrals of row c, per boundary tag
+    ion_flux: np.ndarray              # [n_tags] int sum_ions max(Gamma_i . n, 0)  [1/s]
+    induced_current: float            # sum_s sign_s int Gamma_s . (-grad psi)  [1/s]; 0 without a psi
+    group_sum: np.ndarray             # the unconstrained Poisson rows summed over vertex group g  [V m]
+    field_max: float                  # max over the cells of |grad Phi|  [V/m]
+    field_max_cell: int
+    field_max_centroid: Tuple[float, float]
+    nodal_max: np.ndarray             # [ns + 1] max_v u_c(v), bitwise state values; [ns]: max_v (u_0 - u_e)(v)
+    nodal_max_vertex: np.ndarray
+    finite: bool                      # False: a value met on the way was not finite; the rest is unspecified
+    net: np.ndarray                   # [nr, ns] the reactions' net gains (the model's)
+    sign: np.ndarray                  # [ns] the species' charge numbers
+
+    @property
+    def source(self):
+        """[ns] what the reactions and the field put in: sum_j net[j][s] reaction[j]; [0]: joule - collision_loss."""
+        src = self.net.T.astype(np.float64) @ self.reaction
+        src[0] = self.joule - self.collision_loss
+        return src
+
+    @property
+    def imbalance(self):
+        """[ns] rate_of_change - source + sum_t wall: the sum over all vertices of row c of the residual."""
+        return self.rate_of_change - self.source + self.wall.sum(axis=0)
+
+    @property
+    def wall_current(self):
+        """[n_tags] e sum_s sign_s wall[t][s] [A]: the conduction current into each boundary (ions plus the secondary
+        electrons they release, minus the electrons that arrive)."""
+        return elementary_charge * (self.wall[:, 1:] @ self.sign[1:])
+
+    @property
+    def power_joule(self):
+        """e joule [W]."""
+        return elementary_charge * self.joule
+
+    @property
+    def current(self):
+        """e I_psi [A]."""
+        return elementary_charge * self.induced_current
+
+    @property
+    def surface_charge(self):
+        """eps0 q_g [C]: the charge on electrode g."""
+        return epsilon_0 * self.group_sum
+
+    @property
+    def mean_energy_max(self):
+        """the largest nodal mean energy exp(u_0 - u_e) [eV]."""
+        return float(np.exp(self.nodal_max[-1]))
+
+
+@dataclass
 class FieldValues:
     """One call of :meth:`DeviceProblem.fields` (``fedm_fields``): ``nodal[k]`` the nodal values of request ``k`` in the
     caller's vertex order (None with ``nodal=False``), ``probes[k]`` its values at the probe points (None without
@@ -567,12 +630,14 @@ class DeviceProblem:
         self._dvals = np.ascontiguousarray(dirichlet_vals, dtype=np.float64)
         self._coords_dev = np.ascontiguousarray(self.coords[self._order])
         self._cells_dev = np.ascontiguousarray(self._inv[self.cells], dtype=np.int32)
+        self._cell_order = None        # the caller's index of the device's cell k (None: the same)
         if isinstance(model, GdModel) and reorder and os.environ.get("FEDM_GD_CELL_ORDER", "1") != "0":
             # LMEA: the element kernels take 64 consecutive cells a workgroup and the gather kernel reads, for
             # consecutive matrix rows, the blocks of the cells around them -- cells in the order of their vertices
             # (nothing the caller passes or gets back is indexed by cell besides the facet tags)
             by_vertex = np.argsort(self._cells_dev.min(axis=1), kind="stable")
             self._cells_dev = np.ascontiguousarray(self._cells_dev[by_vertex])
+            self._cell_order = by_vertex
             if self._tags is not None:
                 self._tags = np.ascontiguousarray(self._tags.reshape(self.nc, 3)[by_vertex])
         tab = None
@@ -898,6 +963,73 @@ class DeviceProblem:
             nodal_max_vertex=np.where(vert >= 0, self._order[np.maximum(vert, 0)], -1),
             finite=bool(out.finite), Z=np.asarray(self.model.Z, dtype=np.float64)[:ns],
             linear_representation=not self.model.log_representation)
+
+    # -- particle and energy balance of LMEA models (csrc/gd_balance.hip) ------------------
+    def facet_tags(self):
+        """The boundary tags ``[n_cells, 3]`` in the caller's cell order (None without tags)."""
+        if self._tags is None:
+            return None
+        tags = self._tags.reshape(self.nc, 3)
+        if self._cell_order is None:
+            return tags
+        out = np.empty_like(tags)
+        out[self._cell_order] = tags
+        return out
+
+    def balance_setup(self, weighting_potential=None, vertex_groups=None, n_groups=None):
+        """What :meth:`balance` may use (``fedm_gd_balance_setup``), both in the caller's numbering:
+        ``weighting_potential``: nodal P1 psi ``[n_vertices]`` of the induced current (None: no current);
+        ``vertex_groups``: ``int8 [n_vertices]``, 0 or the group 1..8 whose Poisson rows are summed
+        (:func:`boundary_vertex_groups`; None: no groups); ``n_groups``: how many sums come back (default: the largest
+        group present).  Replaces an earlier set-up."""
+        if not isinstance(self.model, GdModel):
+            raise RuntimeError("balance: LMEA models only (diagnostics() has the LFA family's observables)")
+        psi = grp = None
+        n_groups = int(n_groups or 0)
+        if weighting_potential is not None:
+            psi = np.asarray(weighting_potential, dtype=np.float64).reshape(-1)
+            if psi.size != self.nv:
+                raise ValueError(f"weighting_potential must have {self.nv} entries, got {psi.size}")
+            psi = np.ascontiguousarray(psi[self._order])
+        if vertex_groups is not None:
+            grp = np.asarray(vertex_groups).reshape(-1)
+            if grp.size != self.nv:
+                raise ValueError(f"vertex_groups must have {self.nv} entries, got {grp.size}")
+            if grp.size and (grp.min() < 0 or grp.max() > _lib.GD_BAL_MAX_GROUPS):
+                raise ValueError(f"vertex_groups holds 0 or a group 1..{_lib.GD_BAL_MAX_GROUPS}")
+            n_groups = max(int(grp.max()) if grp.size else 0, n_groups)
+            grp = np.ascontiguousarray(grp[self._order], dtype=np.int8) if n_groups else None
+        else:
+            n_groups = 0
+        self._check(self.lib.fedm_gd_balance_setup(self._h, _dp(psi) if psi is not None else None,
+                                                   grp.ctypes.data_as(C.POINTER(C.c_int8)) if grp is not None else None,
+                                                   n_groups), "fedm_gd_balance_setup")
+        self._balance_groups = n_groups
+
+    def balance(self):
+        """The particle and energy balance at the state the residual of the current step sees (``fedm_gd_balance``): a
+        pass over the cells, one over the tagged facets, one over the vertices, a read-back of 880 bytes.  Returns a
+        :class:`Balance`."""
+        if not isinstance(self.model, GdModel):
+            raise RuntimeError("balance: LMEA models only (diagnostics() has the LFA family's observables)")
+        out = _lib.GdBalanceOut()
+        self._check(self.lib.fedm_gd_balance(self._h, C.byref(out)), "fedm_gd_balance")
+        ns, nr, nt = self.model.n_species, self.model.n_reactions, len(self.model.ref)
+        vert = np.array(out.nodal_max_vertex[:ns + 1], dtype=np.int64)
+        cell = int(out.field_max_cell)
+        if cell >= 0 and self._cell_order is not None:
+            cell = int(self._cell_order[cell])
+        return Balance(
+            content=np.array(out.content[:ns]), rate_of_change=np.array(out.rate_of_change[:ns]),
+            reaction=np.array(out.reaction[:nr]), collision_loss=float(out.collision_loss), joule=float(out.joule),
+            wall=np.array([list(out.wall[t][:ns]) for t in range(nt)]).reshape(nt, ns),
+            ion_flux=np.array(out.ion_flux[:nt]), induced_current=float(out.induced_current),
+            group_sum=np.array(out.group_sum[:getattr(self, "_balance_groups", 0)]),
+            field_max=float(out.field_max), field_max_cell=cell, field_max_centroid=tuple(out.field_max_centroid),
+            nodal_max=np.array(out.nodal_max[:ns + 1]),
+            nodal_max_vertex=np.where(vert >= 0, self._order[np.maximum(vert, 0)], -1),
+            finite=bool(out.finite), net=np.asarray(self.model.net, dtype=np.int64).reshape(nr, -1)[:, :ns],
+            sign=np.asarray(self.model.sign, dtype=np.float64)[:ns])
 
     # -- field output (csrc/fields.hip) ---------------------------------------------------
     def fields_setup(self, consistent=False):

@@ -976,6 +976,29 @@ def Discharge_diagnostics(problem, boundary_tags=(), window=None, weighting_pote
     return diagnose
 
 
+def Discharge_balance(problem, boundary_tags=(), weighting_potential=None):
+    """Extension (what a glow-discharge run is judged by): the particle and energy balance of an LMEA model without
+    downloading the state -- contents, the BDF2 rates of change, reaction totals, Joule heating and collision loss, the
+    walls' integrals and the conduction current per boundary tag, the ion flux, and the imbalance
+    ``rate_of_change - source + sum of the walls``, which is the sum over all vertices of that row of the residual.
+    ``problem``: a :class:`Problem` (or its device problem) of an LMEA model.  ``boundary_tags[g]``: the boundary whose
+    surface charge is wanted, as :func:`Discharge_diagnostics` takes it.  ``weighting_potential``: nodal values
+    [n_vertices] of the Shockley-Ramo psi of ``current`` (for a planar gap ``z / d``).
+
+    Returns a callable: ``balance()`` gives a :class:`fedm_amd.device.Balance` of the state the residual of the current
+    step sees (``u_new`` with the field table, ``u_old``, ``u_old1`` and the step sizes as they stand)."""
+    from .device import GdModel, boundary_vertex_groups
+    dev = getattr(problem, "device", problem)
+    if not isinstance(dev.model, GdModel):
+        raise ValueError("fedm.Discharge_balance: LMEA models only (Discharge_diagnostics has the LFA family's observables)")
+    boundary_tags = list(boundary_tags)
+    groups = None
+    if boundary_tags:
+        groups = boundary_vertex_groups(dev.cells, dev.facet_tags(), dev.nv, dev.dirichlet_vertices(), boundary_tags)
+    dev.balance_setup(weighting_potential=weighting_potential, vertex_groups=groups, n_groups=len(boundary_tags))
+    return dev.balance
+
+
 def Field_output(problem, fields, probes=None, projection="lumped", species_names=None):
     """Extension (what the reference's scripts do with ``project(...)`` and ``file_output``, fedm-gd.py:309,432): derived
     nodal fields of the device-resident state, blended to an output time, without downloading the state.  ``problem``:

@@ -245,7 +245,8 @@ const char *fedm_last_error(void);
  *    with fedm_wall_desc; FEDM_BC_FLUX_SOURCE, a value of bc_kind that the two older creators refuse.
  *    fedm_photo_setup with fedm_photo_desc and fedm_photo_hierarchy, fedm_photo_update, fedm_photo_get, fedm_photo_stats.
  *    fedm_diag_setup and fedm_diagnostics with fedm_diag_opts and fedm_diag.
- *    fedm_fields_setup, fedm_probe_setup and fedm_fields with fedm_field_req and fedm_field_opts. */
+ *    fedm_fields_setup, fedm_probe_setup and fedm_fields with fedm_field_req and fedm_field_opts.
+ *    fedm_gd_balance_setup and fedm_gd_balance with fedm_gd_balance. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -800,6 +801,59 @@ int fedm_probe_setup(fedm_ctx *ctx, int n_points, const int32_t *vertices, const
  * is not finite; probes asked for without points. */
 int fedm_fields(fedm_ctx *ctx, const fedm_field_opts *opts, int n_req, const fedm_field_req *req, double *nodal,
                 double *probes, int32_t *finite, int32_t *cg_iterations);
+
+/* ---- particle and energy balance of LMEA models on the device ------------------------------------
+ * What a glow-discharge run is judged by, from the resident state in one pass over the cells, one over the tagged
+ * boundary facets and one over the vertices; one small read-back per call.  LMEA family (fedm_ctx_create_gd), one GPU.
+ * Notation: ns = n_species; component c = 0 is the energy equation, c = 1..ns-1 the species (ns-1 the electrons), ns
+ * the potential.  W = qp_w |det J| 2 pi r(x_q) at the model's own quadrature points, 1/(2 pi) in place of r when
+ * axisymmetric == 0; on a facet W = fqp_w L 2 pi r.  Everything is evaluated at u_new with the field table as it
+ * stands and the context's u_old, u_old1, dt, dt_old: exactly what the residual of the current step sees -- the
+ * semi-implicit coefficients c + c' dme, dme = (exp(u_0) - exp(u_e) mean_energy_old) / exp(u_e_old), the fluxes
+ * Gamma_s of the species rows, the facet integrands of the 'flux source' walls.  There is no state selector: called
+ * after an accepted step and before the next fedm_gd_prep_step it is the balance of the step just solved.
+ * The P1 basis sums to 1 and its gradient to 0, and species and energy rows carry no Dirichlet condition, so the sum
+ * over ALL vertices of row c of the assembled residual is, in exact arithmetic,
+ *     rate_of_change[c] - source[c] + sum_t wall[t][c],
+ * with the sources the caller forms: source[s] = sum_j net[j][s] reaction[j], source[0] = joule - collision_loss.
+ * Every sum and maximum is reduced in a fixed order without floating-point atomics: two calls on one state return the
+ * same bytes. */
+#define FEDM_GD_BAL_MAX_GROUPS 8
+/* (a struct tag, not a typedef: the call below has the same name, so the type is written `struct fedm_gd_balance`) */
+struct fedm_gd_balance {
+    double content[FEDM_GD_MAX_SPECIES];        /* sum W exp(u_c): particles; c = 0 the electrons' energy [eV]            */
+    double rate_of_change[FEDM_GD_MAX_SPECIES]; /* sum W T_c, T_c = exp(u_c) ((1 + 2w) u_c - (1 + w)^2 u_c,old +
+                                                   w^2 u_c,old1) / ((1 + w) dt), w = dt / dt_old: the residual's BDF2 term */
+    double reaction[FEDM_GD_MAX_REACTIONS];     /* sum W R_j, R_j = k_j N0^p_j0 prod_i n_i^p_ji with the semi-implicit k_j,
+                                                   multiplied in the residual's order                                   */
+    double collision_loss, joule;               /* sum W sum_j loss_j R_j (the two sentinel losses as the residual takes
+                                                   them); sum W (-Gamma_e . E)   [eV/s]                                  */
+    double wall[FEDM_MAX_TAGS][FEDM_GD_MAX_SPECIES]; /* the facet integrand of row c summed over the facets with tag t + 1:
+                                                   (1 - ref)/(1 + ref) (vth/2 + |sign mu E.n|) n - 2 gamma/(1 + ref) ion
+                                                   flux for electrons; 5/3 mu, 1.3333 vth, gamma we_secondary for c = 0;
+                                                   0 for 'reaction' species                                             */
+    double ion_flux[FEDM_MAX_TAGS];             /* sum W sum_ions max(Gamma_i . n, 0)                                    */
+    double induced_current;                     /* sum_(s >= 1) sign_s sum W Gamma_s . (-grad psi) [1/s], the residual's
+                                                   fluxes; 0 without a psi                                              */
+    double group_sum[FEDM_GD_BAL_MAX_GROUPS];   /* the unconstrained Poisson rows summed over the group's vertices, as
+                                                   fedm_diag.group_sum                                                  */
+    double field_max, field_max_centroid[2];    /* max over the cells of |grad Phi|, its cell (the context's cell index, lowest
+                                                   on a tie), that cell's centroid                                      */
+    double nodal_max[FEDM_GD_MAX_SPECIES + 1];  /* c < ns: max_v u_c(v), bitwise a state value; [ns]: max_v (u_0 - u_e)(v),
+                                                   the log of the mean energy                                           */
+    int32_t field_max_cell, nodal_max_vertex[FEDM_GD_MAX_SPECIES + 1];   /* lowest on a tie; -1 for unused entries       */
+    int32_t finite, pad_;                       /* 0: a state value visited or a quantity formed was not finite; the
+                                                   other fields are then unspecified                                    */
+};
+/* psi: nodal P1 weighting potential [n_vertices] or NULL; group: [n_vertices] values 0 (none) or 1..n_groups, or NULL
+ * with n_groups = 0; both in the context's numbering, copied.  Replaces an earlier set-up.  Refused (-2, fedm_last_error
+ * says why): an LFA context; a context with ghosts; n_groups outside 0..FEDM_GD_BAL_MAX_GROUPS or without an array; a
+ * group value outside 0..n_groups; a psi that is not finite. */
+int fedm_gd_balance_setup(fedm_ctx *ctx, const double *psi, const int8_t *group, int n_groups);
+/* The quantities above; works without fedm_gd_balance_setup (no psi, no groups).  Allocates nothing after the first
+ * call, touches no state and synchronises once, for the read-back.  Returns 0 also when out->finite is 0; the next
+ * call is unaffected.  Refused (-2): an LFA context, a context with ghosts, a null argument. */
+int fedm_gd_balance(fedm_ctx *ctx, struct fedm_gd_balance *out);
 
 /* timed micro-benchmarks on the resident state (HIP events on the library's stream):
  * kind 0 = residual+Jacobian assembly, 1 = SpMV, 2 = residual only, 3 = one multigrid cycle on the
