@@ -178,6 +178,22 @@ class FieldOpts(C.Structure):
                 ("rtol", C.c_double)]
 
 
+KOP_RED_K, KOP_MAX_VECTORS = 40, 32
+# include/fedm_hip.h, FEDM_KOP_*
+KRYLOV_OPS = {"dots": 0, "dots_fused": 1, "spmv_dots": 2, "cgs_refine": 3, "norm2": 4, "norm2_publish": 5,
+              "cgs_update": 6, "cgs_update_fs": 7, "scale_copy_fs": 8, "multi_axpy": 9, "newton_update": 10,
+              "normalise_copy": 11, "field_error": 12, "field_error_slots34": 13}
+
+
+class KrylovIo(C.Structure):
+    _fields_ = [("n_vec", C.c_int32), ("finish", C.c_int32), ("y_index", C.c_int32), ("slot", C.c_int32),
+                ("red_in", C.c_int32), ("pad_", C.c_int32), ("a", C.c_double), ("sentinel", C.c_double),
+                ("V", C.POINTER(C.c_double)), ("y", C.POINTER(C.c_double)), ("x", C.POINTER(C.c_double)),
+                ("x0", C.POINTER(C.c_double)), ("coef", C.POINTER(C.c_double)), ("red", C.POINTER(C.c_double)),
+                ("y_out", C.POINTER(C.c_double)), ("x_out", C.POINTER(C.c_double)), ("mail", C.POINTER(C.c_double)),
+                ("g32", C.POINTER(C.c_float)), ("b0", C.POINTER(C.c_double)), ("info", C.c_int64 * 4)]
+
+
 ALLREDUCE_FN =C.CFUNCTYPE(None, C.POINTER(C.c_double), C.c_int32, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_void_p)
 
@@ -283,6 +299,7 @@ _SIGNATURES = {
     "fedm_debug_fieldsplit_apply_produced": (C.c_int, [_P, _D, C.c_int, _D, _D, _D]),
     "fedm_debug_fieldsplit_tiles": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "fedm_debug_species_planes_check": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "fedm_debug_krylov_op": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(KrylovIo)]),
     "fedm_profile": (C.c_int, [_P, C.c_int]),
     "fedm_profile_read": (C.c_int, [_P, C.c_int, _D, C.POINTER(C.c_int64)]),
     "fedm_set_assembly": (C.c_int, [_P, C.c_int]),

@@ -2,6 +2,7 @@
 // points, timers, counters, the profile -- and the installation of a transport.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "solver.hpp"
 
@@ -401,6 +402,229 @@ int fedm_debug_fieldsplit_apply_produced(fedm_ctx *h, const double *t, int k, co
     FEDM_HIP_CHECK(hipGetLastError());
     if (get_vec(c, y, c.d_tmp)) return -1;
     return get_vec(c, z, c.d_w);
+}
+
+}  // extern "C"
+
+// ---- fedm_debug_krylov_op: one launch wrapper of the Krylov step on the caller's vectors -----------------------------
+namespace {
+
+static_assert(FEDM_KOP_RED_K == RED_K, "fedm_krylov_io::red mirrors Ctx::d_red");
+
+// a host vector into a device vector of c.np entries: the caller's first n_keep entries, the sentinel behind them
+int put_with_sentinel(Ctx &c, double *dst, const double *src, size_t n_keep, double sentinel) {
+    for (size_t i = 0; i < (size_t)c.np; ++i) c.h_stage[i] = sentinel;
+    if (src) std::memcpy(c.h_stage, src, sizeof(double) * n_keep);
+    FEDM_HIP_CHECK(hipMemcpyAsync(dst, c.h_stage, sizeof(double) * c.np, hipMemcpyHostToDevice, c.stream));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+int krylov_op_refuse(const char *why) {
+    set_error(std::string("fedm_debug_krylov_op: ") + why);
+    return -2;
+}
+
+// what the op does to the context's own vectors is undone on every way out
+struct KrylovOpGuard {
+    Ctx &c;
+    std::vector<double> red;
+    bool state_saved = false, first_stage_written = false;
+    KrylovOpGuard(Ctx &ctx, const std::vector<double> &red_as_found) : c(ctx), red(red_as_found) {}
+    ~KrylovOpGuard() {
+        c.red_w = nullptr;
+        hipMemcpyAsync(c.d_red, red.data(), sizeof(double) * 2 * RED_K, hipMemcpyHostToDevice, c.stream);
+        if (first_stage_written) {
+            hipMemsetAsync(c.d_fs_g, 0, sizeof(double) * c.np, c.stream);
+            hipMemsetAsync(c.amg->levels[0].b, 0, sizeof(double) * c.nvp, c.stream);
+        }
+        if (state_saved) {
+            hipMemcpyAsync(c.d_u, c.d_Z + (size_t)c.np, sizeof(double) * c.np, hipMemcpyDeviceToDevice, c.stream);
+            hipMemcpyAsync(c.d_uold, c.d_Z + 2 * (size_t)c.np, sizeof(double) * c.np, hipMemcpyDeviceToDevice, c.stream);
+        }
+        hipStreamSynchronize(c.stream);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int fedm_debug_krylov_op(fedm_ctx *h, int op, int k, fedm_krylov_io *io) {
+    if (!h || !io || !io->red) return krylov_op_refuse("null argument");
+    Ctx &c = h->c;
+    if (op < 0 || op >= FEDM_KOP_COUNT) return krylov_op_refuse("unknown op");
+    if (!std::isfinite(io->sentinel)) return krylov_op_refuse("the sentinel must be finite");
+    if (io->n_vec < 0 || io->n_vec > FEDM_KOP_MAX_VECTORS || (io->n_vec > 0 && !io->V))
+        return krylov_op_refuse("n_vec out of range (0 .. 32), or no V");
+    const bool fs_op = op == FEDM_KOP_CGS_UPDATE_FS || op == FEDM_KOP_SCALE_COPY_FS || op == FEDM_KOP_CGS_REFINE;
+    const bool uses_V = op == FEDM_KOP_DOTS || op == FEDM_KOP_DOTS_FUSED || op == FEDM_KOP_SPMV_DOTS ||
+                        op == FEDM_KOP_CGS_REFINE || op == FEDM_KOP_CGS_UPDATE || op == FEDM_KOP_CGS_UPDATE_FS ||
+                        op == FEDM_KOP_MULTI_AXPY || op == FEDM_KOP_NEWTON_UPDATE;
+    const bool uses_x = op == FEDM_KOP_SPMV_DOTS || op == FEDM_KOP_SCALE_COPY_FS || op == FEDM_KOP_NORMALISE_COPY ||
+                        op == FEDM_KOP_FIELD_ERROR || op == FEDM_KOP_FIELD_ERROR_SLOTS34;
+    const bool y_is_V = op == FEDM_KOP_DOTS_FUSED && io->y_index >= 0;
+    const bool y_is_output_only = op == FEDM_KOP_SPMV_DOTS || op == FEDM_KOP_SCALE_COPY_FS ||
+                                  op == FEDM_KOP_NORMALISE_COPY;
+    // ---- arguments: every refusal comes before the first launch
+    int n_basis = 0;   // the vectors of V the op reads
+    switch (op) {
+        case FEDM_KOP_DOTS:
+        case FEDM_KOP_DOTS_FUSED:
+        case FEDM_KOP_CGS_UPDATE:
+        case FEDM_KOP_MULTI_AXPY:
+            if (k < 1 || k > FEDM_KOP_MAX_VECTORS) return krylov_op_refuse("k out of range (1 .. 32)");
+            n_basis = k;
+            break;
+        case FEDM_KOP_SPMV_DOTS:
+            if (c.neq != 3) return krylov_op_refuse("the product fused with the dots exists for three equations only");
+            if (k < 2 || k > 8) return krylov_op_refuse("k out of range (2 .. 8)");
+            if (io->finish < 0 || io->finish > 2) return krylov_op_refuse("finish out of range (0 .. 2)");
+            n_basis = k - 1;
+            break;
+        case FEDM_KOP_CGS_REFINE:
+            if (k < 2 || k > 5) return krylov_op_refuse("k out of range (2 .. 5)");
+            n_basis = k - 1;
+            break;
+        case FEDM_KOP_CGS_UPDATE_FS:
+            if (k < 1 || k > 4) return krylov_op_refuse("k out of range (1 .. 4)");
+            n_basis = k;
+            break;
+        case FEDM_KOP_NEWTON_UPDATE:
+            if (k < 1 || k > 8) return krylov_op_refuse("k out of range (1 .. 8)");
+            n_basis = k;
+            break;
+        case FEDM_KOP_NORM2_PUBLISH:
+            if (k < 1 || k > RED_K) return krylov_op_refuse("k out of range (1 .. RED_K)");
+            [[fallthrough]];
+        case FEDM_KOP_NORM2:
+        case FEDM_KOP_NORMALISE_COPY:
+            if (io->slot < 0 || io->slot >= RED_K) return krylov_op_refuse("slot out of range");
+            break;
+        case FEDM_KOP_FIELD_ERROR:
+        case FEDM_KOP_FIELD_ERROR_SLOTS34:
+            if (io->slot < 0 || io->slot >= c.neq) return krylov_op_refuse("component out of range");
+            break;
+        default: break;
+    }
+    if (uses_V && n_basis > io->n_vec) return krylov_op_refuse("k beyond the vectors in V");
+    if (y_is_V && io->y_index >= io->n_vec) return krylov_op_refuse("y_index beyond the vectors in V");
+    if (!y_is_V && !y_is_output_only && !io->y) return krylov_op_refuse("no y");
+    if (uses_x && !io->x) return krylov_op_refuse("no x");
+    if ((op == FEDM_KOP_MULTI_AXPY || op == FEDM_KOP_NEWTON_UPDATE) && !io->coef) return krylov_op_refuse("no coef");
+    if (fs_op && (c.ns != 2 || !(c.amg && c.poisson) || !c.d_fs_g || c.comm))
+        return krylov_op_refuse("the fused first stage needs two species, one GPU and the field split's buffers "
+                                "(fedm_amg_setup)");
+    if (c.krylov_scaling != 0 && !c.d_kscale2) return krylov_op_refuse("krylov scaling without its weights");
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    // ---- storage, and the counters as found
+    const double *V_before = c.d_V;
+    if (ensure_krylov(c, 30)) return -1;   // (clears the captured steps itself when it reallocates)
+    io->info[3] = c.d_V != V_before ? 1 : 0;
+    unsigned long long dev_seq = 0;
+    FEDM_HIP_CHECK(hipMemcpy(&dev_seq, c.d_mail_seq, sizeof(dev_seq), hipMemcpyDeviceToHost));
+    if (dev_seq != c.mail_seq) {
+        io->info[0] = io->info[2] = -1;
+        io->info[1] = (int64_t)c.mail_seq;
+        return krylov_op_refuse("the host's and the device's publication counts are apart");
+    }
+    const unsigned long long seq_before = c.mail_seq;
+    std::vector<double> red_as_found(2 * RED_K);
+    FEDM_HIP_CHECK(hipMemcpy(red_as_found.data(), c.d_red, sizeof(double) * 2 * RED_K, hipMemcpyDeviceToHost));
+    KrylovOpGuard guard(c, red_as_found);
+    // ---- the caller's vectors
+    const size_t n_red = (size_t)c.n_dot;     // entries that take part in reductions: the owned rows
+    auto V_at = [&](int i) { return i < 31 ? c.d_V + (size_t)i * c.np : c.d_Z; };
+    std::vector<const double *> vp(FEDM_KOP_MAX_VECTORS, nullptr);
+    for (int i = 0; i < io->n_vec; ++i) {
+        vp[i] = V_at(i);
+        if (put_with_sentinel(c, V_at(i), io->V + (size_t)i * c.n, n_red, io->sentinel)) return -1;
+    }
+    double *y = y_is_V ? V_at(io->y_index) : c.d_w;
+    if (!y_is_V && put_with_sentinel(c, c.d_w, y_is_output_only ? nullptr : io->y, n_red, io->sentinel)) return -1;
+    double *x = c.d_tmp;
+    if (op == FEDM_KOP_DOTS_FUSED && io->x0) {
+        if (put_with_sentinel(c, x, io->x0, (size_t)c.nv, io->sentinel)) return -1;
+    } else {
+        if (put_with_sentinel(c, x, uses_x ? io->x : nullptr, op == FEDM_KOP_SPMV_DOTS ? (size_t)c.n : n_red,
+                              io->sentinel))
+            return -1;
+    }
+    if (io->red_in)
+        FEDM_HIP_CHECK(hipMemcpyAsync(c.d_red, io->red, sizeof(double) * 2 * RED_K, hipMemcpyHostToDevice, c.stream));
+    else
+        FEDM_HIP_CHECK(hipMemsetAsync(c.d_red, 0, sizeof(double) * 2 * RED_K, c.stream));
+    float *g32 = reinterpret_cast<float *>(c.d_fs_g);
+    double *b0 = fs_op ? c.amg->levels[0].b : nullptr;
+    if (fs_op) {
+        fieldsplit_setup(c);   // Duu^-1 of the Jacobian as it stands
+        guard.first_stage_written = true;
+        // (what the op does not write shows: g32 holds np doubles' worth of bytes, b0 the padded vertices)
+        FEDM_HIP_CHECK(hipMemsetAsync(c.d_fs_g, 0xff, sizeof(double) * c.np, c.stream));
+        FEDM_HIP_CHECK(hipMemsetAsync(b0, 0xff, sizeof(double) * c.nvp, c.stream));
+    }
+    if (c.krylov_scaling != 0) {
+        launch_row_scale(c, c.d_kscale2, nullptr);
+        c.red_w = c.d_kscale2;
+    }
+    // ---- the op
+    bool launched = true;
+    switch (op) {
+        case FEDM_KOP_DOTS: launch_dots(c, vp.data(), y, k, io->finish != 0); break;
+        case FEDM_KOP_DOTS_FUSED:
+            launch_dots_fused(c, vp.data(), y, k, io->x0 ? x : nullptr, io->finish != 0);
+            break;
+        case FEDM_KOP_SPMV_DOTS: launched = launch_spmv_dots(c, x, y, vp.data(), k, io->finish); break;
+        case FEDM_KOP_CGS_REFINE: launched = launch_cgs_refine(c, k - 2, vp.data(), y, g32, b0); break;
+        case FEDM_KOP_NORM2: launch_norm2(c, y, io->slot); break;
+        case FEDM_KOP_NORM2_PUBLISH: norm2_publish(c, y, io->slot, k); break;
+        case FEDM_KOP_CGS_UPDATE: launch_cgs_update(c, k, vp.data(), y); break;
+        case FEDM_KOP_CGS_UPDATE_FS: launched = launch_cgs_update_fs(c, k, vp.data(), y, g32, b0); break;
+        case FEDM_KOP_SCALE_COPY_FS: launched = launch_scale_copy_fs(c, io->a, x, y, g32, b0); break;
+        case FEDM_KOP_MULTI_AXPY: launch_multi_axpy(c, io->coef, k, vp.data(), y, io->a); break;
+        case FEDM_KOP_NEWTON_UPDATE:
+            launch_newton_update(c, io->coef, k, vp.data(), y, io->finish ? x : nullptr);
+            break;
+        case FEDM_KOP_NORMALISE_COPY: launch_normalise_copy(c, io->slot, x, y); break;
+        default: {   // the field error reads the state itself: the caller's vectors stand in for it, the state comes back
+            double *keep_u = c.d_Z + (size_t)c.np, *keep_old = c.d_Z + 2 * (size_t)c.np;
+            FEDM_HIP_CHECK(hipMemcpyAsync(keep_u, c.d_u, sizeof(double) * c.np, hipMemcpyDeviceToDevice, c.stream));
+            FEDM_HIP_CHECK(hipMemcpyAsync(keep_old, c.d_uold, sizeof(double) * c.np, hipMemcpyDeviceToDevice, c.stream));
+            guard.state_saved = true;
+            FEDM_HIP_CHECK(hipMemcpyAsync(c.d_u, y, sizeof(double) * c.np, hipMemcpyDeviceToDevice, c.stream));
+            FEDM_HIP_CHECK(hipMemcpyAsync(c.d_uold, x, sizeof(double) * c.np, hipMemcpyDeviceToDevice, c.stream));
+            if (op == FEDM_KOP_FIELD_ERROR) launch_field_error(c, io->slot);
+            else launch_field_error_slots34(c, io->slot);
+        }
+    }
+    c.red_w = nullptr;
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    FEDM_HIP_CHECK(hipGetLastError());
+    if (!launched) {
+        set_error("fedm_debug_krylov_op: the launch wrapper has no kernel for this case");
+        return -2;
+    }
+    // ---- what it left
+    FEDM_HIP_CHECK(hipMemcpy(io->red, c.d_red, sizeof(double) * 2 * RED_K, hipMemcpyDeviceToHost));
+    FEDM_HIP_CHECK(hipMemcpy(&dev_seq, c.d_mail_seq, sizeof(dev_seq), hipMemcpyDeviceToHost));
+    io->info[0] = (int64_t)(c.mail_seq - seq_before);
+    io->info[1] = (int64_t)c.mail_seq;
+    io->info[2] = (int64_t)dev_seq;
+    if (io->info[0] > 0 && dev_seq == c.mail_seq) {
+        wait_red(c);
+        if (io->mail) std::memcpy(io->mail, c.h_red, sizeof(double) * RED_K);
+    }
+    if (io->y_out && get_vec(c, io->y_out, y)) return -1;
+    if (io->x_out && get_vec(c, io->x_out, x)) return -1;
+    if (fs_op && io->g32)
+        FEDM_HIP_CHECK(hipMemcpy(io->g32, g32, sizeof(float) * (size_t)c.nv * 2, hipMemcpyDeviceToHost));
+    if (fs_op && io->b0) FEDM_HIP_CHECK(hipMemcpy(io->b0, b0, sizeof(double) * c.nv, hipMemcpyDeviceToHost));
+    if (dev_seq != c.mail_seq) {
+        set_error("fedm_debug_krylov_op: the op left the host's and the device's publication counts apart");
+        return -1;
+    }
+    return 0;
 }
 
 int fedm_pattern_stats(const fedm_mesh_desc *mesh, int64_t out[12]) {

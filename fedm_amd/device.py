@@ -1683,6 +1683,50 @@ class DeviceProblem:
                                                                   _dp(z)), "fedm_debug_fieldsplit_apply_produced")
         return y, z
 
+    def krylov_op(self, op, k=0, V=None, y=None, x=None, x0=None, coef=None, red=None, finish=0, y_index=-1, slot=0,
+                  a=1.0, sentinel=1e30):
+        """Test hook: ONE launch wrapper of a Krylov step's reductions and vector updates on the caller's vectors
+        (``fedm_debug_krylov_op``; ``op`` a key of ``_lib.KRYLOV_OPS``, the fields each op reads are listed in
+        include/fedm_hip.h).  Vectors in the device's numbering: ``V`` of shape (n_vec, n), ``y`` and ``x`` of n
+        entries, ``x0`` of n_vertices.  ``red``: the two reduction rows, shape (2, 40), uploaded before the op when
+        given.  Every device entry outside the part of a vector that takes part in reductions holds ``sentinel``.
+        Returns a dict: ``y`` and ``x`` as the op left them, ``red`` (2, 40), ``mail`` (the published slot, or None),
+        ``published``, ``host_seq`` and ``device_seq`` (the publication counts), ``allocated`` (the Krylov storage was
+        made by this call), and for the ops with the field split's first stage ``g32`` (n_vertices, 2) and ``b0``."""
+        io = _lib.KrylovIo()
+        keep = []
+
+        def arr(v, size, what):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            if v.size != size:
+                raise ValueError(f"krylov_op: {what} must have {size} entries, got {v.size}")
+            keep.append(v)
+            return _dp(v)
+
+        n_vec = 0 if V is None else int(np.asarray(V).shape[0])
+        io.n_vec, io.finish, io.y_index, io.slot = n_vec, int(finish), int(y_index), int(slot)
+        io.a, io.sentinel = float(a), float(sentinel)
+        io.V = arr(V, n_vec * self.n, "V") if n_vec else None
+        io.y, io.x, io.x0 = arr(y, self.n, "y"), arr(x, self.n, "x"), arr(x0, self.nv, "x0")
+        io.coef = arr(coef, max(int(k), 0), "coef")
+        red_io = np.zeros((2, _lib.KOP_RED_K))
+        if red is not None:
+            red_io[...] = np.asarray(red, dtype=np.float64).reshape(2, _lib.KOP_RED_K)
+            io.red_in = 1
+        y_out, x_out, mail = np.empty(self.n), np.empty(self.n), np.empty(_lib.KOP_RED_K)
+        g32, b0 = np.empty((self.nv, 2), dtype=np.float32), np.empty(self.nv)
+        io.red, io.y_out, io.x_out, io.mail, io.b0 = _dp(red_io), _dp(y_out), _dp(x_out), _dp(mail), _dp(b0)
+        io.g32 = g32.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(self.lib.fedm_debug_krylov_op(self._h, _lib.KRYLOV_OPS[op], int(k), C.byref(io)),
+                    "fedm_debug_krylov_op")
+        published = int(io.info[0])
+        fs = op in ("cgs_update_fs", "scale_copy_fs", "cgs_refine")
+        return dict(y=y_out, x=x_out, red=red_io, mail=mail if published > 0 else None, published=published,
+                    host_seq=int(io.info[1]), device_seq=int(io.info[2]), allocated=bool(io.info[3]),
+                    g32=g32 if fs else None, b0=b0 if fs else None)
+
     def configure_fieldsplit_tiles(self, on, slices_per_tile=0, layers=0, threads=0, multigrid=True):
         """Test hook: species sweeps on tiles (several per launch) or one launch each; multigrid=False keeps the
         finest multigrid level's sweeps as kernels of their own."""

@@ -673,6 +673,71 @@ int fedm_debug_fieldsplit_tiles(fedm_ctx *ctx, int mode, int tile_slices, int de
  * the fused one}. */
 int fedm_debug_species_planes_check(fedm_ctx *ctx, double *out);
 
+/* Test hook: ONE launch wrapper of a Krylov step's reductions and vector updates (csrc/kernels.hip, the second half of
+ * csrc/spmv.hip) on the caller's vectors -- the production wrapper itself, with the production grids.
+ *   Vectors are host arrays of n_vertices * n_eq doubles in the device's order (fedm_debug_fieldsplit_apply's).  They
+ * go into the Krylov storage (ensure_krylov(30): V[i] for i < 31, the first preconditioned vector for i = 31), y into
+ * the product vector, x into the scratch vector.  Every device entry outside the part of a vector that takes part in
+ * reductions is overwritten with `sentinel` (finite): the padding rows [n, np) and, with n_owned < n_vertices, the
+ * ghost rows -- a kernel that reads a wrong range shows it.  Exceptions, because the entries are operands: x of
+ * FEDM_KOP_SPMV_DOTS keeps the caller's ghost entries, and x0 (n_vertices doubles) is sentinel beyond n_vertices only.
+ *   red[2][FEDM_KOP_RED_K]: the reductions' result rows; uploaded first when red_in is set (coefficients live there),
+ * zero otherwise; always returned.  mail[FEDM_KOP_RED_K]: the mailbox slot of the op's last publication, when it made
+ * one.  info = {publications made, host count of publications, device count (the two must agree; -1 when the entry
+ * found them apart), 1 if the Krylov storage was allocated by this call}.  With fedm_set_krylov_scaling "rows" the
+ * reductions take their weighted instantiations with the weights of the Jacobian as it stands.
+ *   The context is left as found (state, reduction rows, scaling); only scratch vectors are overwritten.
+ * op, k and the fields read:
+ *   DOTS             red[i] = V[i] . y, i < k <= 32; finish: the finish formulae on them and a publication
+ *   DOTS_FUSED       the same through dots_scatter_kernel; y_index >= 0: y IS V[y_index] (and y is not read from the
+ *                    caller); x0: the potential component of y is taken from it first; y_out returns y
+ *   SPMV_DOTS        y = J x, red[i] = V[i] . y (i < k - 1), red[k-1] = y . y; 2 <= k <= 8, three equations; finish 0,
+ *                    1, 2 (SPMV_DOTS_SUMS, _PUBLISH, _REFINED)
+ *   CGS_REFINE       the second Gram-Schmidt pass behind step j = k - 2 on y with V[0 .. j]; red_in carries the flag
+ *   NORM2            red[slot] = y . y;   NORM2_PUBLISH  the same and the publication of red[0 .. k)
+ *   CGS_UPDATE       y = (y - sum_i red[i] V[i]) red[RED_K-1], k <= 32
+ *   CGS_UPDATE_FS    the same for k <= 4 with the field split's first stage: g32 [n_vertices][2] and b0 [n_vertices]
+ *   SCALE_COPY_FS    y = a x with that first stage
+ *   MULTI_AXPY       y += a sum_i coef[i] V[i], k <= 32
+ *   NEWTON_UPDATE    delta = sum_i coef[i] V[i], y += delta, red[1] = |delta|^2, red[2] = |y|^2, k <= 8; finish = 0:
+ *                    delta is not stored; x_out returns delta
+ *   NORMALISE_COPY   y = x / sqrt(red[slot])
+ *   FIELD_ERROR(_SLOTS34)  component `slot` of y against x as new and old state: red[0..1] (red[3..4])
+ * Refused (-2, nothing launched): k out of the op's range or beyond n_vec, SPMV_DOTS on a model without exactly three
+ * equations, an _FS op or CGS_REFINE without two species and the field split's buffers (fedm_amg_setup,
+ * fedm_set_fieldsplit with more than one sweep), a missing vector. */
+#define FEDM_KOP_RED_K 40
+#define FEDM_KOP_MAX_VECTORS 32
+enum {
+    FEDM_KOP_DOTS = 0, FEDM_KOP_DOTS_FUSED, FEDM_KOP_SPMV_DOTS, FEDM_KOP_CGS_REFINE, FEDM_KOP_NORM2,
+    FEDM_KOP_NORM2_PUBLISH, FEDM_KOP_CGS_UPDATE, FEDM_KOP_CGS_UPDATE_FS, FEDM_KOP_SCALE_COPY_FS, FEDM_KOP_MULTI_AXPY,
+    FEDM_KOP_NEWTON_UPDATE, FEDM_KOP_NORMALISE_COPY, FEDM_KOP_FIELD_ERROR, FEDM_KOP_FIELD_ERROR_SLOTS34,
+    FEDM_KOP_COUNT
+};
+typedef struct {
+    int32_t n_vec;        /* vectors in V                                                   */
+    int32_t finish;       /* DOTS, DOTS_FUSED: 0 / 1; SPMV_DOTS: 0 / 1 / 2; NEWTON_UPDATE: store delta */
+    int32_t y_index;      /* DOTS_FUSED: y is V[y_index]; -1: a vector of its own           */
+    int32_t slot;         /* NORM2, NORM2_PUBLISH, NORMALISE_COPY; FIELD_ERROR*: component  */
+    int32_t red_in;       /* upload red before the op                                       */
+    int32_t pad_;
+    double a;             /* SCALE_COPY_FS: factor; MULTI_AXPY: sign                        */
+    double sentinel;
+    const double *V;      /* [n_vec][n]                                                     */
+    const double *y;      /* [n]                                                            */
+    const double *x;      /* [n]                                                            */
+    const double *x0;     /* [n_vertices] or null                                           */
+    const double *coef;   /* [k] host coefficients (MULTI_AXPY, NEWTON_UPDATE)              */
+    double *red;          /* [2][FEDM_KOP_RED_K], in / out                                  */
+    double *y_out;        /* [n] or null                                                    */
+    double *x_out;        /* [n] or null                                                    */
+    double *mail;         /* [FEDM_KOP_RED_K] or null                                       */
+    float *g32;           /* [n_vertices][2] or null                                        */
+    double *b0;           /* [n_vertices] or null                                           */
+    int64_t info[4];
+} fedm_krylov_io;
+int fedm_debug_krylov_op(fedm_ctx *ctx, int op, int k, fedm_krylov_io *io);
+
 /* |new - old + eps| / |old + eps| on one component        fedm/functions.py:1062-1064 */
 int fedm_field_error(fedm_ctx *ctx, int component, double *rel_err);
 

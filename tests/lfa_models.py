@@ -2,11 +2,12 @@
 import numpy as np
 
 
-def four_species_problem():
-    """The largest model `fedm_model_desc` holds (FEDM_MAX_SPECIES = 4 + Poisson, five equations) on the graded 20 x 20
-    streamer mesh: a metastable that only diffuses, an ion that drifts, a negative ion drifting with a prescribed
-    velocity, electrons with field-dependent coefficients; three reactions with field-dependent, constant and
-    quadratic rates.  Returns (mesh, device problem, the oracle's model of it, Dirichlet dofs, Dirichlet values)."""
+def four_species_problem(n=20, grading=2.0, oracle_model=True):
+    """The largest model `fedm_model_desc` holds (FEDM_MAX_SPECIES = 4 + Poisson, five equations) on the graded n x n
+    streamer mesh (20 x 20 unless told otherwise; oracle_model=False: without the oracle's model, None in its place --
+    what a large mesh wants): a metastable that only diffuses, an ion that drifts, a negative ion drifting with a
+    prescribed velocity, electrons with field-dependent coefficients; three reactions with field-dependent, constant
+    and quadratic rates.  Returns (mesh, device problem, the oracle's model of it, Dirichlet dofs, Dirichlet values)."""
     from oracle import streamer as ost
     from oracle.forms import LFAModel
     from oracle.mesh import Mesh as OMesh, mark_boundaries
@@ -14,7 +15,7 @@ def four_species_problem():
     from fedm_amd.device import DeviceProblem, Model, Reaction
     from fedm_amd.mesh import Marking_boundaries, Mesh
     from fedm_amd.termsum import TermSum, parse
-    msh = streamer.mesh(20, 2.0)
+    msh = streamer.mesh(n, grading)
     m = Mesh(msh.coords, msh.cells)
     tags = Marking_boundaries(m, streamer.BOUNDARIES)
     eq = ["diffusion-reaction", "drift-diffusion-reaction", "drift-diffusion-reaction", "drift-diffusion-reaction"]
@@ -32,6 +33,8 @@ def four_species_problem():
     ddofs, dvals = streamer.dirichlet(m.coords)
     ddofs = (ddofs // 3) * 5 + 4
     prob = DeviceProblem(m.coords, m.cells, model, facet_tags=tags, dirichlet_dofs=ddofs.astype(np.int32), dirichlet_vals=dvals)
+    if not oracle_model:
+        return m, prob, None, ddofs, dvals
     omesh = OMesh(msh.coords, msh.cells)
     om = LFAModel(omesh, 4, True, eq, Z,
                   mu=[0.0, 2e-4, 0.0, ost.MU_E], D=[5e-4, 3e-6, 2e-3, ost.D_E],
