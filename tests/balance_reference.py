@@ -65,11 +65,13 @@ def geometry(coords, cells):
 
 
 class _Points:
-    """The residual's point functions on a subset of the cells: unknowns, dme, semi-implicit mu, D, k, the fluxes."""
+    """The residual's point functions on a subset of the cells: unknowns, dme, semi-implicit mu, D, k, the fluxes.
+    ``Uc``: the cells' own nodal unknowns [cells, 3, n_eq] in place of ``U[cells]``; they may be complex (the
+    complex-step Jacobian of tests/lmea_family_reference.py), and everything at a point then is."""
 
-    def __init__(self, md, fields, U, cells, G):
+    def __init__(self, md, fields, U, cells, G, Uc=None):
         self.md, self.fields, self.cells, self.G = md, np.asarray(fields, dtype=np.float64), cells, G
-        self.Uc = np.asarray(U, dtype=np.float64)[cells]
+        self.Uc = np.asarray(U, dtype=np.float64)[cells] if Uc is None else Uc
         self.ns, self.nr = int(md.n_species), int(md.n_reactions)
 
     def sg(self, A, phi):

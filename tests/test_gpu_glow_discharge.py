@@ -1,11 +1,15 @@
 """Glow discharge (LMEA, 5 equations) on the device against the oracle and the reference's
 own goldens (tests/integrated_tests/glow_discharge/test_glow_discharge.py:48-62)."""
 import json
+import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from lmea_checks import gd_lds_bytes as _gd_lds_bytes  # noqa: E402
+from lmea_checks import jacobian_error as _jacobian_error, residual_error as _residual_error  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -84,18 +88,6 @@ def _upload(case, ref):
     return prob
 
 
-def _residual_error(F_gpu, F_cpu):
-    """largest error of F relative to the scale of its component"""
-    scale = np.abs(F_cpu).reshape(-1, 5).max(axis=0)
-    return (np.abs(F_gpu - F_cpu).reshape(-1, 5) / scale).max()
-
-
-def _jacobian_error(J_gpu, J_cpu):
-    """largest error of J relative to the largest entry of its row"""
-    rs = np.maximum(abs(J_cpu).max(axis=1).toarray().ravel(), 1e-300)
-    return (sp.diags(1.0 / rs) @ abs(J_gpu - J_cpu)).max()
-
-
 @pytest.mark.parametrize("losses", ["deck", "sentinels"])
 @pytest.mark.parametrize("variant", ["5", "3", "4", "2", "0"])
 def test_gd_residual_and_jacobian_match_the_oracle(variant, losses, monkeypatch):
@@ -163,17 +155,6 @@ def test_gd_gathers_per_position_and_per_row_agree_bit_for_bit(variant, monkeypa
     assert np.array_equal(Jp.data, Jr.data)
 
 
-def _gd_lds_bytes(n_eq, n_fields, n_qp):
-    """Dynamic LDS of gd_jacobian_rows_kernel (csrc/gd.hip, gd_plan): vertex ids, nodal fields and unknowns of 64 cells,
-    the table of exp(u) at the quadrature points while it fits 80 KiB, the rows' reaction weights and powers."""
-    from fedm_amd import _lib
-    lds = 8 * ((3 * 64 + 1) // 2 + 64 * n_fields * 3 + 64 * 3 * n_eq)
-    table = 8 * n_qp * n_eq * 64
-    if lds + table <= 80 * 1024:
-        lds += table
-    return lds + (n_eq - 1) * _lib.GD_MAX_REACTIONS * 12 + _lib.GD_MAX_REACTIONS * 4 + 8
-
-
 def test_gd_second_context_with_a_larger_lds_need():
     """Dynamic LDS beyond 64 KiB is opt-in per kernel.  The element kernel's need depends on the model (fields,
     quadrature points), not on the mesh: a degree-2 case (3 points, 67 656 bytes) and then, in the same process, a
@@ -186,7 +167,7 @@ def test_gd_second_context_with_a_larger_lds_need():
         case = gdc.Case(nx=10, ny=10, device_pipeline=False, quadrature_degree=degree)
         ref = _reference(case, degree=degree)
         prob = _upload(case, ref)
-        needs.append(_gd_lds_bytes(5, prob.model.n_fields, len(quadrature.triangle(degree)[1])))
+        needs.append(_gd_lds_bytes(5, prob.model.n_reactions, len(quadrature.triangle(degree)[1])))
         F_gpu, _ = prob.residual()
         f_err = _residual_error(F_gpu, ref["F"])
         prob.jacobian()
