@@ -21,6 +21,12 @@ whole per-step pipeline on the GPU.
 conduction currents into the two electrodes, Joule power, collision loss, the imbalances of the energy and particle
 balances and the Shockley-Ramo current with psi = z / gap, all formed on the device without downloading the state (an
 extension: `fedm.Discharge_balance`); off by default.
+
+`--fields LIST` writes derived fields (`mean_energy,E_norm,source:electrons,joule,flux_z:Ar_plus,...`) as VTU series at
+the output times (every N-th of them with `--fields-every N`); `--axis-profile FILE` writes, per accepted step, the
+profiles of AXIS_FIELDS along r = 0.  Both are formed on the device from the resident state and the coefficient table,
+where the residual of the step just solved evaluates them (an extension: `fedm.Field_output`): the values are those of
+the accepted step that reaches the output time, at its own time, not blended; off by default.
 """
 import argparse
 import contextlib
@@ -54,6 +60,8 @@ CHARGE_ROLE = ["Neutral", "Neutral", "Ion", "electrons"]
 START_DENSITY = [GAS_DENSITY, 1e12, 1e12, 1e12]
 OUTPUT_WINDOWS = [1e-11, 1e-10, 1e-9, 1e-8, 1e-7, 1e-6, 1e-5]
 OUTPUT_STRIDES = [1e-11, 1e-10, 1e-9, 1e-8, 1e-7, 1e-6, 1e-6]
+AXIS_POINTS = 64                          # points of --axis-profile on r = 0, from the powered to the grounded electrode
+AXIS_FIELDS = ["mean_energy", "E_z", "density:electrons", "joule"]
 
 
 def read_deck(input_dir):
@@ -241,7 +249,7 @@ def balance_row(t, b):
 
 
 def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", quiet=True, ttol=2e-3,
-         stop_before_device=None, balance=None, balance_every=1):
+         stop_before_device=None, balance=None, balance_every=1, fields=None, fields_every=1, axis_profile=None):
     fem.parameters["form_compiler"]["quadrature_degree"] = 4
     deck = read_deck(input_dir)
     file_io.files.output_folder_path = Path(output_dir)
@@ -296,6 +304,23 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
         balance_of = fedm.Discharge_balance(problem, boundary_tags=(1, 2), weighting_potential=problem.device.coords[:, 1] / GAP)
         rows = open(balance, "w")
         rows.write("# " + " ".join(balance_columns(deck["file_names"])) + "\n")
+    field_out = field_files = profile = profile_rows = None
+    if fields:
+        fields = [name.strip() for name in (fields.split(",") if isinstance(fields, str) else fields) if name.strip()]
+        field_out = fedm.Field_output(problem, fields, species_names=deck["file_names"])
+        field_files = file_io.output_files("pvd", "fields", [name.replace(":", "_") for name in fields])
+        for writer in field_files:
+            writer.mesh = mesh
+    if axis_profile is not None:
+        # its own set-up on the same problem: the requests go with a call, the points belong to the context
+        z_axis = np.linspace(0.0, GAP, AXIS_POINTS)
+        profile = fedm.Field_output(problem, AXIS_FIELDS, probes=np.column_stack([0.0 * z_axis, z_axis]),
+                                    species_names=deck["file_names"])
+        profile_rows = open(axis_profile, "w")
+        profile_rows.write("# t, then %s at %d points each on r = 0; first row: nan and the points' z per field\n"
+                           % (", ".join(AXIS_FIELDS), AXIS_POINTS))
+        profile_rows.write(" ".join(f"{x:.17g}" for x in [float("nan"), *np.tile(z_axis, len(AXIS_FIELDS))]) + "\n")
+    field_window, field_stride, outputs = OUTPUT_WINDOWS[0], OUTPUT_STRIDES[0], 0
     step_errors, recent_errors, steps = [0.0] * (ns + 1), [1] * 3, 0
     while t < T_final:
         t_before = t
@@ -316,7 +341,20 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
             # (here, before anything of the next step reaches the device: the balance of the residual just solved)
             rows.write(" ".join(repr(float(v)) for v in balance_row(t, balance_of())) + "\n")
             rows.flush()
-        dis.energy.vector()[:] = np.exp(dis.w_now.vector()[:] - dis.dens_now[ns - 1].vector()[:])
+        if profile is not None:     # (here too: the state and the table of the residual just solved)
+            p = profile()["probes"]
+            profile_rows.write(" ".join(f"{x:.17g}" for x in [t, *p.ravel()]) + "\n")
+            profile_rows.flush()
+        if field_out is not None:
+            from fedm_amd.mesh_io import output_times
+            due, (field_window, field_stride) = output_times(t, field_window, field_stride, OUTPUT_WINDOWS, OUTPUT_STRIDES)
+            if due:                 # one set per accepted step that reaches an output time, at the step's own time
+                outputs += 1
+                if outputs % max(1, int(fields_every)) == 0:
+                    values = field_out()
+                    for name, writer in zip(fields, field_files):
+                        writer.write(values[name], name, t)
+        dis.energy.vector()[:] =np.exp(dis.w_now.vector()[:] - dis.dens_now[ns - 1].vector()[:])
         window, stride = file_io.file_output(t, t_before, window, stride, OUTPUT_WINDOWS, OUTPUT_STRIDES,
                                              ["pvd"] + ["xdmf"] * (ns - 1), out_files, out_names, out_now, out_before,
                                              unit="us")
@@ -326,6 +364,8 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
         steps += 1
     if rows is not None:
         rows.close()
+    if profile_rows is not None:
+        profile_rows.close()
     return dict(t=t, steps=steps, output=str(file_io.files.output_folder_path), species=deck["file_names"],
                 error_file=str(file_io.files.error_file), problem=problem)
 
@@ -335,6 +375,13 @@ if __name__ == "__main__":
     ap.add_argument("out", nargs="?", default="gd_output")
     ap.add_argument("--balance", metavar="FILE", help="write the particle and energy balance per accepted step")
     ap.add_argument("--balance-every", type=int, default=1, metavar="N", help="... every N-th accepted step")
+    ap.add_argument("--fields", metavar="LIST",
+                    help="comma-separated derived fields written at the output times: mean_energy, reduced_field, E_norm, "
+                         "E_r, E_z, charge, density:s, state:e, table:f, rate:j, source:s, collision_loss, joule, "
+                         "flux_r:s, flux_z:s, current_r, current_z (s: a species' index or name; 0 is the energy)")
+    ap.add_argument("--fields-every", type=int, default=1, metavar="N", help="... at every N-th output time")
+    ap.add_argument("--axis-profile", metavar="FILE", help="write the profiles of %s on r = 0 per accepted step" % ", ".join(AXIS_FIELDS))
     a = ap.parse_args()
-    result = main(output_dir=a.out, quiet=False, balance=a.balance, balance_every=a.balance_every)
+    result = main(output_dir=a.out, quiet=False, balance=a.balance, balance_every=a.balance_every, fields=a.fields,
+                  fields_every=a.fields_every, axis_profile=a.axis_profile)
     print({k: v for k, v in result.items() if k != "problem"})

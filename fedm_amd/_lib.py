@@ -257,6 +257,10 @@ _SIGNATURES = {
     "fedm_probe_setup": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), _D]),
     "fedm_fields": (C.c_int, [_P, C.POINTER(FieldOpts), C.c_int, C.POINTER(FieldReq), _D, _D, C.POINTER(C.c_int32),
                               C.POINTER(C.c_int32)]),
+    "fedm_gd_fields_setup": (C.c_int, [_P, C.POINTER(Csr)]),
+    "fedm_gd_probe_setup": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), _D]),
+    "fedm_gd_fields": (C.c_int, [_P, C.POINTER(FieldOpts), C.c_int, C.POINTER(FieldReq), _D, _D, C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32)]),
     "fedm_block_nnz": (C.c_int64, [_P]),
     "fedm_block_csr": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _D]),
     "fedm_jacobian_poisson_only": (C.c_int, [_P]),

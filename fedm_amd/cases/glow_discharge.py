@@ -60,6 +60,7 @@ class Case:
                        for kx, ky, dep in zip(self.k_x, self.k_y, self.k_dep)]
         ns, n_eq, species, M, sign = ff.modify_approximation_vars("LMEA", ns, species, M, sign)
         self.ns, self.nr = ns, len(kfiles)
+        self.species_names = [str(s) for s in names]            # the deck's file names, the gas first: the model's indices
 
         self.gap = self.wall = 0.01
         # (mesh: any triangle mesh of the 1 cm x 1 cm domain instead of the script's crossed one)
@@ -302,6 +303,21 @@ class Case:
             self._balance = ff.Discharge_balance(self.prob, boundary_tags=(1, 2),
                                                  weighting_potential=self.mesh.coords[:, 1] / self.gap)
         return self._balance()
+
+    def fields(self, requests, probes=None, t_out=None, t_old=None, projection="lumped"):
+        """Derived nodal fields of the device-resident state and field table (``fedm.Field_output`` on the LMEA model; no
+        download): a dict name -> nodal array, with ``"probes"`` -> ``[n_fields, n_points]`` for points ``probes [n, 2]``
+        and ``"finite"``.  Names as ``DeviceProblem.gd_fields`` takes them, species by index or by the deck's names.  The
+        kinds of a state alone and of the potential alone blend to ``t_out`` between ``t_old`` and the current time when
+        both are given; the residual-evaluated kinds are those of the step just solved (between its solve and the next
+        step's refresh: what ``balance()`` says about the mean-energy row holds here too).  The set-up is made at the
+        first call and again when the names, the points or the projection change."""
+        key = (tuple(requests), None if probes is None else np.asarray(probes, dtype=np.float64).tobytes(), projection)
+        if getattr(self, "_fields_key", None) != key:
+            self._fields = ff.Field_output(self.prob, list(requests), probes=probes, projection=projection,
+                                           species_names=self.species_names)
+            self._fields_key = key
+        return self._fields(t_out, t_old, None if t_out is None else self.t)
 
     def run(self):
         while self.t < self.T_final:

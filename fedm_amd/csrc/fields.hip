@@ -4,7 +4,9 @@
 // pointwise kinds from the state, projected kinds by adding the vertex's entries in the ascending (cell, corner) order of
 // the list -- photo.hip's store-then-sum load vector), the blend of two states, the probes, and one read-back.  Plain
 // launches on the context's stream; no kernel caps its grid, none waits for another workgroup, and nothing adds with
-// floating-point atomics: a call is bitwise reproducible.
+// floating-point atomics: a call is bitwise reproducible.  The set-up, the consistent solve, the blend, the probes and
+// the read-back serve the LMEA family's fedm_gd_fields as well (gd_fields.hip has its cell and vertex pass): fields.hpp
+// declares what the two share.
 #include "fields.hpp"
 
 #include <algorithm>
@@ -243,12 +245,14 @@ void fields_release(Ctx &c) {
     c.fields = nullptr;
 }
 
-namespace {
-
-int refuse(const char *who, const std::string &why) {
+int fields_refuse(const char *who, const std::string &why) {
     set_error(std::string(who) + ": " + why);
     return -2;
 }
+
+namespace {
+
+int refuse(const char *who, const std::string &why) { return fields_refuse(who, why); }
 
 // the contexts the cell kernel is instantiated for (0), or the refusal
 int check_ctx(const Ctx &c, const char *who) {
@@ -266,7 +270,7 @@ int device_array(T *&dst, const T *src, size_t n) {
     return 0;
 }
 
-int setup_impl(Ctx &c, const fedm_csr *mass) {
+int setup_impl(Ctx &c, const fedm_csr *mass, const char *who) {
     Fields &f = *c.fields;
     std::vector<int> cells((size_t)3 * c.nc);
     std::vector<double> coords((size_t)2 * c.nv);
@@ -302,10 +306,10 @@ int setup_impl(Ctx &c, const fedm_csr *mass) {
         f.M.single = false;
         const int rc = f.M.from_csr(*mass, true);
         if (rc) {
-            set_error("fedm_fields_setup: mass matrix upload failed (bad CSR or out of memory)");
+            set_error(std::string(who) + ": mass matrix upload failed (bad CSR or out of memory)");
             return rc < -1 ? -2 : -1;
         }
-        if (f.M.n_rows_p != c.nvp) return refuse("fedm_fields_setup", "the mass matrix's padded rows differ from the context's");
+        if (f.M.n_rows_p != c.nvp) return refuse(who, "the mass matrix's padded rows differ from the context's");
         f.cg = new Photo();
         if (device_array<double>(f.rhs, nullptr, nvp) || device_array<double>(f.cg->r, nullptr, nvp) ||
             device_array<double>(f.cg->z, nullptr, nvp) || device_array<double>(f.cg->p, nullptr, nvp) ||
@@ -341,9 +345,8 @@ void with_model_flags(const Ctx &c, Fn &&fn) {
 
 bool projected(int kind) { return kind >= FEDM_FIELD_E_R && kind <= FEDM_FIELD_FLUX_Z; }
 
-// X(state) of every request into dst[n_req][nvp].  Returns 0, or FEDM_DIVERGED_LINEAR when a solve stopped at max_it.
-int evaluate(Ctx &c, const double *u, const FieldCellReqs &cq, const FieldVertexReqs &vq, const fedm_field_opts &o,
-             double *dst, int *its) {
+// the LFA family's cell and vertex pass: X(state) of every request into dst[n_req][nvp]
+void launch_lfa(Ctx &c, const double *u, const FieldCellReqs &cq, const FieldVertexReqs &vq, int raw, double *dst) {
     Fields &f = *c.fields;
     const dim3 b(FIELDS_THREADS);
     if (cq.n > 0)
@@ -353,18 +356,26 @@ int evaluate(Ctx &c, const double *u, const FieldCellReqs &cq, const FieldVertex
             hipLaunchKernelGGL((fields_cell_kernel<NS, PO, TAB>), dim3((c.nc + FIELDS_THREADS - 1) / FIELDS_THREADS), b, 0,
                                c.stream, c.nc, c.d_model, c.d_coords, c.d_cells, u, cq, f.cell_b);
         });
-    const int raw = o.projection == 1 ? 1 : 0;
     hipLaunchKernelGGL(fields_vertex_kernel, dim3((c.nvp + FIELDS_THREADS - 1) / FIELDS_THREADS, vq.n), b, 0, c.stream,
                        c.n_owned, c.nvp, c.nc, c.ns, c.neq, c.d_model, u, f.v_ptr, f.v_idx, f.m, f.cell_b, vq, raw, dst,
                        f.flag);
+}
+
+// X(state) of every request into dst[n_req][nvp].  Returns 0, or FEDM_DIVERGED_LINEAR when a solve stopped at max_it.
+int evaluate(Ctx &c, const double *u, int n_req, const int *slot, const FieldsLaunch &launch, const fedm_field_opts &o,
+             double *dst, int *its) {
+    Fields &f = *c.fields;
+    const dim3 b(FIELDS_THREADS);
+    const int raw = o.projection == 1 ? 1 : 0;
+    launch(u, raw, dst);
     int rc = 0;
     if (raw) {
         // the load vector of request k sits in dst[k]: it moves to rhs, and dst[k] becomes the solution from 0.
         // scalar_pcg takes its scratch vectors from Ctx::photo: ours stand in for the duration of the solve.
         Photo *const kept = c.photo;
         c.photo = f.cg;
-        for (int k = 0; k < vq.n; ++k) {
-            if (vq.slot[k] < 0) continue;
+        for (int k = 0; k < n_req; ++k) {
+            if (slot[k] < 0) continue;
             double *x = dst + (size_t)k * c.nvp;
             hipMemcpyAsync(f.rhs, x, sizeof(double) * c.nvp, hipMemcpyDeviceToDevice, c.stream);
             hipMemsetAsync(x, 0, sizeof(double) * c.nvp, c.stream);
@@ -384,17 +395,8 @@ int evaluate(Ctx &c, const double *u, const FieldCellReqs &cq, const FieldVertex
 }
 
 }  // namespace
-}  // namespace fedm
 
-using namespace fedm;
-
-extern "C" {
-
-int fedm_fields_setup(fedm_ctx *h, const fedm_csr *mass) {
-    const char *who = "fedm_fields_setup";
-    if (!h) return refuse(who, "null context");
-    Ctx &c = h->c;
-    if (const int rc = check_ctx(c, who)) return rc;
+int fields_setup_shared(Ctx &c, const fedm_csr *mass, const char *who) {
     if (mass) {
         if (c.n_owned != c.nv)
             return refuse(who, "the consistent projection runs on one GPU (this context has ghost vertices): no mass matrix");
@@ -406,17 +408,14 @@ int fedm_fields_setup(fedm_ctx *h, const fedm_csr *mass) {
     FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
     fields_release(c);
     c.fields = new Fields();
-    const int rc = setup_impl(c, mass);
+    const int rc = setup_impl(c, mass, who);
     if (rc != 0) fields_release(c);
     return rc;
 }
 
-int fedm_probe_setup(fedm_ctx *h, int n_points, const int32_t *vertices, const double *weights) {
-    const char *who = "fedm_probe_setup";
-    if (!h) return refuse(who, "null context");
-    Ctx &c = h->c;
-    if (const int rc = check_ctx(c, who)) return rc;
-    if (!c.fields) return refuse(who, "fedm_fields_setup has not been called");
+int fields_probe_setup_shared(Ctx &c, int n_points, const int32_t *vertices, const double *weights, const char *who,
+                              const char *setup_name) {
+    if (!c.fields) return refuse(who, std::string(setup_name) + " has not been called");
     if (c.n_owned != c.nv) return refuse(who, "probes run on one GPU (this context has ghost vertices)");
     if (n_points < 0 || (n_points > 0 && (!vertices || !weights))) return refuse(who, "points without their arrays");
     for (int p = 0; p < n_points; ++p)
@@ -446,15 +445,8 @@ int fedm_probe_setup(fedm_ctx *h, int n_points, const int32_t *vertices, const d
     return 0;
 }
 
-int fedm_fields(fedm_ctx *h, const fedm_field_opts *opts, int n_req, const fedm_field_req *req, double *nodal,
-                double *probes, int32_t *finite, int32_t *cg_iterations) {
-    const char *who = "fedm_fields";
-    if (!h || !opts || !req || !finite) return refuse(who, "null argument");
-    Ctx &c = h->c;
-    if (const int rc = check_ctx(c, who)) return rc;
-    if (!c.fields) return refuse(who, "fedm_fields_setup has not been called");
-    Fields &f = *c.fields;
-    const fedm_field_opts &o = *opts;
+int fields_check_opts(const Ctx &c, const fedm_field_opts &o, int n_req, const char *who, const char *setup_name) {
+    if (!c.fields) return refuse(who, std::string(setup_name) + " has not been called");
     if (n_req < 1 || n_req > FEDM_FIELDS_MAX_REQ)
         return refuse(who, std::to_string(n_req) + " requests, 1 to " + std::to_string(FEDM_FIELDS_MAX_REQ) + " are possible");
     if (!std::isfinite(o.num) || !std::isfinite(o.den)) return refuse(who, "num or den of the blend is not finite");
@@ -462,6 +454,99 @@ int fedm_fields(fedm_ctx *h, const fedm_field_opts *opts, int n_req, const fedm_
     if (o.projection != 0 && o.projection != 1)
         return refuse(who, "projection " + std::to_string(o.projection) + ": 0 (lumped) or 1 (consistent)");
     if (!std::isfinite(o.rtol)) return refuse(who, "rtol is not finite");
+    return 0;
+}
+
+int fields_check_projection(const Ctx &c, const fedm_field_opts &o, bool probes, const char *who, const char *setup_name,
+                            const char *probe_name) {
+    const Fields &f = *c.fields;
+    if (o.projection == 1) {
+        if (c.n_owned != c.nv) return refuse(who, "the consistent projection runs on one GPU (this context has ghost vertices)");
+        if (!f.have_mass)
+            return refuse(who, "the consistent projection needs the mass matrix of " + std::string(setup_name) + ", and none was given");
+        if (!(o.rtol > 0.0) || o.max_it < 1) return refuse(who, "the consistent projection needs rtol > 0 and max_it >= 1");
+    }
+    if (probes && f.n_points == 0) return refuse(who, "probes asked for, and " + std::string(probe_name) + " has set no points");
+    return 0;
+}
+
+int fields_run(Ctx &c, const fedm_field_opts &o, int n_req, const int *slot, bool any_projected, const FieldsLaunch &launch,
+               double *nodal, double *probes, int32_t *finite, int32_t *cg_iterations) {
+    Fields &f = *c.fields;
+    const bool solve = o.projection == 1 && any_projected;
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    const bool want_new = o.num != 0.0, want_old = o.num != o.den;
+    if (want_new && c.halo_pending) {   // (several GPUs: the ghost entries of u_new are exchanged lazily)
+        comm_halo(c, c.d_u);
+        c.halo_pending = false;
+    }
+    fedm_field_opts o_run = o;
+    if (!solve) o_run.projection = 0;   // (nothing projected: nothing to solve)
+    int its[FEDM_FIELDS_MAX_REQ] = {0};
+    FEDM_HIP_CHECK(hipMemsetAsync(f.flag, 0, sizeof(int), c.stream));
+    int rc = 0;
+    if (want_old && want_new) {
+        rc = evaluate(c, c.d_uold, n_req, slot, launch, o_run, f.first, its);
+        const int rc2 = evaluate(c, c.d_u, n_req, slot, launch, o_run, f.out, its);
+        if (rc == 0) rc = rc2;
+        const size_t n = (size_t)n_req * c.nvp;
+        hipLaunchKernelGGL(fields_blend_kernel, dim3((unsigned)((n + FIELDS_THREADS - 1) / FIELDS_THREADS)),
+                           dim3(FIELDS_THREADS), 0, c.stream, n, o.num, o.den, f.first, f.out, f.flag);
+    } else {
+        rc = evaluate(c, want_new ? c.d_u : c.d_uold, n_req, slot, launch, o_run, f.out, its);
+    }
+    if (probes) {
+        const int n = f.n_points * n_req;
+        hipLaunchKernelGGL(fields_probe_kernel, dim3((n + FIELDS_THREADS - 1) / FIELDS_THREADS), dim3(FIELDS_THREADS), 0,
+                           c.stream, f.n_points, n_req, c.nvp, f.p_vert, f.p_w, f.out, f.p_out);
+        FEDM_HIP_CHECK(hipMemcpyAsync(probes, f.p_out, sizeof(double) * n, hipMemcpyDeviceToHost, c.stream));
+    }
+    // the nodal results come down in one copy into pinned memory and are unpadded from there (a copy straight into the
+    // caller's pageable rows measured 2.7 ms for two fields of 341 k vertices, next to 70 us of kernels)
+    if (nodal)
+        FEDM_HIP_CHECK(hipMemcpyAsync(f.h_out, f.out, sizeof(double) * n_req * c.nvp, hipMemcpyDeviceToHost, c.stream));
+    int flag = 0;
+    FEDM_HIP_CHECK(hipMemcpyAsync(&flag, f.flag, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    FEDM_HIP_CHECK(hipGetLastError());
+    for (int k = 0; nodal && k < n_req; ++k)
+        std::memcpy(nodal + (size_t)k * c.nv, f.h_out + (size_t)k * c.nvp, sizeof(double) * c.nv);
+    *finite = flag ? 0 : 1;
+    if (cg_iterations)
+        for (int k = 0; k < n_req; ++k) cg_iterations[k] = its[k];
+    return rc;
+}
+
+}  // namespace fedm
+
+using namespace fedm;
+
+extern "C" {
+
+int fedm_fields_setup(fedm_ctx *h, const fedm_csr *mass) {
+    const char *who = "fedm_fields_setup";
+    if (!h) return refuse(who, "null context");
+    Ctx &c = h->c;
+    if (const int rc = check_ctx(c, who)) return rc;
+    return fields_setup_shared(c, mass, who);
+}
+
+int fedm_probe_setup(fedm_ctx *h, int n_points, const int32_t *vertices, const double *weights) {
+    const char *who = "fedm_probe_setup";
+    if (!h) return refuse(who, "null context");
+    Ctx &c = h->c;
+    if (const int rc = check_ctx(c, who)) return rc;
+    return fields_probe_setup_shared(c, n_points, vertices, weights, who, "fedm_fields_setup");
+}
+
+int fedm_fields(fedm_ctx *h, const fedm_field_opts *opts, int n_req, const fedm_field_req *req, double *nodal,
+                double *probes, int32_t *finite, int32_t *cg_iterations) {
+    const char *who = "fedm_fields";
+    if (!h || !opts || !req || !finite) return refuse(who, "null argument");
+    Ctx &c = h->c;
+    if (const int rc = check_ctx(c, who)) return rc;
+    const fedm_field_opts &o = *opts;
+    if (const int rc = fields_check_opts(c, o, n_req, who, "fedm_fields_setup")) return rc;
     FieldCellReqs cq{};
     FieldVertexReqs vq{};
     vq.n = n_req;
@@ -501,55 +586,10 @@ int fedm_fields(fedm_ctx *h, const fedm_field_opts *opts, int n_req, const fedm_
             ++cq.n;
         }
     }
-    const bool solve = o.projection == 1 && cq.n > 0;
-    if (o.projection == 1) {
-        if (c.n_owned != c.nv) return refuse(who, "the consistent projection runs on one GPU (this context has ghost vertices)");
-        if (!f.have_mass) return refuse(who, "the consistent projection needs the mass matrix of fedm_fields_setup, and none was given");
-        if (!(o.rtol > 0.0) || o.max_it < 1) return refuse(who, "the consistent projection needs rtol > 0 and max_it >= 1");
-    }
-    if (probes && f.n_points == 0) return refuse(who, "probes asked for, and fedm_probe_setup has set no points");
-    FEDM_HIP_CHECK(hipSetDevice(c.device));
-    const bool want_new = o.num != 0.0, want_old = o.num != o.den;
-    if (want_new && c.halo_pending) {   // (several GPUs: the ghost entries of u_new are exchanged lazily)
-        comm_halo(c, c.d_u);
-        c.halo_pending = false;
-    }
-    const FieldVertexReqs &vq_run = vq;
-    fedm_field_opts o_run = o;
-    if (!solve) o_run.projection = 0;   // (nothing projected: nothing to solve)
-    int its[FEDM_FIELDS_MAX_REQ] = {0};
-    FEDM_HIP_CHECK(hipMemsetAsync(f.flag, 0, sizeof(int), c.stream));
-    int rc = 0;
-    if (want_old && want_new) {
-        rc = evaluate(c, c.d_uold, cq, vq_run, o_run, f.first, its);
-        const int rc2 = evaluate(c, c.d_u, cq, vq_run, o_run, f.out, its);
-        if (rc == 0) rc = rc2;
-        const size_t n = (size_t)n_req * c.nvp;
-        hipLaunchKernelGGL(fields_blend_kernel, dim3((unsigned)((n + FIELDS_THREADS - 1) / FIELDS_THREADS)),
-                           dim3(FIELDS_THREADS), 0, c.stream, n, o.num, o.den, f.first, f.out, f.flag);
-    } else {
-        rc = evaluate(c, want_new ? c.d_u : c.d_uold, cq, vq_run, o_run, f.out, its);
-    }
-    if (probes) {
-        const int n = f.n_points * n_req;
-        hipLaunchKernelGGL(fields_probe_kernel, dim3((n + FIELDS_THREADS - 1) / FIELDS_THREADS), dim3(FIELDS_THREADS), 0,
-                           c.stream, f.n_points, n_req, c.nvp, f.p_vert, f.p_w, f.out, f.p_out);
-        FEDM_HIP_CHECK(hipMemcpyAsync(probes, f.p_out, sizeof(double) * n, hipMemcpyDeviceToHost, c.stream));
-    }
-    // the nodal results come down in one copy into pinned memory and are unpadded from there (a copy straight into the
-    // caller's pageable rows measured 2.7 ms for two fields of 341 k vertices, next to 70 us of kernels)
-    if (nodal)
-        FEDM_HIP_CHECK(hipMemcpyAsync(f.h_out, f.out, sizeof(double) * n_req * c.nvp, hipMemcpyDeviceToHost, c.stream));
-    int flag = 0;
-    FEDM_HIP_CHECK(hipMemcpyAsync(&flag, f.flag, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
-    FEDM_HIP_CHECK(hipGetLastError());
-    for (int k = 0; nodal && k < n_req; ++k)
-        std::memcpy(nodal + (size_t)k * c.nv, f.h_out + (size_t)k * c.nvp, sizeof(double) * c.nv);
-    *finite = flag ? 0 : 1;
-    if (cg_iterations)
-        for (int k = 0; k < n_req; ++k) cg_iterations[k] = its[k];
-    return rc;
+    if (const int rc = fields_check_projection(c, o, probes != nullptr, who, "fedm_fields_setup", "fedm_probe_setup")) return rc;
+    return fields_run(c, o, n_req, vq.slot, cq.n > 0,
+                      [&](const double *u, int raw_sums, double *dst) { launch_lfa(c, u, cq, vq, raw_sums, dst); }, nodal,
+                      probes, finite, cg_iterations);
 }
 
 }  // extern "C"

@@ -1082,8 +1082,71 @@ class DeviceProblem:
         names = species_names if species_names is not None else getattr(self, "species_names", None)
         pairs = [field_output.parse_request(r, self.model.n_species, self.n_eq, len(self.model.reactions), names)
                  for r in requests]
+        return self._fields_call("fedm_fields", "fields", requests, pairs, t_out, t_old, t, projection, rtol, nodal, probes,
+                                 max_it)
+
+    # -- field output of LMEA models (csrc/gd_fields.hip) --------------------------------
+    def gd_fields_setup(self, consistent=False):
+        """:meth:`fields_setup` for an LMEA model (``fedm_gd_fields_setup``): what :meth:`gd_fields` needs once;
+        ``consistent``: the P1 mass matrix of the plain measure as well.  Replaces an earlier set-up and drops its probe
+        points."""
+        if not isinstance(self.model, GdModel):
+            raise RuntimeError("gd_fields: LMEA models only (fields() has the LFA family's)")
+        mass = None
+        if consistent:
+            from . import amg, field_output
+            keep = []
+            mass = amg._csr_struct(field_output.mass_matrix(self._coords_dev, self._cells_dev), keep)
+        self._check(self.lib.fedm_gd_fields_setup(self._h, C.byref(mass) if mass is not None else None),
+                    "fedm_gd_fields_setup")
+        self._fields_ready, self._n_probe_points = True, 0
+
+    def gd_probe_setup(self, points):
+        """:meth:`probe_setup` for an LMEA model (``fedm_gd_probe_setup``): probe points ``[n, 2]`` for
+        :meth:`gd_fields`; a point on an edge or a vertex goes to the lowest cell index, a point outside the mesh is a
+        ``ValueError`` naming it.  Returns ``(cells, weights)``."""
+        from . import field_output
+        if not isinstance(self.model, GdModel):
+            raise RuntimeError("gd_fields: LMEA models only (fields() has the LFA family's)")
+        if not getattr(self, "_fields_ready", False):
+            self.gd_fields_setup()
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+        cell, w = field_output.locate_points(self.coords, self.cells, pts)
+        verts = np.ascontiguousarray(self._inv[self.cells[cell]], dtype=np.int32)
+        w = np.ascontiguousarray(w)
+        self._check(self.lib.fedm_gd_probe_setup(self._h, int(pts.shape[0]), verts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 _dp(w)), "fedm_gd_probe_setup")
+        self._n_probe_points = int(pts.shape[0])
+        return cell, w
+
+    def gd_fields(self, requests, t_out=None, t_old=None, t=None, projection="lumped", rtol=1e-10, nodal=True,
+                  probes=False, max_it=10000, species_names=None):
+        """Derived fields of an LMEA model from the resident state and the field table (``fedm_gd_fields``;
+        include/fedm_hip.h has the definitions).  ``requests``: up to 8 names -- ``"state:e"``, ``"density:s"``,
+        ``"charge"``, ``"mean_energy"`` (pointwise, from a state), ``"table:f"`` (a row of the field table), ``"E_r"``,
+        ``"E_z"``, ``"E_norm"``, ``"reduced_field"`` (projected, from the potential), ``"rate:j"``, ``"source:s"``,
+        ``"collision_loss"``, ``"joule"``, ``"flux_r:s"``, ``"flux_z:s"``, ``"current_r"``, ``"current_z"`` (projected, as
+        the residual of the current step evaluates them) -- or ``(kind, index)`` pairs; ``s`` an index or one of
+        ``species_names`` (the gas is 0; component 0 is the energy).  Times blend as in :meth:`fields`; the
+        residual-evaluated kinds and ``table`` belong to the current step and take no ``t_out != t``.  Returns a
+        :class:`FieldValues` in the caller's vertex order."""
+        from . import field_output
+        if not isinstance(self.model, GdModel):
+            raise RuntimeError("gd_fields: LMEA models only (fields() has the LFA family's)")
+        if projection not in ("lumped", "consistent"):
+            raise ValueError('gd_fields: projection is "lumped" or "consistent"')
+        if not getattr(self, "_fields_ready", False):
+            self.gd_fields_setup(consistent=projection == "consistent")
+        names = species_names if species_names is not None else getattr(self, "species_names", None)
+        pairs = [field_output.parse_gd_request(r, self.model.n_species, self.model.n_reactions, self.model.n_fields, names)
+                 for r in requests]
+        return self._fields_call("fedm_gd_fields", "gd_fields", requests, pairs, t_out, t_old, t, projection, rtol, nodal,
+                                 probes, max_it)
+
+    def _fields_call(self, entry, what, requests, pairs, t_out, t_old, t, projection, rtol, nodal, probes, max_it):
+        """One call of ``fedm_fields`` or ``fedm_gd_fields`` (``entry``) with the parsed ``pairs``."""
         if not 1 <= len(pairs) <= _lib.FIELDS_MAX_REQ:
-            raise ValueError(f"fields: 1 to {_lib.FIELDS_MAX_REQ} requests a call, got {len(pairs)}")
+            raise ValueError(f"{what}: 1 to {_lib.FIELDS_MAX_REQ} requests a call, got {len(pairs)}")
         req = (_lib.FieldReq * len(pairs))()
         for k, (kind, index) in enumerate(pairs):
             req[k].kind, req[k].index = kind, index
@@ -1092,25 +1155,25 @@ class DeviceProblem:
             opts.num = opts.den = 1.0
         else:
             if t_old is None or t is None:
-                raise ValueError("fields: t_out goes with t_old and t")
+                raise ValueError(f"{what}: t_out goes with t_old and t")
             opts.num, opts.den = float(t_out) - float(t_old), float(t) - float(t_old)
         opts.projection, opts.max_it, opts.rtol = (1 if projection == "consistent" else 0), int(max_it), float(rtol)
         n_points = getattr(self, "_n_probe_points", 0)
         if probes and not n_points:
-            raise RuntimeError("fields: probes=True needs probe_setup(points) first")
+            raise RuntimeError(f"{what}: probes=True needs {'gd_' if what.startswith('gd_') else ''}probe_setup(points) first")
         out_n = np.empty((len(pairs), self.nv)) if nodal else None
         out_p = np.empty((len(pairs), n_points)) if probes else None
         finite = C.c_int32(0)
         its = (C.c_int32 * len(pairs))()
         import time
         t0 = time.perf_counter()
-        rc = self.lib.fedm_fields(self._h, C.byref(opts), len(pairs), req, _dp(out_n) if nodal else None,
-                                  _dp(out_p) if probes else None, C.byref(finite), its)
+        rc = getattr(self.lib, entry)(self._h, C.byref(opts), len(pairs), req, _dp(out_n) if nodal else None,
+                                         _dp(out_p) if probes else None, C.byref(finite), its)
         self.last_fields_call_seconds = time.perf_counter() - t0     # (the library's share; the rest is the reordering here)
         if rc == 3:
-            raise RuntimeError(f"fedm_fields: conjugate gradients stopped at max_it = {max_it} "
+            raise RuntimeError(f"{entry}: conjugate gradients stopped at max_it = {max_it} "
                                f"(iterations per request {[int(v) for v in its]})")
-        self._check(rc, "fedm_fields")
+        self._check(rc, entry)
         return FieldValues(names=[r if isinstance(r, str) else tuple(r) for r in requests],
                            # (np.take along the rows: five times faster than out_n[:, self._inv] at 341 k vertices)
                            nodal=np.take(out_n, self._inv, axis=1) if nodal else None, probes=out_p,

@@ -9,6 +9,16 @@ KINDS = {"state": 0, "density": 1, "charge": 2, "e_r": 3, "e_z": 4, "e_norm": 5,
 INDEXED = {"state", "density", "rate", "flux_r", "flux_z"}
 PROJECTED = {"e_r", "e_z", "e_norm", "rate", "flux_r", "flux_z"}
 MAX_REQUESTS = 8
+# the LMEA family's kinds (include/fedm_hip.h, FEDM_GD_FIELD_*): component 0 is the energy, species 0 the gas
+GD_KINDS = {"state": 32, "density": 33, "charge": 34, "mean_energy": 35, "table": 36, "e_r": 37, "e_z": 38, "e_norm": 39,
+            "reduced_field": 40, "rate": 41, "source": 42, "collision_loss": 43, "joule": 44, "flux_r": 45, "flux_z": 46,
+            "current_r": 47, "current_z": 48}
+GD_INDEXED = {"state", "density", "table", "rate", "source", "flux_r", "flux_z"}
+GD_BY_SPECIES = {"density", "source", "flux_r", "flux_z"}          # their index may be a species name
+GD_POTENTIAL_ONLY = {"e_r", "e_z", "e_norm", "reduced_field"}
+# evaluated as the residual of the current step evaluates them (u_new, the field table as it stands): no blend
+GD_OF_THE_STEP = {"table", "rate", "source", "collision_loss", "joule", "flux_r", "flux_z", "current_r", "current_z"}
+GD_PROJECTED = GD_POTENTIAL_ONLY | (GD_OF_THE_STEP - {"table"})
 
 
 def mass_matrix(coords, cells):
@@ -103,3 +113,46 @@ def parse_request(name, n_species, n_eq, n_reactions, species_names=None):
     elif tail not in ("", None):
         raise ValueError(f"field '{name}': '{key}' takes no index")
     return KINDS[key], index
+
+
+def gd_kind_name(request):
+    """The kind of a request of :func:`parse_gd_request` as a lower-case name (``"rate"`` of ``"rate:3"``)."""
+    head = request.partition(":")[0] if isinstance(request, str) else request[0]
+    if isinstance(head, str):
+        return head.strip().lower()
+    return next((k for k, v in GD_KINDS.items() if v == int(head)), None)
+
+
+def parse_gd_request(name, n_species, n_reactions, n_fields, species_names=None):
+    """``(kind, index)`` of a field name of the LMEA family: ``"state:e"``, ``"density:s"``, ``"charge"``,
+    ``"mean_energy"``, ``"table:f"``, ``"E_r"``, ``"E_z"``, ``"E_norm"``, ``"reduced_field"``, ``"rate:j"``, ``"source:s"``,
+    ``"collision_loss"``, ``"joule"``, ``"flux_r:s"``, ``"flux_z:s"``, ``"current_r"``, ``"current_z"``.  ``s`` is an index
+    or one of ``species_names`` (the gas is index 0; component 0 is the energy: ``"density:0"`` is the energy density and
+    ``"flux_z:0"`` the energy flux; ``"source"`` starts at 1).  A pair ``(kind, index)`` passes through (kind a name or a
+    number)."""
+    if isinstance(name, str):
+        head, _, tail = name.partition(":")
+    else:
+        head, tail = name[0], name[1] if len(name) > 1 else ""
+    key = gd_kind_name(name)
+    if key not in GD_KINDS:
+        raise ValueError(f"field {name!r}: unknown kind {head!r} (one of {', '.join(sorted(GD_KINDS))})")
+    index = 0
+    if key in GD_INDEXED:
+        if tail == "" or tail is None:
+            raise ValueError(f"field '{name}': '{key}' needs an index ('{key}:1')")
+        names = list(species_names or ())
+        if isinstance(tail, str) and tail.strip() in names and key in GD_BY_SPECIES:
+            index = names.index(tail.strip())
+        else:
+            try:
+                index = int(tail)
+            except (TypeError, ValueError):
+                raise ValueError(f"field '{name}': '{tail}' is neither an index nor one of the species {names}") from None
+        first = 1 if key == "source" else 0
+        limit = {"state": n_species + 1, "rate": n_reactions, "table": n_fields}.get(key, n_species)
+        if not first <= index < limit:
+            raise ValueError(f"field '{name}': index {index} out of range ({first} to {limit - 1})")
+    elif tail not in ("", None):
+        raise ValueError(f"field '{name}': '{key}' takes no index")
+    return GD_KINDS[key], index

@@ -1002,9 +1002,13 @@ def Discharge_balance(problem, boundary_tags=(), weighting_potential=None):
 def Field_output(problem, fields, probes=None, projection="lumped", species_names=None):
     """Extension (what the reference's scripts do with ``project(...)`` and ``file_output``, fedm-gd.py:309,432): derived
     nodal fields of the device-resident state, blended to an output time, without downloading the state.  ``problem``:
-    a :class:`Problem` (or its device problem) of an LFA model.  ``fields``: up to 8 names -- ``"E_norm"``, ``"E_r"``,
+    a :class:`Problem` (or its device problem).  ``fields``: up to 8 names -- ``"E_norm"``, ``"E_r"``,
     ``"E_z"`` (the cell-constant field, projected), ``"charge"``, ``"density:s"``, ``"state:e"`` (pointwise),
-    ``"rate:j"``, ``"flux_r:s"``, ``"flux_z:s"`` (projected); ``s`` an index or one of ``species_names``.  ``probes``:
+    ``"rate:j"``, ``"flux_r:s"``, ``"flux_z:s"`` (projected); ``s`` an index or one of ``species_names``.  An LMEA model
+    has ``"mean_energy"``, ``"reduced_field"``, ``"table:f"``, ``"source:s"``, ``"collision_loss"``, ``"joule"``,
+    ``"current_r"`` and ``"current_z"`` as well (``DeviceProblem.gd_fields``; component 0 is the energy, species 0 the
+    gas); there the rates, sources, losses, fluxes and currents are what the residual of the current step evaluates, so
+    times with ``t_out != t`` together with one of them (or ``table``) are a ``ValueError`` naming the kinds.  ``probes``:
     points ``[n, 2]`` at which every field is interpolated as well.  ``projection``: "lumped" or "consistent".
 
     Returns a callable: ``out(t_out=None, t_old=None, t=None)`` gives a dict name -> nodal array [n_vertices] at
@@ -1012,18 +1016,29 @@ def Field_output(problem, fields, probes=None, projection="lumped", species_name
     ``"probes"`` -> ``[n_fields, n_points]`` when points were given and ``"finite"``."""
     from .device import GdModel
     dev = getattr(problem, "device", problem)
-    if isinstance(dev.model, GdModel):
-        raise ValueError("fedm.Field_output: LFA models only (the LMEA family is not covered)")
     fields = list(fields)
     if isinstance(projection, str) and projection not in ("lumped", "consistent"):
         raise ValueError('fedm.Field_output: projection is "lumped" or "consistent"')
-    dev.fields_setup(consistent=projection == "consistent")
+    lmea = isinstance(dev.model, GdModel)
+    setup, probe_setup, call = ((dev.gd_fields_setup, dev.gd_probe_setup, dev.gd_fields) if lmea else
+                                (dev.fields_setup, dev.probe_setup, dev.fields))
+    of_the_step = []
+    if lmea:
+        # an LMEA model: its own kinds ("mean_energy", "reduced_field", "table:f", "source:s", "collision_loss", "joule",
+        # "current_r", "current_z" besides the above; component 0 is the energy, species 0 the gas).  Those the residual
+        # of the current step evaluates, and "table", belong to the new state: they take no blend
+        from . import field_output
+        of_the_step = [name for name in fields if field_output.gd_kind_name(name) in field_output.GD_OF_THE_STEP]
+    setup(consistent=projection == "consistent")
     if probes is not None:
-        dev.probe_setup(probes)
+        probe_setup(probes)
 
     def output(t_out=None, t_old=None, t=None):
-        res = dev.fields(fields, t_out=t_out, t_old=t_old, t=t, projection=projection, probes=probes is not None,
-                         species_names=species_names)
+        if of_the_step and t_out is not None and t is not None and float(t_out) != float(t):
+            raise ValueError(f"fedm.Field_output: {', '.join(map(str, of_the_step))} are evaluated as the residual of the "
+                             f"current step evaluates them and cannot be blended to t_out = {t_out!r} != t = {t!r}")
+        res = call(fields, t_out=t_out, t_old=t_old, t=t, projection=projection, probes=probes is not None,
+                   species_names=species_names)
         out = {name: res.nodal[k] for k, name in enumerate(fields)}
         if probes is not None:
             out["probes"] = res.probes

@@ -246,7 +246,8 @@ const char *fedm_last_error(void);
  *    fedm_photo_setup with fedm_photo_desc and fedm_photo_hierarchy, fedm_photo_update, fedm_photo_get, fedm_photo_stats.
  *    fedm_diag_setup and fedm_diagnostics with fedm_diag_opts and fedm_diag.
  *    fedm_fields_setup, fedm_probe_setup and fedm_fields with fedm_field_req and fedm_field_opts.
- *    fedm_gd_balance_setup and fedm_gd_balance with fedm_gd_balance. */
+ *    fedm_gd_balance_setup and fedm_gd_balance with fedm_gd_balance.
+ *    fedm_gd_fields_setup, fedm_gd_probe_setup and fedm_gd_fields with the FEDM_GD_FIELD_* kinds. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -866,6 +867,67 @@ int fedm_probe_setup(fedm_ctx *ctx, int n_points, const int32_t *vertices, const
  * is not finite; probes asked for without points. */
 int fedm_fields(fedm_ctx *ctx, const fedm_field_opts *opts, int n_req, const fedm_field_req *req, double *nodal,
                 double *probes, int32_t *finite, int32_t *cg_iterations);
+
+/* ---- field output of LMEA models on the device ------------------------------------------------
+ * The same for the LMEA family (fedm_ctx_create_gd), one GPU: where things happen in a glow discharge, without
+ * downloading the states and the field table.  fedm_field_req, fedm_field_opts, FEDM_FIELDS_MAX_REQ, the meaning of num,
+ * den, projection, max_it and rtol, the result layout, the finite flag and the return codes are fedm_fields'.  Notation
+ * is the balance's: ns = n_species; component c = 0 is the energy, c = 1..ns-1 the species (ns-1 the electrons), ns the
+ * potential; species index 0 is the gas.  Kinds (numbers of their own; an LFA kind is an unknown kind here):
+ *  pointwise, from a state alone (may be blended):
+ *   STATE    index = equation e   u_e(v), bitwise
+ *   DENSITY  index = component c  exp(u_c(v)); c = 0: the energy density
+ *   CHARGE   -                    e sum_(s >= 1) sign_s exp(u_s(v)), in ascending order
+ *   MEAN_ENERGY -                 exp(u_0(v) - u_e(v)), as fedm_gd_update_mean_energy forms it
+ *  pointwise, from the field table:
+ *   TABLE    index = row f        row f of fedm_gd_set_fields as it stands, bitwise
+ *  projected, from the potential alone (may be blended):
+ *   E_R, E_Z, E_NORM -            the cell-constant -dPhi/dr, -dPhi/dz, |grad Phi|
+ *   REDUCED_FIELD -               1e21 |grad Phi| / N0, the reference's redE (fedm-gd.py:432)
+ *  projected, as the residual of the current step evaluates it -- u_new, the field table as it stands, the
+ *  semi-implicit coefficients c + c' dme at the quadrature points (fedm_gd_balance's notation):
+ *   RATE     index = reaction j   R_j = k_j N0^p_j0 prod_i n_i^p_ji, multiplied in the residual's order
+ *   SOURCE   index = species s >= 1   sum_j net[j][s] R_j, reactions in ascending order
+ *   COLLISION_LOSS -              sum_j loss_j R_j, the two sentinel losses as the residual takes them
+ *   JOULE    -                    -Gamma_e . E
+ *   FLUX_R, FLUX_Z  index = component c   c >= 1: the flux of the species' row: 0 for 'reaction',
+ *                                 -grad(D n) for 'diffusion-reaction', the drift-diffusion flux otherwise; c = 0: the
+ *                                 energy row's flux, the electrons' with 5/3 D_e, 5/3 mu_e on u_0
+ *   CURRENT_R, CURRENT_Z -        e sum_(s >= 1) sign_s Gamma_s, the conduction current density
+ * The kinds of the last group and TABLE have no state selector, for the balance's reason (the table belongs to the
+ * current step): a call that contains one needs num == den.  Called after an accepted step and before the next
+ * fedm_gd_prep_step they are the fields of the step just solved.
+ * Projection is fedm_fields': the plain measure qp_w |det J| at the model's own quadrature points, b_v and m_v added in
+ * ascending (cell, corner) order, no floating-point atomics, lumped or consistent with the mass matrix of the set-up.
+ * Two calls on one state return the same bytes; a call touches no state and no table row. */
+#define FEDM_GD_FIELD_STATE 32
+#define FEDM_GD_FIELD_DENSITY 33
+#define FEDM_GD_FIELD_CHARGE 34
+#define FEDM_GD_FIELD_MEAN_ENERGY 35
+#define FEDM_GD_FIELD_TABLE 36
+#define FEDM_GD_FIELD_E_R 37
+#define FEDM_GD_FIELD_E_Z 38
+#define FEDM_GD_FIELD_E_NORM 39
+#define FEDM_GD_FIELD_REDUCED_FIELD 40
+#define FEDM_GD_FIELD_RATE 41
+#define FEDM_GD_FIELD_SOURCE 42
+#define FEDM_GD_FIELD_COLLISION_LOSS 43
+#define FEDM_GD_FIELD_JOULE 44
+#define FEDM_GD_FIELD_FLUX_R 45
+#define FEDM_GD_FIELD_FLUX_Z 46
+#define FEDM_GD_FIELD_CURRENT_R 47
+#define FEDM_GD_FIELD_CURRENT_Z 48
+/* fedm_fields_setup and fedm_probe_setup for an LMEA context.  Refused (-2, fedm_last_error names the cause): an LFA
+ * context; a context with ghosts; what fedm_fields_setup / fedm_probe_setup refuse for the same arguments. */
+int fedm_gd_fields_setup(fedm_ctx *ctx, const fedm_csr *mass);
+int fedm_gd_probe_setup(fedm_ctx *ctx, int n_points, const int32_t *vertices, const double *weights);
+/* fedm_fields for an LMEA context, with the kinds above.  Refused (-2): an LFA context; a context with ghosts; before
+ * fedm_gd_fields_setup; n_req outside 1..FEDM_FIELDS_MAX_REQ; an unknown kind; an index out of range (SOURCE: 1..ns-1);
+ * a residual-evaluated kind or TABLE with num != den (the message names the request); projection other than 0 or 1, 1
+ * without a mass matrix, 1 with max_it < 1 or rtol <= 0; den == 0; a num, den or rtol that is not finite; probes asked
+ * for without points.  A refused call leaves the next one unaffected. */
+int fedm_gd_fields(fedm_ctx *ctx, const fedm_field_opts *opts, int n_req, const fedm_field_req *req, double *nodal,
+                   double *probes, int32_t *finite, int32_t *cg_iterations);
 
 /* ---- particle and energy balance of LMEA models on the device ------------------------------------
  * What a glow-discharge run is judged by, from the resident state in one pass over the cells, one over the tagged
