@@ -21,6 +21,10 @@ whole per-step pipeline on the GPU.
 conduction currents into the two electrodes, Joule power, collision loss, the imbalances of the energy and particle
 balances and the Shockley-Ramo current with psi = z / gap, all formed on the device without downloading the state (an
 extension: `fedm.Discharge_balance`); off by default.
+`--currents FILE` writes t and the conduction, displacement and total current of the powered and of the grounded
+electrode per accepted step (every N-th with `--currents-every N`): the Shockley-Ramo currents with weighting potentials
+solved for on the device, the displacement part that of the rising voltage (an extension: `fedm.Electrode_currents`);
+off by default.
 
 `--fields LIST` writes derived fields (`mean_energy,E_norm,source:electrons,joule,flux_z:Ar_plus,...`) as VTU series at
 the output times (every N-th of them with `--fields-every N`); `--axis-profile FILE` writes, per accepted step, the
@@ -248,8 +252,18 @@ def balance_row(t, b):
     return [t, *b.content, b.wall_current[0], b.wall_current[1], b.power_joule, b.collision_loss, *b.imbalance, b.current]
 
 
+CURRENTS_COLUMNS = ("t", "conduction_powered", "displacement_powered", "total_powered", "conduction_grounded",
+                    "displacement_grounded", "total_grounded")
+
+
+def currents_row(t, c):
+    """One `--currents` row from a `fedm_amd.device.Currents`: t, then conduction, displacement and total [A] per electrode."""
+    return [t] + [x for g in range(len(c.conduction)) for x in (c.conduction[g], c.displacement[g], c.total[g])]
+
+
 def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", quiet=True, ttol=2e-3,
-         stop_before_device=None, balance=None, balance_every=1, fields=None, fields_every=1, axis_profile=None):
+         stop_before_device=None, balance=None, balance_every=1, fields=None, fields_every=1, axis_profile=None,
+         currents=None, currents_every=1):
     fem.parameters["form_compiler"]["quadrature_degree"] = 4
     deck = read_deck(input_dir)
     file_io.files.output_folder_path = Path(output_dir)
@@ -304,6 +318,11 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
         balance_of = fedm.Discharge_balance(problem, boundary_tags=(1, 2), weighting_potential=problem.device.coords[:, 1] / GAP)
         rows = open(balance, "w")
         rows.write("# " + " ".join(balance_columns(deck["file_names"])) + "\n")
+    currents_of = current_rows = None
+    if currents is not None:
+        currents_of = fedm.Electrode_currents(problem, boundary_tags=(1, 2))
+        current_rows = open(currents, "w")
+        current_rows.write("# " + " ".join(CURRENTS_COLUMNS) + "\n")
     field_out = field_files = profile = profile_rows = None
     if fields:
         fields = [name.strip() for name in (fields.split(",") if isinstance(fields, str) else fields) if name.strip()]
@@ -341,6 +360,9 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
             # (here, before anything of the next step reaches the device: the balance of the residual just solved)
             rows.write(" ".join(repr(float(v)) for v in balance_row(t, balance_of())) + "\n")
             rows.flush()
+        if currents_of is not None and steps % max(1, int(currents_every)) == 0:     # (here too: the residual just solved)
+            current_rows.write(" ".join(repr(float(v)) for v in currents_row(t, currents_of())) + "\n")
+            current_rows.flush()
         if profile is not None:     # (here too: the state and the table of the residual just solved)
             p = profile()["probes"]
             profile_rows.write(" ".join(f"{x:.17g}" for x in [t, *p.ravel()]) + "\n")
@@ -366,6 +388,8 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
         rows.close()
     if profile_rows is not None:
         profile_rows.close()
+    if current_rows is not None:
+        current_rows.close()
     return dict(t=t, steps=steps, output=str(file_io.files.output_folder_path), species=deck["file_names"],
                 error_file=str(file_io.files.error_file), problem=problem)
 
@@ -375,6 +399,9 @@ if __name__ == "__main__":
     ap.add_argument("out", nargs="?", default="gd_output")
     ap.add_argument("--balance", metavar="FILE", help="write the particle and energy balance per accepted step")
     ap.add_argument("--balance-every", type=int, default=1, metavar="N", help="... every N-th accepted step")
+    ap.add_argument("--currents", metavar="FILE",
+                    help="write t and the conduction, displacement and total current of both electrodes per accepted step")
+    ap.add_argument("--currents-every", type=int, default=1, metavar="N", help="... every N-th accepted step")
     ap.add_argument("--fields", metavar="LIST",
                     help="comma-separated derived fields written at the output times: mean_energy, reduced_field, E_norm, "
                          "E_r, E_z, charge, density:s, state:e, table:f, rate:j, source:s, collision_loss, joule, "
@@ -383,5 +410,6 @@ if __name__ == "__main__":
     ap.add_argument("--axis-profile", metavar="FILE", help="write the profiles of %s on r = 0 per accepted step" % ", ".join(AXIS_FIELDS))
     a = ap.parse_args()
     result = main(output_dir=a.out, quiet=False, balance=a.balance, balance_every=a.balance_every, fields=a.fields,
-                  fields_every=a.fields_every, axis_profile=a.axis_profile)
+                  fields_every=a.fields_every, axis_profile=a.axis_profile, currents=a.currents,
+                  currents_every=a.currents_every)
     print({k: v for k, v in result.items() if k != "problem"})

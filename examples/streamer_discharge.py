@@ -21,6 +21,9 @@ E/N tables (an extension: `fedm.Coefficient_table`, looked up in the element ker
 `--diagnostics FILE` writes one row per accepted step (every N-th with `--diagnostics-every N`): head position, field
 maximum in the channel, particle numbers, net charge, electrode charges and the induced current, computed on the
 device without downloading the state (an extension: `fedm.Discharge_diagnostics`); off by default.
+`--currents FILE` writes t and the conduction, displacement and total current of the cathode and of the anode per
+accepted step (every N-th with `--currents-every N`), with weighting potentials solved for on the device (an extension:
+`fedm.Electrode_currents`); off by default.
 `--fields LIST` writes derived fields (`E_norm,charge,rate:0,flux_z:1,...`) as VTU series at the output times (every
 N-th of them with `--fields-every N`), projected and blended to the output time on the device; `--axis-profile FILE`
 writes one row of `E_z` and `n_e` on `r = 0` per accepted step (an extension: `fedm.Field_output`); off by default.
@@ -231,16 +234,28 @@ def quiet_stdout(quiet):
     return contextlib.redirect_stdout(io.StringIO()) if quiet else contextlib.nullcontext()
 
 
+CURRENTS_COLUMNS = ("t", "conduction_cathode", "displacement_cathode", "total_cathode", "conduction_anode",
+                    "displacement_anode", "total_anode")
+
+
+def currents_row(t, c):
+    """One `--currents` row from a `fedm_amd.device.Currents`: t, then conduction, displacement and total [A] per electrode."""
+    return [t] + [x for g in range(len(c.conduction)) for x in (c.conduction[g], c.displacement[g], c.total[g])]
+
+
 def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_dir=None, output_dir=None,
          quiet=False, stop_before_device=None, coupling="coupled", model="benchmark_model", photoionization=False,
-         diagnostics=None, diagnostics_every=1, fields=None, fields_every=1, axis_profile=None):
+         diagnostics=None, diagnostics_every=1, fields=None, fields_every=1, axis_profile=None, currents=None,
+         currents_every=1):
     """Runs the case; returns (state as (n_vertices, 3) array of ln n_i, ln n_e, Phi; error-log path).
     `model`: the deck folder under the input directory ("benchmark_model", "tabulated_model").
     `photoionization`: add the Helmholtz photoionisation source (coupled step only).
     `diagnostics`: a file that receives DIAGNOSTICS_COLUMNS per accepted step (every `diagnostics_every`-th).
     `fields`: names of derived fields (fedm.Field_output) written as VTU series under `<output>/fields/` at the output
     times (every `fields_every`-th of them).  `axis_profile`: a file that receives, per accepted step, t followed by
-    E_z and then n_e at the AXIS_POINTS points of the axis (the first row holds their z)."""
+    E_z and then n_e at the AXIS_POINTS points of the axis (the first row holds their z).  `currents`: a file that
+    receives, per accepted step (every `currents_every`-th), t and then conduction, displacement and total current [A] of
+    the cathode and of the anode (fedm.Electrode_currents, their weighting potentials solved for on the device)."""
     case = Case(deck=model) if end_time is None else Case(deck=model, end_time=end_time)
     fem.parameters["form_compiler"]["quadrature_degree"] = 2
     deck = read_deck(case, input_dir)
@@ -283,6 +298,11 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
                                               weighting_potential=mesh.coords[:, 1] / case.side)
         rows = open(diagnostics, "w")
         rows.write("# " + " ".join(DIAGNOSTICS_COLUMNS) + "\n")
+    currents_of = current_rows = None
+    if currents is not None:
+        currents_of = fedm.Electrode_currents(problem, boundary_tags=(1, 2))
+        current_rows = open(currents, "w")
+        current_rows.write("# " + " ".join(CURRENTS_COLUMNS) + "\n")
     field_out = field_files = profile = profile_rows = None
     if fields:
         fields = [name.strip() for name in (fields.split(",") if isinstance(fields, str) else fields) if name.strip()]
@@ -335,6 +355,9 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
                    d.surface_charge[0], d.surface_charge[1], d.current)
             rows.write(" ".join(f"{x:.17g}" for x in row) + "\n")
             rows.flush()
+        if currents_of is not None and accepted % max(1, int(currents_every)) == 0:
+            current_rows.write(" ".join(f"{x:.17g}" for x in currents_row(t, currents_of())) + "\n")
+            current_rows.flush()
         if profile is not None:
             p = profile()["probes"]
             profile_rows.write(" ".join(f"{x:.17g}" for x in [t, *p[0], *p[1]]) + "\n")
@@ -355,6 +378,8 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
         rows.close()
     if profile_rows is not None:
         profile_rows.close()
+    if current_rows is not None:
+        current_rows.close()
     return problem.device.get_state(), file_io.files.error_file
 
 
@@ -379,12 +404,16 @@ if __name__ == "__main__":
                          "density:electrons, rate:0, flux_r:1, flux_z:1, state:2")
     ap.add_argument("--fields-every", type=int, default=1, metavar="N", help="... at every N-th output time")
     ap.add_argument("--axis-profile", metavar="FILE", help="write E_z and n_e on r = 0 per accepted step")
+    ap.add_argument("--currents", metavar="FILE",
+                    help="write t and the conduction, displacement and total current of cathode and anode per accepted step")
+    ap.add_argument("--currents-every", type=int, default=1, metavar="N", help="... every N-th accepted step")
     ap.add_argument("--save-state", metavar="FILE", help="write the final state (n_vertices, 3) as a .npy file")
     a = ap.parse_args()
     state, log_path = main(cells=a.cells, mesh_spacing=a.mesh_spacing, mesh_file=a.mesh, end_time=a.end,
                            output_dir=a.out, coupling=a.coupling, model=a.model, photoionization=a.photoionization,
                            diagnostics=a.diagnostics, diagnostics_every=a.diagnostics_every, fields=a.fields,
-                           fields_every=a.fields_every, axis_profile=a.axis_profile)
+                           fields_every=a.fields_every, axis_profile=a.axis_profile, currents=a.currents,
+                           currents_every=a.currents_every)
     if a.save_state:
         import numpy
         numpy.save(a.save_state, state)

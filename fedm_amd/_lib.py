@@ -166,6 +166,16 @@ class GdBalanceOut(C.Structure):
                 ("finite", C.c_int32), ("pad_", C.c_int32)]
 
 
+CURRENTS_MAX = 8
+
+
+class CurrentsOut(C.Structure):
+    _fields_ = [("conduction", C.c_double * CURRENTS_MAX), ("displacement", C.c_double * CURRENTS_MAX),
+                ("coupling", C.c_double * CURRENTS_MAX), ("induced_charge", C.c_double * CURRENTS_MAX),
+                ("capacitance", (C.c_double * CURRENTS_MAX) * CURRENTS_MAX),
+                ("n_psi", C.c_int32), ("finite", C.c_int32)]
+
+
 FIELDS_MAX_REQ = 8
 
 
@@ -253,6 +263,10 @@ _SIGNATURES = {
     "fedm_diagnostics": (C.c_int, [_P, C.POINTER(DiagOpts), C.POINTER(DiagOut)]),
     "fedm_gd_balance_setup": (C.c_int, [_P, _D, C.POINTER(C.c_int8), C.c_int]),
     "fedm_gd_balance": (C.c_int, [_P, C.POINTER(GdBalanceOut)]),
+    "fedm_currents_setup": (C.c_int, [_P, C.c_int, _D]),
+    "fedm_currents_solve": (C.c_int, [_P, C.POINTER(PhotoHierarchy), _D, C.c_double, C.c_int, C.POINTER(C.c_int)]),
+    "fedm_currents_get_psi": (C.c_int, [_P, _D]),
+    "fedm_currents": (C.c_int, [_P, C.POINTER(CurrentsOut)]),
     "fedm_fields_setup": (C.c_int, [_P, C.POINTER(Csr)]),
     "fedm_probe_setup": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), _D]),
     "fedm_fields": (C.c_int, [_P, C.POINTER(FieldOpts), C.c_int, C.POINTER(FieldReq), _D, _D, C.POINTER(C.c_int32),

@@ -31,7 +31,7 @@ class Case:
     def __init__(self, nx=100, ny=100, file_input=DECK, device=0, T_final=1e-11,
                  relative_tolerance=1e-4, maximum_iterations=20, quiet=True, error_file=None,
                  device_pipeline=True, mesh=None, energy_loss=None, energy_Ei=0.0, quadrature_degree=4,
-                 keep_balance=False):
+                 keep_balance=False, keep_currents=False):
         import tempfile
         self.quiet = quiet
         model = "4_particles"
@@ -144,6 +144,8 @@ class Case:
         self.newton_iterations = self.linear_iterations = 0
         # keep_balance: every step leaves the balance of the residual it solved in last_balance
         self.keep_balance, self.last_balance = keep_balance, None
+        # keep_currents: every step leaves the electrode currents of the residual it solved in last_currents
+        self.keep_currents, self.last_currents = keep_currents, None
 
     def dirichlet_values(self, t):
         return np.concatenate([np.full(self.powered.size, self.U_w * (1.0 - np.exp(-t / 1e-9))),
@@ -251,6 +253,8 @@ class Case:
         self.linear_iterations += prob.last_report.linear_iterations
         if self.keep_balance:
             self.last_balance = self.balance()
+        if self.keep_currents:
+            self.last_currents = self.currents()
         self.U = prob.get_state()
         self.mean_energy.vector()[:] = np.exp(self.U[:, 0] - self.U[:, ns - 1])      # :452
         if self.snapshot is None and self.t_output <= self.t:        # file_output, file_io.py:582-587
@@ -280,6 +284,8 @@ class Case:
         self._solve()
         if self.keep_balance:       # before the mean-energy field moves on to the next step
             self.last_balance = self.balance()
+        if self.keep_currents:      # the fluxes of the residual just solved, as keep_balance
+            self.last_currents = self.currents()
         prob.gd_update_mean_energy()
         if self.snapshot is None and self.t_output <= self.t:
             U_old, U = prob.get_state_old(), prob.get_state()
@@ -303,6 +309,19 @@ class Case:
             self._balance = ff.Discharge_balance(self.prob, boundary_tags=(1, 2),
                                                  weighting_potential=self.mesh.coords[:, 1] / self.gap)
         return self._balance()
+
+    def currents(self):
+        """The electrode currents on the device (``fedm.Electrode_currents``) of the state and the field table as they
+        stand: electrode 0 the powered one (tag 1), electrode 1 the grounded one (tag 2), their weighting potentials solved
+        for on the device at the first call; the displacement part is that of the powered electrode's time-dependent
+        potential.  Returns a :class:`fedm_amd.device.Currents`.  ``keep_currents=True`` makes every ``step()`` leave the
+        currents of the residual it solved in ``last_currents``, taken where ``keep_balance`` takes the balance.  Unlike the
+        balance, a call after ``step()`` returns the same bytes: the mean-energy refresh rewrites only the row the walls'
+        thermal velocity reads, and the fluxes read the rows ``gd_prep_step`` writes; the currents move once the next
+        step's shift and refresh have run."""
+        if getattr(self, "_currents", None) is None:
+            self._currents = ff.Electrode_currents(self.prob, boundary_tags=(1, 2))
+        return self._currents()
 
     def fields(self, requests, probes=None, t_out=None, t_old=None, projection="lumped"):
         """Derived nodal fields of the device-resident state and field table (``fedm.Field_output`` on the LMEA model; no

@@ -282,6 +282,14 @@ class Stepper:
             self.t, d.z_head, d.window_max, d.field_max, d.species_integral[0], d.species_integral[1], d.net_charge,
             d.surface_charge[0], d.surface_charge[1], d.current, dens[0], dens[1])))
 
+    def currents(self):
+        """The electrode currents of the device-resident state (``fedm_amd.functions.Electrode_currents``; no download):
+        electrode 0 the cathode (tag 1), electrode 1 the anode (tag 2), their weighting potentials solved for on the
+        device at the first call.  Returns a :class:`fedm_amd.device.Currents`."""
+        if getattr(self, "_currents", None) is None:
+            self._currents = self.ff.Electrode_currents(self.prob, boundary_tags=(1, 2))
+        return self._currents()
+
     def fields(self, names, t_out=None, t_old=None, probes=None, projection="lumped"):
         """Derived nodal fields of the device-resident state (``fedm_amd.functions.Field_output``; no download): a dict
         name -> nodal array, blended to ``t_out`` between ``t_old`` and the current time when both are given.

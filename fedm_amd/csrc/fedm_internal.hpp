@@ -77,6 +77,7 @@ struct Photo;
 struct Diag;
 struct Fields;
 struct GdBalance;
+struct Currents;
 
 // Optional in-run kernel timing with HIP events on the library's stream (bench.py roofline).
 // kinds: 0 assembly F+J, 1 Jacobian SpMV, 2 assembly F only, 3 multigrid V-cycle
@@ -316,6 +317,7 @@ struct Ctx {
     Diag *diag = nullptr;     // discharge diagnostics: psi, groups and the reductions' buffers (diag.hpp; allocated at first use)
     Fields *fields = nullptr; // field output: the vertex lists, the lumped mass, the results' buffers (fields.hpp; fedm_fields_setup)
     GdBalance *gd_balance = nullptr;   // LMEA balance: psi, groups, the tags' facet lists and the reductions' buffers (gd_balance.hpp; allocated at first use)
+    Currents *currents = nullptr;      // electrode currents: the weighting potentials, the capacitance and the reductions' buffers (currents.hpp; fedm_currents_setup)
 };
 
 // Indices of Ctx::path_stats, in the order fedm_solver_path_stats documents (include/fedm_hip.h)
@@ -439,6 +441,8 @@ void diag_release(Ctx &c);
 void fields_release(Ctx &c);
 // ---- gd_balance.hip (gd_balance.hpp has the rest) ---------------------------------------------
 void gd_balance_release(Ctx &c);
+// ---- currents.hip (currents.hpp has the rest) -------------------------------------------------
+void currents_release(Ctx &c);
 // ---- spmv.hip -------------------------------------------------------------------------------
 void launch_block_inverse(Ctx &c);                              // d_dinv from diagonal blocks
 void launch_row_scale(Ctx &c, double *d2, double *d_out);       // d^2 (and d, unless null) of the rows' equilibration

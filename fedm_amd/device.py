@@ -374,6 +374,26 @@ class Balance:
 
 
 @dataclass
+class Currents:
+    """One call of :meth:`DeviceProblem.currents` (``fedm_currents``, include/fedm_hip.h has the formulae), in SI units:
+    entry ``g`` belongs to weighting potential ``g``.  Axisymmetric: totals; planar: per metre of depth.  ``raw`` keeps
+    the library's own sums (``conduction`` [1/s], ``displacement`` [V m/s], ``coupling`` [V m], ``induced_charge`` [1],
+    ``capacitance`` [m])."""
+    conduction: np.ndarray            # e sum_s Z_s int Gamma_s . (-grad psi_g)  [A; A/m planar]
+    displacement: np.ndarray          # eps0 int grad(D_t Phi) . grad psi_g  [A; A/m planar]
+    induced_charge: np.ndarray        # e sum_s Z_s int n_s psi_g  [C; C/m planar]
+    coupling: np.ndarray              # int grad Phi . grad psi_g  [V m; V planar]
+    capacitance: np.ndarray           # eps0 int grad psi_g . grad psi_h  [F; F/m planar]
+    finite: bool                      # False: a value met on the way was not finite; the rest is unspecified
+    raw: dict = field(default_factory=dict)
+
+    @property
+    def total(self):
+        """conduction + displacement: the Shockley-Ramo current in the lead of each electrode."""
+        return self.conduction + self.displacement
+
+
+@dataclass
 class FieldValues:
     """One call of :meth:`DeviceProblem.fields` (``fedm_fields``): ``nodal[k]`` the nodal values of request ``k`` in the
     caller's vertex order (None with ``nodal=False``), ``probes[k]`` its values at the probe points (None without
@@ -1030,6 +1050,106 @@ class DeviceProblem:
             nodal_max_vertex=np.where(vert >= 0, self._order[np.maximum(vert, 0)], -1),
             finite=bool(out.finite), net=np.asarray(self.model.net, dtype=np.int64).reshape(nr, -1)[:, :ns],
             sign=np.asarray(self.model.sign, dtype=np.float64)[:ns])
+
+    # -- electrode currents (csrc/currents.hip) --------------------------------------------
+    def currents_setup(self, potentials=None, boundary_tags=None, rtol=1e-10, max_it=2000, multigrid=True,
+                       max_coarse=600, nu=1, omega=0.67, theta=0.08):
+        """What :meth:`currents` needs once.  Either ``potentials``: nodal P1 weighting potentials
+        ``[n_psi, n_vertices]`` in the caller's numbering, taken as they are (``fedm_currents_setup``); or
+        ``boundary_tags``: electrode ``g`` is the potential-Dirichlet vertices of the facets tagged
+        ``boundary_tags[g]`` (:func:`boundary_vertex_groups`; a vertex in two groups raises ``ValueError``), and
+        ``psi_g`` -- 1 on it, 0 on every other Dirichlet vertex of the potential, natural conditions elsewhere -- is
+        solved for on the device (``fedm_currents_solve``): the host assembles ``K_w`` in the device's numbering once
+        (``photo.helmholtz_matrices``), eliminates the Dirichlet vertices, builds the hierarchy (``amg.build_hierarchy``;
+        Jacobi alone with ``multigrid=False`` or below ``max_coarse`` vertices) and the right-hand sides
+        ``-K_w psi_D``; ``rtol``, ``max_it``: of the conjugate gradients, ``|r| <= rtol |b|``.  At most 8 potentials.
+        Replaces an earlier set-up.  Returns the CG iterations per potential (empty without a solve), kept in
+        ``last_currents_iterations`` too."""
+        if (potentials is None) == (boundary_tags is None):
+            raise ValueError("currents_setup: give either potentials or boundary_tags")
+        # (the count and the iterations follow the library: a refused set-up leaves the earlier one in place, here too)
+        if potentials is not None:
+            psi = np.atleast_2d(np.asarray(potentials, dtype=np.float64))
+            if psi.ndim != 2 or psi.shape[1] != self.nv:
+                raise ValueError(f"potentials must be [n_psi, {self.nv}], got {psi.shape}")
+            if not 1 <= psi.shape[0] <= _lib.CURRENTS_MAX:
+                raise ValueError(f"1 to {_lib.CURRENTS_MAX} weighting potentials, got {psi.shape[0]}")
+            psi = np.ascontiguousarray(psi[:, self._order])
+            self._check(self.lib.fedm_currents_setup(self._h, psi.shape[0], _dp(psi)), "fedm_currents_setup")
+            self._currents_n, self.last_currents_iterations = psi.shape[0], []
+            return []
+        from . import amg, photo
+        tags = [int(t) for t in boundary_tags]
+        if not 1 <= len(tags) <= _lib.CURRENTS_MAX:
+            raise ValueError(f"1 to {_lib.CURRENTS_MAX} electrodes, got {len(tags)}")
+        if not getattr(self.model, "poisson", True):
+            raise RuntimeError("currents_setup: the model has no Poisson equation")
+        fixed_caller = self.dirichlet_vertices()
+        group = boundary_vertex_groups(self.cells, self.facet_tags(), self.nv, fixed_caller, tags)
+        fixed = np.zeros(self.nv, dtype=bool)
+        fixed[self._inv[fixed_caller]] = True                       # the device's numbering from here on
+        group_dev = group[self._order]
+        psi = np.zeros((len(tags), self.nv))
+        for g in range(len(tags)):
+            psi[g, group_dev == g + 1] = 1.0
+        K, _ = photo.helmholtz_matrices(self._coords_dev, self._cells_dev.astype(np.int64), self.model.axisymmetric,
+                                        self.model.quadrature_degree)
+        A = photo.eliminate(K, fixed)
+        rhs = -(K @ psi.T).T
+        rhs[:, fixed] = 0.0
+        rhs = np.ascontiguousarray(rhs)
+        levels = [(A, None)]
+        if multigrid:
+            levels = amg.build_hierarchy(A, theta=theta, max_coarse=max_coarse, fixed=fixed, coords=self._coords_dev)
+        self._check(self.lib.fedm_currents_setup(self._h, len(tags), _dp(psi)), "fedm_currents_setup")
+        self._currents_n = len(tags)
+        self.currents_levels = [a.shape[0] for a, _ in levels]
+        # (what was solved, in the device's numbering: the hierarchy, the right-hand sides, the conductors' vertices)
+        self.currents_system = (levels, rhs, fixed)
+        return self.currents_solve(levels, rhs, rtol, max_it, nu=nu, omega=omega)
+
+    def currents_solve(self, levels, rhs, rtol=1e-10, max_it=2000, nu=1, omega=0.67):
+        """``fedm_currents_solve`` with a hierarchy ``[(A_l, P_l)]`` of :func:`fedm_amd.amg.build_hierarchy` (one level:
+        Jacobi) and right-hand sides ``[n_psi, n_vertices]``, both in the DEVICE's numbering.  A solve that stops at
+        ``max_it`` or meets a NaN raises ``RuntimeError`` and leaves the installed potentials as they were."""
+        from . import amg
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+        n, Ac, Pc, Rc, coarse, held = amg._pack(levels, dense_coarse=len(levels) > 1)
+        h = _lib.PhotoHierarchy()
+        h.n_levels, h.nu, h.omega = n, int(nu), float(omega)
+        h.A, h.P, h.R = Ac, Pc, Rc
+        h.coarse_inverse = coarse.ctypes.data_as(C.POINTER(C.c_double)) if coarse is not None else None
+        its = (C.c_int * _lib.CURRENTS_MAX)()
+        rc = self.lib.fedm_currents_solve(self._h, C.byref(h), _dp(rhs), float(rtol), int(max_it), its)
+        self.last_currents_iterations = [int(v) for v in its[:getattr(self, "_currents_n", 0)]]
+        if rc == 3:
+            raise RuntimeError(f"fedm_currents_solve: conjugate gradients stopped at max_it = {max_it} "
+                               f"(iterations per potential {self.last_currents_iterations})")
+        if rc == 2:
+            raise RuntimeError("fedm_currents_solve: NaN or an operator that is not positive definite")
+        self._check(rc, "fedm_currents_solve")
+        return self.last_currents_iterations
+
+    def currents_psi(self):
+        """The installed weighting potentials ``[n_psi, n_vertices]`` in the caller's numbering
+        (``fedm_currents_get_psi``)."""
+        out = np.empty((_lib.CURRENTS_MAX, self.nv))        # (room for whatever the library holds)
+        self._check(self.lib.fedm_currents_get_psi(self._h, _dp(out)), "fedm_currents_get_psi")
+        return np.ascontiguousarray(out[:getattr(self, "_currents_n", 0), self._inv])
+
+    def currents(self):
+        """The electrode currents of the resident state (``fedm_currents``): one pass over the cells, a one-workgroup
+        finish, a read-back of under a kilobyte.  LFA: the fluxes at ``u_new``; LMEA: the fluxes the residual of the
+        current step sees.  Returns a :class:`Currents`."""
+        out = _lib.CurrentsOut()
+        self._check(self.lib.fedm_currents(self._h, C.byref(out)), "fedm_currents")
+        n = int(out.n_psi)
+        raw = dict(conduction=np.array(out.conduction[:n]), displacement=np.array(out.displacement[:n]),
+                   coupling=np.array(out.coupling[:n]), induced_charge=np.array(out.induced_charge[:n]),
+                   capacitance=np.array([list(out.capacitance[g][:n]) for g in range(n)]).reshape(n, n))
+        return Currents(conduction=elementary_charge * raw["conduction"], displacement=epsilon_0 * raw["displacement"],
+                        induced_charge=elementary_charge * raw["induced_charge"], coupling=raw["coupling"].copy(),
+                        capacitance=epsilon_0 * raw["capacitance"], finite=bool(out.finite), raw=raw)
 
     # -- field output (csrc/fields.hip) ---------------------------------------------------
     def fields_setup(self, consistent=False):

@@ -999,6 +999,34 @@ def Discharge_balance(problem, boundary_tags=(), weighting_potential=None):
     return dev.balance
 
 
+def Electrode_currents(problem, boundary_tags=None, weighting_potentials=None, rtol=1e-10):
+    """Extension (what an experiment measures: the current in the lead of an electrode): the Shockley-Ramo currents of
+    the device-resident state without downloading it, for either model family.  ``problem``: a :class:`Problem` (or its
+    device problem) of a model with a Poisson equation.  ``boundary_tags[g]``: the boundary that is electrode ``g`` --
+    its weighting potential is 1 on the potential's Dirichlet vertices of the facets with that tag, 0 on every other
+    Dirichlet vertex of the potential, and solved for on the device with natural conditions elsewhere (conjugate
+    gradients to ``rtol``); a vertex that would fall into two electrodes raises ``ValueError``.
+    ``weighting_potentials``: nodal values ``[n_psi, n_vertices]`` taken as they are instead.  At most 8 potentials; the
+    conductors are the Dirichlet boundaries of the potential; no dielectric solids; no circuit feedback.
+
+    Returns a callable: ``currents()`` gives a :class:`fedm_amd.device.Currents` in SI units -- ``conduction``,
+    ``displacement`` (of the variable-step BDF2 rate of change of the potential), ``total``, ``induced_charge``,
+    ``coupling``, ``capacitance``, ``finite`` -- from one pass over the cells on the device; its ``.psi`` holds the
+    potentials in the caller's vertex order and ``.iterations`` the solves' CG steps."""
+    dev = getattr(problem, "device", problem)
+    if (boundary_tags is None) == (weighting_potentials is None):
+        raise ValueError("fedm.Electrode_currents: give either boundary_tags or weighting_potentials")
+    if not getattr(dev.model, "poisson", True):
+        raise ValueError("fedm.Electrode_currents: the currents need the Poisson equation")
+    its = dev.currents_setup(potentials=weighting_potentials, boundary_tags=boundary_tags, rtol=rtol)
+
+    def currents():
+        return dev.currents()
+    currents.psi = dev.currents_psi()
+    currents.iterations = its
+    return currents
+
+
 def Field_output(problem, fields, probes=None, projection="lumped", species_names=None):
     """Extension (what the reference's scripts do with ``project(...)`` and ``file_output``, fedm-gd.py:309,432): derived
     nodal fields of the device-resident state, blended to an output time, without downloading the state.  ``problem``:

@@ -247,7 +247,8 @@ const char *fedm_last_error(void);
  *    fedm_diag_setup and fedm_diagnostics with fedm_diag_opts and fedm_diag.
  *    fedm_fields_setup, fedm_probe_setup and fedm_fields with fedm_field_req and fedm_field_opts.
  *    fedm_gd_balance_setup and fedm_gd_balance with fedm_gd_balance.
- *    fedm_gd_fields_setup, fedm_gd_probe_setup and fedm_gd_fields with the FEDM_GD_FIELD_* kinds. */
+ *    fedm_gd_fields_setup, fedm_gd_probe_setup and fedm_gd_fields with the FEDM_GD_FIELD_* kinds.
+ *    fedm_currents_setup, fedm_currents_solve, fedm_currents_get_psi and fedm_currents with fedm_currents. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -981,6 +982,53 @@ int fedm_gd_balance_setup(fedm_ctx *ctx, const double *psi, const int8_t *group,
  * call, touches no state and synchronises once, for the read-back.  Returns 0 also when out->finite is 0; the next
  * call is unaffected.  Refused (-2): an LFA context, a context with ghosts, a null argument. */
 int fedm_gd_balance(fedm_ctx *ctx, struct fedm_gd_balance *out);
+
+/* ---- electrode currents (both families; models with a Poisson equation; one GPU) ------------------------------------
+ * Shockley-Ramo currents of up to FEDM_CURRENTS_MAX weighting potentials psi_g at once, from the resident state.
+ * W is the residual's weight, qp_w |det J| 2 pi w(x_q) with w = r (axisymmetric) or 1/(2 pi) (planar), at the model's
+ * own quadrature points -- what fedm_diagnostics and fedm_gd_balance document.
+ *   conduction: fedm_diag.induced_current (LFA: the fluxes of fedm_diagnostics at u_new; log and linear representation,
+ *     drift_w, 0 for 'reaction' species, tables) or fedm_gd_balance.induced_current (LMEA: the residual's own fluxes of
+ *     the current step, species s >= 1 with sign_s) for each psi_g.
+ *   D_t Phi: the variable-step BDF2 quotient of the species rows' time term,
+ *     ((1 + 2w) Phi - (1 + w)^2 Phi_old + w^2 Phi_old1) / ((1 + w) dt),  w = dt / dt_old,
+ *     from the potential entries of u_new, u_old, u_old1, nodal; its gradient per cell.
+ *   With E = -grad Phi and E_w = -grad psi,  eps0 d_t E . E_w = eps0 grad(d_t Phi) . grad psi:
+ *   e conduction + eps0 displacement is the total current with the sign induced_current has.
+ *   capacitance: formed in fedm_currents_setup and after fedm_currents_solve, [g][h] and [h][g] from one sum.
+ * Every sum is reduced in a fixed order without floating-point atomics: two calls on one state return the same bytes. */
+#define FEDM_CURRENTS_MAX 8
+/* (a struct tag, not a typedef: the call below has the same name, so the type is written `struct fedm_currents`) */
+struct fedm_currents {
+    double conduction[FEDM_CURRENTS_MAX];      /* sum_s Z_s sum W Gamma_s . (-grad psi_g)        [1/s]    */
+    double displacement[FEDM_CURRENTS_MAX];    /* sum W grad(D_t Phi) . grad psi_g               [V m/s]  */
+    double coupling[FEDM_CURRENTS_MAX];        /* sum W grad Phi(u_new) . grad psi_g             [V m]    */
+    double induced_charge[FEDM_CURRENTS_MAX];  /* sum_s Z_s sum W n_s psi_g                      [1]      */
+    double capacitance[FEDM_CURRENTS_MAX][FEDM_CURRENTS_MAX];   /* sum W grad psi_g . grad psi_h  [m]      */
+    int32_t n_psi, finite;                     /* finite 0: a state value visited or a quantity formed was not finite;
+                                                  the sums are then unspecified                                         */
+};
+/* psi: n_psi nodal P1 weighting potentials [n_psi][n_vertices] in the context's numbering, copied; the capacitance
+ * matrix is formed.  Replaces an earlier set-up.  Refused (-2, fedm_last_error says why): no Poisson equation; a context
+ * with ghost vertices or a transport; n_psi outside 1..FEDM_CURRENTS_MAX; a null argument; a psi that is not finite. */
+int fedm_currents_setup(fedm_ctx *ctx, int n_psi, const double *psi);
+/* Solves for the installed potentials on the device.  laplace->A[0] is K_w (int w grad phi_a . grad phi_b) in the
+ * context's numbering with rows and columns of the conductors' (Dirichlet) vertices eliminated symmetrically: those
+ * vertices are the unit rows of A[0], and the installed psi_g carries their values.  Per potential, conjugate gradients
+ * preconditioned by the hierarchy (n_levels = 1: Jacobi), as fedm_photo_setup takes it, for the free vertices' values
+ * with rhs_g (-K_w psi_D on the free rows; the unit rows' entries are not read) until |r|_2 <= rtol |rhs|_2 on the
+ * recurrence's residual; the conductors' values stay bitwise.  The capacitance is formed again.  iterations (unless
+ * NULL): CG steps per potential.  Returns 0, FEDM_DIVERGED_LINEAR (a potential stopped at max_it) or FEDM_DIVERGED_NAN
+ * (an operator that is not positive definite, a NaN on the way); a failed solve leaves every installed potential and the
+ * capacitance as they were.  Refused (-2): the refusals of fedm_currents_setup; no set-up; an rhs that is not finite;
+ * rtol <= 0 or max_it < 0; a hierarchy that fedm_amg_setup would refuse or whose operator is not n_vertices square. */
+int fedm_currents_solve(fedm_ctx *ctx, const fedm_photo_hierarchy *laplace, const double *rhs, double rtol, int max_it,
+                        int iterations[FEDM_CURRENTS_MAX]);
+/* Test hook: the installed potentials [n_psi][n_vertices], the context's numbering. */
+int fedm_currents_get_psi(fedm_ctx *ctx, double *psi);
+/* One pass over the cells, a one-workgroup finish, one read-back.  Touches no state and no field table; returns 0 also
+ * when out->finite is 0, and the next call is unaffected.  Refused (-2): as fedm_currents_setup; no set-up. */
+int fedm_currents(fedm_ctx *ctx, struct fedm_currents *out);
 
 /* timed micro-benchmarks on the resident state (HIP events on the library's stream):
  * kind 0 = residual+Jacobian assembly, 1 = SpMV, 2 = residual only, 3 = one multigrid cycle on the
