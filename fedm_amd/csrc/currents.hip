@@ -4,7 +4,7 @@
 // solved for on the device.  diag.hip's pattern: a pass over the cells writes slot-major partials, one workgroup
 // reduces them; plain launches on the context's stream and one copy to the host.  Every sum has a fixed order (thread,
 // wave by shuffles, the workgroup's waves one after the other, the partials) and nothing adds with floating-point
-// atomics, so a call is bitwise reproducible.
+// atomics, so a call is bitwise reproducible.  The reductions' cores and the host's helpers are postproc.hpp's.
 // A cell's part does not depend on the potential: sum W, the charge-weighted flux J = sum_s Z_s sum W Gamma_s (the
 // gradients of P1 functions are constant on a cell, so Gamma_s . grad psi sums to J . grad psi), the charge moments
 // Q_a = sum_s Z_s sum W n_s phi_a and the gradients of Phi and of D_t Phi.  It is formed once per cell, as
@@ -14,35 +14,14 @@
 
 #include <algorithm>
 #include <cmath>
-#include <type_traits>
 #include <vector>
 
-#include "device_util.hpp"
 #include "element.hpp"
 #include "gd_balance.hpp"
+#include "postproc.hpp"
 #include "solver.hpp"
 
 namespace fedm {
-
-// ---- reductions ----------------------------------------------------------------------------------
-constexpr int CUR_WAVES = CUR_THREADS / 64;
-
-// K values per thread -> thread k holds sum k: lanes by shuffles, then the waves in ascending order
-template <int K>
-__device__ __forceinline__ double cur_block_sums(const double (&v)[K], double (*lds)[CUR_WAVES]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) lds[k][wave] = s;
-    }
-    __syncthreads();
-    double s = 0.0;
-    if ((int)threadIdx.x < K)
-        for (int w = 0; w < CUR_WAVES; ++w) s += lds[threadIdx.x][w];
-    __syncthreads();
-    return s;
-}
 
 // ---- what the families share -------------------------------------------------------------------------
 // the variable-step BDF2 quotient of a nodal value (element.hpp, step_coef; gd_balance's rate_of_change)
@@ -95,19 +74,19 @@ __device__ __forceinline__ double cur_accumulate(double (&acc)[CUR_SUMS], const 
 template <int K>
 __device__ __forceinline__ void cur_write_partials(const double (&acc)[K], bool bad, double *__restrict__ sum_part,
                                                    int *__restrict__ flag_part) {
-    __shared__ double lds_sum[K][CUR_WAVES];
-    const double s = cur_block_sums(acc, lds_sum);
+    __shared__ double lds_sum[K][POST_WAVES];
+    const double s = block_sums(acc, lds_sum);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
-    if ((int)threadIdx.x < K) sum_part[(size_t)threadIdx.x * CUR_BLOCKS + blockIdx.x] = s;
+    if ((int)threadIdx.x < K) sum_part[(size_t)threadIdx.x * POST_BLOCKS + blockIdx.x] = s;
     if (threadIdx.x == 0) flag_part[blockIdx.x] = any_bad;
 }
 
 // ---- the cells, LFA ----------------------------------------------------------------------------------
-// A thread per cell (a stride loop beyond CUR_BLOCKS workgroups).  |E| and the coefficients once per cell as
+// A thread per cell (a stride loop beyond POST_BLOCKS workgroups).  |E| and the coefficients once per cell as
 // Element::setup has them, the densities at the model's quadrature points with Element::point's weight: the fluxes are
 // diag_cell_kernel's, kept as vectors.
 template <int NS, bool TAB>
-__global__ __launch_bounds__(CUR_THREADS) void currents_cell_kernel(
+__global__ __launch_bounds__(POST_THREADS) void currents_cell_kernel(
     int nc, int nvp, const fedm_model_desc *__restrict__ md, const double *__restrict__ coords,
     const int *__restrict__ cells, const double *__restrict__ u, const double *__restrict__ uold,
     const double *__restrict__ uold1, double dt, double dt_old, const double *__restrict__ psi, int n_psi,
@@ -205,7 +184,7 @@ __global__ __launch_bounds__(CUR_THREADS) void currents_cell_kernel(
 // The residual's own fluxes of the current step at every quadrature point (gd_balance.hpp: bal_point, bal_species_flux;
 // the electrons' by bal_flux, as gd_balance_cell_kernel takes them), species s >= 1 with sign_s.
 template <int NEQ>
-__global__ __launch_bounds__(CUR_THREADS) void gd_currents_cell_kernel(
+__global__ __launch_bounds__(POST_THREADS) void gd_currents_cell_kernel(
     int nc, int nv, int nvp, const fedm_gd_desc *__restrict__ md, const double *__restrict__ fields,
     const double *__restrict__ coords, const int *__restrict__ cells, const double *__restrict__ u,
     const double *__restrict__ uold, const double *__restrict__ uold1, double dt, double dt_old,
@@ -213,7 +192,6 @@ __global__ __launch_bounds__(CUR_THREADS) void gd_currents_cell_kernel(
     constexpr int ns = NEQ - 1, IPHI = NEQ - 1, ie = ns - 1;
     const double two_pi = 6.283185307179586476925286766559;
     const int nr = md->n_reactions, nq = md->n_qp;
-    const bool axi = md->axisymmetric != 0;
     const double tr = dt / dt_old, inv_dt = 1.0 / dt;
     double acc[CUR_SUMS];
 #pragma unroll
@@ -222,19 +200,10 @@ __global__ __launch_bounds__(CUR_THREADS) void gd_currents_cell_kernel(
     for (int cell = blockIdx.x * blockDim.x + threadIdx.x; cell < nc; cell += gridDim.x * blockDim.x) {
         BalCell c;
         double U[3][NEQ], Dt[3];
+        bad |= bal_load_cell<NEQ>(cell, md, coords, cells, u, c, U);
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            c.v[a] = cells[3 * (size_t)cell + a];
-            c.x[a][0] = coords[2 * (size_t)c.v[a]];
-            c.x[a][1] = coords[2 * (size_t)c.v[a] + 1];
-#pragma unroll
-            for (int e = 0; e < NEQ; ++e) {
-                U[a][e] = u[(size_t)c.v[a] * NEQ + e];
-                bad |= !isfinite(U[a][e]);
-            }
+        for (int a = 0; a < 3; ++a)
             Dt[a] = cur_rate(U[a][IPHI], uold[(size_t)c.v[a] * NEQ + IPHI], uold1[(size_t)c.v[a] * NEQ + IPHI], tr, inv_dt);
-        }
-        bal_cell_init(c, axi);
         CurCell cc;
         cur_grad(c.G, U[0][IPHI], U[1][IPHI], U[2][IPHI], cc.gP);
         cur_grad(c.G, Dt[0], Dt[1], Dt[2], cc.gD);
@@ -276,7 +245,7 @@ __global__ __launch_bounds__(CUR_THREADS) void gd_currents_cell_kernel(
 // place of D_t Phi; the host writes [g][h] and [h][g] from the one sum.  Desc: either family's descriptor (the
 // quadrature rule and the symmetry are all it gives).
 template <class Desc>
-__global__ __launch_bounds__(CUR_THREADS) void currents_capacitance_kernel(
+__global__ __launch_bounds__(POST_THREADS) void currents_capacitance_kernel(
     int nc, int nvp, const Desc *__restrict__ md, const double *__restrict__ coords, const int *__restrict__ cells,
     const double *__restrict__ psi, int h, double *__restrict__ sum_part, int *__restrict__ flag_part) {
     const double two_pi = 6.283185307179586476925286766559;
@@ -319,19 +288,19 @@ __global__ __launch_bounds__(CUR_THREADS) void currents_capacitance_kernel(
 }
 
 // ---- second pass -----------------------------------------------------------------------------------
-// One workgroup: thread t brings the partials of workgroup t (nb of them, at most CUR_BLOCKS = CUR_THREADS), reduced
+// One workgroup: thread t brings the partials of workgroup t (nb of them, at most POST_BLOCKS = POST_THREADS), reduced
 // slot by slot in the same fixed order.  The slots from n_slots on were not written by the first pass and are not read.
-__global__ __launch_bounds__(CUR_THREADS) void currents_finish_kernel(int nb, int n_slots,
+__global__ __launch_bounds__(POST_THREADS) void currents_finish_kernel(int nb, int n_slots,
                                                                       const double *__restrict__ sum_part,
                                                                       const int *__restrict__ flag_part,
                                                                       CurResult *__restrict__ res) {
-    __shared__ double lds_sum[CUR_SUMS][CUR_WAVES];
+    __shared__ double lds_sum[CUR_SUMS][POST_WAVES];
     const int t = threadIdx.x;
     double sv[CUR_SUMS];
 #pragma unroll
-    for (int k = 0; k < CUR_SUMS; ++k) sv[k] = (t < nb && k < n_slots) ? sum_part[(size_t)k * CUR_BLOCKS + t] : 0.0;
+    for (int k = 0; k < CUR_SUMS; ++k) sv[k] = (t < nb && k < n_slots) ? sum_part[(size_t)k * POST_BLOCKS + t] : 0.0;
     const int bad = t < nb && flag_part[t];
-    const double s = cur_block_sums(sv, lds_sum);
+    const double s = block_sums(sv, lds_sum);
     const int any_bad = __syncthreads_or(bad);
     if (t < CUR_SUMS) res->sum[t] = s;
     if (t == 0) {
@@ -363,9 +332,7 @@ void currents_release(Ctx &c) {
     Currents *k = c.currents;
     if (!k) return;
     if (k->cg) {
-        void *cgp[] = {k->cg->r, k->cg->z, k->cg->p, k->cg->q, k->cg->partials, k->cg->red};
-        for (void *p : cgp)
-            if (p) hipFree(p);
+        photo_cg_free(*k->cg);
         delete k->cg;
     }
     void *ptrs[] = {k->psi, k->sum_part, k->flag_part, k->result, k->psi_new, k->rhs, k->x, k->b, k->fixed};
@@ -377,43 +344,24 @@ void currents_release(Ctx &c) {
 
 namespace {
 
-int cur_refuse(const char *who, const std::string &why) {
-    set_error(std::string(who) + ": " + why);
-    return -2;
-}
-
 // the contexts the kernels are instantiated for (0), or the refusal
 int cur_check_ctx(const Ctx &c, const char *who) {
     if (c.model_kind == 0 && !c.poisson)
-        return cur_refuse(who, "the model has no Poisson equation (the currents are those of its potential)");
+        return refuse(who, "the model has no Poisson equation (the currents are those of its potential)");
     if (c.comm || c.n_owned != c.nv)
-        return cur_refuse(who, "the electrode currents run on one GPU (this context has a transport or ghost vertices)");
+        return refuse(who, "the electrode currents run on one GPU (this context has a transport or ghost vertices)");
     if (c.model_kind == 1 && (c.neq < 3 || c.neq > 6))
-        return cur_refuse(who, std::to_string(c.neq) + " equations: 3 to 6 are built");
+        return refuse(who, std::to_string(c.neq) + " equations: 3 to 6 are built");
     return 0;
 }
 
-template <class T>
-int cur_device_array(T *&dst, size_t n) {
-    FEDM_HIP_CHECK(hipMalloc((void **)&dst, sizeof(T) * std::max<size_t>(n, 1)));
-    FEDM_HIP_CHECK(hipMemset(dst, 0, sizeof(T) * std::max<size_t>(n, 1)));
-    return 0;
-}
-
-int cur_blocks(const Ctx &c) { return std::max(std::min((c.nc + CUR_THREADS - 1) / CUR_THREADS, CUR_BLOCKS), 1); }
-
-int cur_read(Ctx &c, CurResult &r) {
-    FEDM_HIP_CHECK(hipMemcpyAsync(&r, c.currents->result, sizeof(CurResult), hipMemcpyDeviceToHost, c.stream));
-    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
-    FEDM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
+int cur_blocks(const Ctx &c) { return std::max(std::min((c.nc + POST_THREADS - 1) / POST_THREADS, POST_BLOCKS), 1); }
 
 // the capacitance matrix of the potentials psi[n_psi][nvp] into cap: a launch and a read-back per column
 int form_capacitance(Ctx &c, const double *psi, int n_psi, double cap[CUR_MAX][CUR_MAX]) {
     Currents &k = *c.currents;
     const int nb = cur_blocks(c);
-    const dim3 t(CUR_THREADS);
+    const dim3 t(POST_THREADS);
     for (int h = 0; h < n_psi; ++h) {
         if (c.model_kind == 0)
             hipLaunchKernelGGL((currents_capacitance_kernel<fedm_model_desc>), dim3(nb), t, 0, c.stream, c.nc, c.nvp,
@@ -423,7 +371,7 @@ int form_capacitance(Ctx &c, const double *psi, int n_psi, double cap[CUR_MAX][C
                                c.d_coords, c.d_cells, psi, h, k.sum_part, k.flag_part);
         hipLaunchKernelGGL(currents_finish_kernel, dim3(1), t, 0, c.stream, nb, CUR_MAX, k.sum_part, k.flag_part, k.result);
         CurResult r;
-        if (const int rc = cur_read(c, r)) return rc;
+        if (const int rc = read_result(c, r, c.currents->result)) return rc;
         for (int g = 0; g <= h; ++g) cap[g][h] = cap[h][g] = r.sum[g];
     }
     return 0;
@@ -432,38 +380,24 @@ int form_capacitance(Ctx &c, const double *psi, int n_psi, double cap[CUR_MAX][C
 void launch_currents(Ctx &c) {
     Currents &k = *c.currents;
     const int nb = cur_blocks(c);
-    const dim3 t(CUR_THREADS);
+    const dim3 t(POST_THREADS);
     if (c.model_kind == 0) {
-        auto go = [&](auto ns, auto tab) {
+        // (cur_check_ctx has required the Poisson equation: the PO switch is always true here)
+        with_model_flags(c, [&](auto ns, auto, auto tab) {
             constexpr int NS = decltype(ns)::value;
             constexpr bool TAB = decltype(tab)::value;
             hipLaunchKernelGGL((currents_cell_kernel<NS, TAB>), dim3(nb), t, 0, c.stream, c.nc, c.nvp, c.d_model,
                                c.d_coords, c.d_cells, c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, k.psi, k.n_psi,
                                k.sum_part, k.flag_part);
-        };
-        auto tab = [&](auto ns) {
-            if (c.model_tables) go(ns, std::true_type{});
-            else go(ns, std::false_type{});
-        };
-        switch (c.ns) {   // (the instantiations the assembly has with a Poisson equation)
-            case 1: tab(std::integral_constant<int, 1>{}); break;
-            case 2: tab(std::integral_constant<int, 2>{}); break;
-            case 3: tab(std::integral_constant<int, 3>{}); break;
-            default: tab(std::integral_constant<int, 4>{}); break;
-        }
+        });
     } else {
-        auto go = [&](auto neq) {
+        // (cur_check_ctx has refused the equation counts that are not built)
+        with_gd_neq(c, [&](auto neq) {
             constexpr int NEQ = decltype(neq)::value;
             hipLaunchKernelGGL((gd_currents_cell_kernel<NEQ>), dim3(nb), t, 0, c.stream, c.nc, c.nv, c.nvp, c.d_gd,
                                c.d_gd_fields, c.d_coords, c.d_cells, c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, k.psi,
                                k.n_psi, k.sum_part, k.flag_part);
-        };
-        switch (c.neq) {   // (what launch_assemble_gd instantiates; cur_check_ctx has refused the others)
-            case 3: go(std::integral_constant<int, 3>{}); break;
-            case 4: go(std::integral_constant<int, 4>{}); break;
-            case 5: go(std::integral_constant<int, 5>{}); break;
-            default: go(std::integral_constant<int, 6>{}); break;
-        }
+        });
     }
     hipLaunchKernelGGL(currents_finish_kernel, dim3(1), t, 0, c.stream, nb, CUR_SUMS, k.sum_part, k.flag_part, k.result);
 }
@@ -473,13 +407,11 @@ int ensure_solve_buffers(Ctx &c) {
     if (k.cg) return 0;
     const size_t nvp = (size_t)c.nvp;
     k.cg = new Photo();
-    if (cur_device_array(k.psi_new, nvp * CUR_MAX) || cur_device_array(k.rhs, nvp * CUR_MAX) ||
-        cur_device_array(k.x, nvp) || cur_device_array(k.b, nvp) || cur_device_array(k.fixed, nvp) ||
-        cur_device_array(k.cg->r, nvp) || cur_device_array(k.cg->z, nvp) || cur_device_array(k.cg->p, nvp) ||
-        cur_device_array(k.cg->q, nvp) || cur_device_array(k.cg->partials, (size_t)2 * PHOTO_RED_BLOCKS) ||
-        cur_device_array(k.cg->red, 4)) {
-        // nothing half-made stays behind: the next call starts from nothing again
-        void *ptrs[] = {k.psi_new, k.rhs, k.x, k.b, k.fixed, k.cg->r, k.cg->z, k.cg->p, k.cg->q, k.cg->partials, k.cg->red};
+    if (device_array<double>(k.psi_new, nullptr, nvp * CUR_MAX) || device_array<double>(k.rhs, nullptr, nvp * CUR_MAX) ||
+        device_array<double>(k.x, nullptr, nvp) || device_array<double>(k.b, nullptr, nvp) ||
+        device_array<unsigned char>(k.fixed, nullptr, nvp) || photo_cg_alloc(*k.cg, nvp)) {
+        // nothing half-made stays behind (photo_cg_alloc has freed its own): the next call starts from nothing again
+        void *ptrs[] = {k.psi_new, k.rhs, k.x, k.b, k.fixed};
         for (void *p : ptrs)
             if (p) hipFree(p);
         k.psi_new = k.rhs = k.x = k.b = nullptr;
@@ -500,21 +432,22 @@ extern "C" {
 
 int fedm_currents_setup(fedm_ctx *h, int n_psi, const double *psi) {
     const char *who = "fedm_currents_setup";
-    if (!h || !psi) return cur_refuse(who, "null argument");
+    if (!h || !psi) return refuse(who, "null argument");
     Ctx &c = h->c;
     if (const int rc = cur_check_ctx(c, who)) return rc;
     if (n_psi < 1 || n_psi > CUR_MAX)
-        return cur_refuse(who, std::to_string(n_psi) + " weighting potentials, 1 to " + std::to_string(CUR_MAX) + " are possible");
+        return refuse(who, std::to_string(n_psi) + " weighting potentials, 1 to " + std::to_string(CUR_MAX) + " are possible");
     for (size_t i = 0; i < (size_t)n_psi * c.nv; ++i)
         if (!std::isfinite(psi[i]))
-            return cur_refuse(who, "psi[" + std::to_string(i / c.nv) + "][" + std::to_string(i % c.nv) + "] is not finite");
+            return refuse(who, "psi[" + std::to_string(i / c.nv) + "][" + std::to_string(i % c.nv) + "] is not finite");
     FEDM_HIP_CHECK(hipSetDevice(c.device));
     FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
     if (!c.currents) {
         Currents *k = new Currents();
         c.currents = k;
-        if (cur_device_array(k->psi, (size_t)c.nvp * CUR_MAX) || cur_device_array(k->sum_part, (size_t)CUR_SUMS * CUR_BLOCKS) ||
-            cur_device_array(k->flag_part, CUR_BLOCKS) || cur_device_array(k->result, 1)) {
+        if (device_array<double>(k->psi, nullptr, (size_t)c.nvp * CUR_MAX) ||
+            device_array<double>(k->sum_part, nullptr, (size_t)CUR_SUMS * POST_BLOCKS) ||
+            device_array<int>(k->flag_part, nullptr, POST_BLOCKS) || device_array<CurResult>(k->result, nullptr, 1)) {
             currents_release(c);
             return -1;
         }
@@ -534,23 +467,23 @@ int fedm_currents_setup(fedm_ctx *h, int n_psi, const double *psi) {
 int fedm_currents_solve(fedm_ctx *h, const fedm_photo_hierarchy *laplace, const double *rhs, double rtol, int max_it,
                         int iterations[FEDM_CURRENTS_MAX]) {
     const char *who = "fedm_currents_solve";
-    if (!h || !laplace || !rhs) return cur_refuse(who, "null argument");
+    if (!h || !laplace || !rhs) return refuse(who, "null argument");
     Ctx &c = h->c;
     if (const int rc = cur_check_ctx(c, who)) return rc;
-    if (!c.currents || c.currents->n_psi == 0) return cur_refuse(who, "fedm_currents_setup has not been called");
+    if (!c.currents || c.currents->n_psi == 0) return refuse(who, "fedm_currents_setup has not been called");
     Currents &k = *c.currents;
-    if (!(rtol > 0.0) || max_it < 0) return cur_refuse(who, "rtol must be positive and max_it not negative");
+    if (!(rtol > 0.0) || max_it < 0) return refuse(who, "rtol must be positive and max_it not negative");
     const fedm_photo_hierarchy &t = *laplace;
     if (t.n_levels < 1 || !t.A || (t.n_levels > 1 && (!t.P || !t.R || !t.coarse_inverse || t.nu < 1)))
-        return cur_refuse(who, "bad hierarchy (levels with their prolongators, restrictions and a dense coarsest inverse; "
-                               "V(nu,nu) with nu >= 1)");
+        return refuse(who, "bad hierarchy (levels with their prolongators, restrictions and a dense coarsest inverse; "
+                           "V(nu,nu) with nu >= 1)");
     const fedm_csr &A0 = t.A[0];
     if (A0.n_rows != c.nv || A0.n_cols != c.nv || !A0.indptr || !A0.indices || !A0.values)
-        return cur_refuse(who, "the operator has " + std::to_string(A0.n_rows) + " rows, the mesh " + std::to_string(c.nv) +
-                                   " vertices");
+        return refuse(who, "the operator has " + std::to_string(A0.n_rows) + " rows, the mesh " + std::to_string(c.nv) +
+                               " vertices");
     for (size_t i = 0; i < (size_t)k.n_psi * c.nv; ++i)
         if (!std::isfinite(rhs[i]))
-            return cur_refuse(who, "rhs[" + std::to_string(i / c.nv) + "][" + std::to_string(i % c.nv) + "] is not finite");
+            return refuse(who, "rhs[" + std::to_string(i / c.nv) + "][" + std::to_string(i % c.nv) + "] is not finite");
     // the conductors' vertices: the unit rows of the eliminated operator (and the padding)
     std::vector<unsigned char> fixed((size_t)c.nvp, 1);
     for (int v = 0; v < c.nv; ++v) {
@@ -579,7 +512,7 @@ int fedm_currents_solve(fedm_ctx *h, const fedm_photo_hierarchy *laplace, const 
     }
     if (A.n_rows_p != c.nvp) {
         drop();
-        return cur_refuse(who, "the operator's padded rows differ from the context's");
+        return refuse(who, "the operator's padded rows differ from the context's");
     }
     if (t.n_levels > 1) {   // plain sweeps on every level, as a photoionisation term's
         if (const int rc = build_amg(c, c.nv, t.n_levels, t.A, t.P, t.R, t.coarse_inverse, t.nu, t.omega, &M, t.n_levels + 1)) {
@@ -638,9 +571,9 @@ int fedm_currents_solve(fedm_ctx *h, const fedm_photo_hierarchy *laplace, const 
 
 int fedm_currents_get_psi(fedm_ctx *h, double *psi) {
     const char *who = "fedm_currents_get_psi";
-    if (!h || !psi) return cur_refuse(who, "null argument");
+    if (!h || !psi) return refuse(who, "null argument");
     Ctx &c = h->c;
-    if (!c.currents || c.currents->n_psi == 0) return cur_refuse(who, "fedm_currents_setup has not been called");
+    if (!c.currents || c.currents->n_psi == 0) return refuse(who, "fedm_currents_setup has not been called");
     FEDM_HIP_CHECK(hipSetDevice(c.device));
     FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
     for (int g = 0; g < c.currents->n_psi; ++g)
@@ -651,15 +584,15 @@ int fedm_currents_get_psi(fedm_ctx *h, double *psi) {
 
 int fedm_currents(fedm_ctx *h, struct fedm_currents *out) {
     const char *who = "fedm_currents";
-    if (!h || !out) return cur_refuse(who, "null argument");
+    if (!h || !out) return refuse(who, "null argument");
     Ctx &c = h->c;
     if (const int rc = cur_check_ctx(c, who)) return rc;
-    if (!c.currents || c.currents->n_psi == 0) return cur_refuse(who, "fedm_currents_setup has not been called");
+    if (!c.currents || c.currents->n_psi == 0) return refuse(who, "fedm_currents_setup has not been called");
     const Currents &k = *c.currents;
     FEDM_HIP_CHECK(hipSetDevice(c.device));
     launch_currents(c);
     CurResult r;
-    if (const int rc = cur_read(c, r)) return rc;
+    if (const int rc = read_result(c, r, c.currents->result)) return rc;
     *out = {};
     for (int g = 0; g < k.n_psi; ++g) {
         out->conduction[g] = r.sum[CUR_COND + g];

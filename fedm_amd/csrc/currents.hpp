@@ -5,8 +5,6 @@
 
 namespace fedm {
 
-constexpr int CUR_BLOCKS = 256;   // workgroups of the cell pass at the most (beyond: a stride loop); the finish is one workgroup
-constexpr int CUR_THREADS = 256;
 constexpr int CUR_MAX = FEDM_CURRENTS_MAX;
 // slots of the cell pass's sums: a row of CUR_MAX per quantity
 constexpr int CUR_COND = 0, CUR_DISP = CUR_MAX, CUR_COUP = 2 * CUR_MAX, CUR_CHARGE = 3 * CUR_MAX;
@@ -22,9 +20,9 @@ struct Currents {
     int n_psi = 0;
     double *psi = nullptr;        // [CUR_MAX][nvp] the installed weighting potentials (padding stays 0)
     double cap[CUR_MAX][CUR_MAX] = {};   // the capacitance matrix of the installed potentials
-    // slot-major partials of the cell pass, one entry per workgroup
-    double *sum_part = nullptr;   // [CUR_SUMS][CUR_BLOCKS]
-    int *flag_part = nullptr;     // [CUR_BLOCKS]
+    // slot-major partials of the cell pass, one entry per workgroup (postproc.hpp, POST_BLOCKS at the most)
+    double *sum_part = nullptr;   // [CUR_SUMS][POST_BLOCKS]
+    int *flag_part = nullptr;     // [POST_BLOCKS]
     CurResult *result = nullptr;
     // fedm_currents_solve (allocated at its first call): the candidates, one system and the vectors scalar_pcg borrows
     double *psi_new = nullptr;    // [CUR_MAX][nvp]

@@ -3,105 +3,41 @@
 // a weighting potential, from the resident state.  A pass over the cells and one over the vertices write slot-major
 // partials, one workgroup reduces them; plain launches on the context's stream and one copy to the host.  Every sum
 // and maximum has a fixed order (thread, wave by shuffles, the workgroup's waves one after the other, the partials)
-// and nothing adds with floating-point atomics, so a call is bitwise reproducible -- photo.hip's pattern.
+// and nothing adds with floating-point atomics, so a call is bitwise reproducible -- photo.hip's pattern.  The
+// reductions' cores and the host's helpers are postproc.hpp's, one copy for every pass of this kind.
 #include "diag.hpp"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <type_traits>
 
-#include "device_util.hpp"
 #include "element.hpp"
+#include "postproc.hpp"
 #include "solver.hpp"
 
 namespace fedm {
-
-// ---- reductions ----------------------------------------------------------------------------------
-constexpr int DIAG_WAVES = DIAG_THREADS / 64;
-
-// a maximum with the index it sits at; on an exact tie the lower index stays.  Nothing compares greater than or equal
-// to a NaN, so a NaN is never taken: the not-finite flag reports it.
-struct MaxIdx {
-    double v;
-    int i;
-    __device__ __forceinline__ void take(double ov, int oi) {
-        if (ov > v || (ov == v && oi < i)) {
-            v = ov;
-            i = oi;
-        }
-    }
-};
-
-__device__ __forceinline__ MaxIdx wave_max(MaxIdx m) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_down(m.v, off, 64);
-        const int oi = __shfl_down(m.i, off, 64);
-        m.take(ov, oi);
-    }
-    return m;
-}
-
-// K values per thread -> K sums in the threads 0 .. K - 1 (thread k holds sum k): lanes by shuffles, then the waves
-// in ascending order
-template <int K>
-__device__ __forceinline__ double block_sums(const double (&v)[K], double (*lds)[DIAG_WAVES]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) lds[k][wave] = s;
-    }
-    __syncthreads();
-    double s = 0.0;
-    if ((int)threadIdx.x < K)
-        for (int w = 0; w < DIAG_WAVES; ++w) s += lds[threadIdx.x][w];
-    __syncthreads();
-    return s;
-}
-
-// K maxima per thread -> thread k holds maximum k
-template <int K>
-__device__ __forceinline__ MaxIdx block_maxes(const MaxIdx (&m)[K], double (*lv)[DIAG_WAVES], int (*li)[DIAG_WAVES]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const MaxIdx r = wave_max(m[k]);
-        if (lane == 0) {
-            lv[k][wave] = r.v;
-            li[k][wave] = r.i;
-        }
-    }
-    __syncthreads();
-    MaxIdx r{-INFINITY, INT_MAX};
-    if ((int)threadIdx.x < K)
-        for (int w = 0; w < DIAG_WAVES; ++w) r.take(lv[threadIdx.x][w], li[threadIdx.x][w]);
-    __syncthreads();
-    return r;
-}
 
 struct DiagWindow {
     double r_lo, r_hi, z_lo, z_hi;
 };
 
 // ---- the cells -------------------------------------------------------------------------------------
-// A thread per cell (a stride loop beyond DIAG_BLOCKS workgroups).  |E| and the coefficients once per cell as
+// A thread per cell (a stride loop beyond POST_BLOCKS workgroups).  |E| and the coefficients once per cell as
 // Element::setup has them, the densities at the model's quadrature points with Element::point's weight.  A cell with a
 // ghost vertex (n_owned < nv) weighs its integrals' terms by the owned basis functions' sum; a cell without one by
 // exactly 1.0.  The Poisson rows are the rows the assembly forms before dirichlet_kernel overwrites them: whole rows,
 // taken for the owned group vertices.
 template <int NS, bool PO, bool TAB>
-__global__ __launch_bounds__(DIAG_THREADS) void diag_cell_kernel(
+__global__ __launch_bounds__(POST_THREADS) void diag_cell_kernel(
     int nc, int n_owned, const fedm_model_desc *__restrict__ md, const double *__restrict__ coords,
     const int *__restrict__ cells, const double *__restrict__ u, const double *__restrict__ psi,
     const int8_t *__restrict__ group, int n_groups, DiagWindow win, double *__restrict__ sum_part,
     double *__restrict__ max_part, int *__restrict__ idx_part, int *__restrict__ flag_part) {
     constexpr int NEQ = NS + (PO ? 1 : 0);
     const double two_pi = 6.283185307179586476925286766559;
-    __shared__ double lds_sum[DIAG_SUMS][DIAG_WAVES];
-    __shared__ double lds_mv[DIAG_CELL_MAXES][DIAG_WAVES];
-    __shared__ int lds_mi[DIAG_CELL_MAXES][DIAG_WAVES];
+    __shared__ double lds_sum[DIAG_SUMS][POST_WAVES];
+    __shared__ double lds_mv[DIAG_CELL_MAXES][POST_WAVES];
+    __shared__ int lds_mi[DIAG_CELL_MAXES][POST_WAVES];
     const bool axi = md->axisymmetric != 0, lin = md->linear_representation != 0;
     const bool groups = PO && group && n_groups > 0;
     const int nq = md->n_qp;
@@ -245,23 +181,23 @@ __global__ __launch_bounds__(DIAG_THREADS) void diag_cell_kernel(
     const double s = block_sums(acc, lds_sum);
     const MaxIdx m = block_maxes(mx, lds_mv, lds_mi);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
-    if ((int)threadIdx.x < DIAG_SUMS) sum_part[(size_t)threadIdx.x * DIAG_BLOCKS + blockIdx.x] = s;
+    if ((int)threadIdx.x < DIAG_SUMS) sum_part[(size_t)threadIdx.x * POST_BLOCKS + blockIdx.x] = s;
     if ((int)threadIdx.x < DIAG_CELL_MAXES) {
-        max_part[(size_t)threadIdx.x * DIAG_BLOCKS + blockIdx.x] = m.v;
-        idx_part[(size_t)threadIdx.x * DIAG_BLOCKS + blockIdx.x] = m.i;
+        max_part[(size_t)threadIdx.x * POST_BLOCKS + blockIdx.x] = m.v;
+        idx_part[(size_t)threadIdx.x * POST_BLOCKS + blockIdx.x] = m.i;
     }
     if (threadIdx.x == 0) flag_part[blockIdx.x] = any_bad;
 }
 
 // ---- the vertices ----------------------------------------------------------------------------------
 // A thread per owned vertex: the species' nodal maxima; every component is looked at for the flag.
-__global__ __launch_bounds__(DIAG_THREADS) void diag_vertex_kernel(int n_owned, int ns, int neq,
+__global__ __launch_bounds__(POST_THREADS) void diag_vertex_kernel(int n_owned, int ns, int neq,
                                                                    const double *__restrict__ u,
                                                                    double *__restrict__ max_part,
                                                                    int *__restrict__ idx_part,
                                                                    int *__restrict__ flag_part) {
-    __shared__ double lds_mv[FEDM_MAX_SPECIES][DIAG_WAVES];
-    __shared__ int lds_mi[FEDM_MAX_SPECIES][DIAG_WAVES];
+    __shared__ double lds_mv[FEDM_MAX_SPECIES][POST_WAVES];
+    __shared__ int lds_mi[FEDM_MAX_SPECIES][POST_WAVES];
     MaxIdx mx[FEDM_MAX_SPECIES];
 #pragma unroll
     for (int s = 0; s < FEDM_MAX_SPECIES; ++s) mx[s] = MaxIdx{-INFINITY, INT_MAX};
@@ -279,37 +215,37 @@ __global__ __launch_bounds__(DIAG_THREADS) void diag_vertex_kernel(int n_owned, 
     const MaxIdx m = block_maxes(mx, lds_mv, lds_mi);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
     if ((int)threadIdx.x < FEDM_MAX_SPECIES) {
-        max_part[(size_t)(DIAG_CELL_MAXES + threadIdx.x) * DIAG_BLOCKS + blockIdx.x] = m.v;
-        idx_part[(size_t)(DIAG_CELL_MAXES + threadIdx.x) * DIAG_BLOCKS + blockIdx.x] = m.i;
+        max_part[(size_t)(DIAG_CELL_MAXES + threadIdx.x) * POST_BLOCKS + blockIdx.x] = m.v;
+        idx_part[(size_t)(DIAG_CELL_MAXES + threadIdx.x) * POST_BLOCKS + blockIdx.x] = m.i;
     }
-    if (threadIdx.x == 0) flag_part[DIAG_BLOCKS + blockIdx.x] = any_bad;
+    if (threadIdx.x == 0) flag_part[POST_BLOCKS + blockIdx.x] = any_bad;
 }
 
 // ---- second pass -----------------------------------------------------------------------------------
 // One workgroup: thread t brings the partials of workgroup t (nbc of the cell pass, nbv of the vertex pass, both at
-// most DIAG_BLOCKS = DIAG_THREADS), reduced slot by slot in the same fixed order.
-__global__ __launch_bounds__(DIAG_THREADS) void diag_finish_kernel(int nbc, int nbv, const double *__restrict__ coords,
+// most POST_BLOCKS = POST_THREADS), reduced slot by slot in the same fixed order.
+__global__ __launch_bounds__(POST_THREADS) void diag_finish_kernel(int nbc, int nbv, const double *__restrict__ coords,
                                                                    const int *__restrict__ cells,
                                                                    const double *__restrict__ sum_part,
                                                                    const double *__restrict__ max_part,
                                                                    const int *__restrict__ idx_part,
                                                                    const int *__restrict__ flag_part,
                                                                    DiagResult *__restrict__ res) {
-    __shared__ double lds_sum[DIAG_SUMS][DIAG_WAVES];
-    __shared__ double lds_mv[DIAG_CELL_MAXES + FEDM_MAX_SPECIES][DIAG_WAVES];
-    __shared__ int lds_mi[DIAG_CELL_MAXES + FEDM_MAX_SPECIES][DIAG_WAVES];
+    __shared__ double lds_sum[DIAG_SUMS][POST_WAVES];
+    __shared__ double lds_mv[DIAG_CELL_MAXES + FEDM_MAX_SPECIES][POST_WAVES];
+    __shared__ int lds_mi[DIAG_CELL_MAXES + FEDM_MAX_SPECIES][POST_WAVES];
     const int t = threadIdx.x;
     double sv[DIAG_SUMS];
 #pragma unroll
-    for (int k = 0; k < DIAG_SUMS; ++k) sv[k] = t < nbc ? sum_part[(size_t)k * DIAG_BLOCKS + t] : 0.0;
+    for (int k = 0; k < DIAG_SUMS; ++k) sv[k] = t < nbc ? sum_part[(size_t)k * POST_BLOCKS + t] : 0.0;
     MaxIdx mv[DIAG_CELL_MAXES + FEDM_MAX_SPECIES];
 #pragma unroll
     for (int k = 0; k < DIAG_CELL_MAXES + FEDM_MAX_SPECIES; ++k) {
         const bool have = t < (k < DIAG_CELL_MAXES ? nbc : nbv);
-        mv[k].v = have ? max_part[(size_t)k * DIAG_BLOCKS + t] : -INFINITY;
-        mv[k].i = have ? idx_part[(size_t)k * DIAG_BLOCKS + t] : INT_MAX;
+        mv[k].v = have ? max_part[(size_t)k * POST_BLOCKS + t] : -INFINITY;
+        mv[k].i = have ? idx_part[(size_t)k * POST_BLOCKS + t] : INT_MAX;
     }
-    const int bad = (t < nbc && flag_part[t]) || (t < nbv && flag_part[DIAG_BLOCKS + t]);
+    const int bad = (t < nbc && flag_part[t]) || (t < nbv && flag_part[POST_BLOCKS + t]);
     const double s = block_sums(sv, lds_sum);
     const MaxIdx m = block_maxes(mv, lds_mv, lds_mi);
     const int any_bad = __syncthreads_or(bad);
@@ -319,11 +255,7 @@ __global__ __launch_bounds__(DIAG_THREADS) void diag_finish_kernel(int nbc, int 
         res->cell_max[t] = none ? 0.0 : m.v;
         res->cell[t] = none ? -1 : m.i;
         double cr = 0.0, cz = 0.0;
-        if (!none) {
-            const int v0 = cells[3 * (size_t)m.i], v1 = cells[3 * (size_t)m.i + 1], v2 = cells[3 * (size_t)m.i + 2];
-            cr = (coords[2 * (size_t)v0] + coords[2 * (size_t)v1] + coords[2 * (size_t)v2]) / 3.0;
-            cz = (coords[2 * (size_t)v0 + 1] + coords[2 * (size_t)v1 + 1] + coords[2 * (size_t)v2 + 1]) / 3.0;
-        }
+        if (!none) cell_centroid(coords, cells, m.i, cr, cz);
         res->centroid[t][0] = cr;
         res->centroid[t][1] = cz;
     } else if (t < DIAG_CELL_MAXES + FEDM_MAX_SPECIES) {
@@ -350,11 +282,6 @@ void diag_release(Ctx &c) {
 
 namespace {
 
-int refuse(const char *who, const std::string &why) {
-    set_error(std::string(who) + ": " + why);
-    return -2;
-}
-
 // the contexts the kernels are instantiated for (0), or the refusal
 int check_ctx(const Ctx &c, const char *who) {
     if (c.model_kind != 0) return refuse(who, "the LMEA family has no diagnostics (LFA models only)");
@@ -368,10 +295,10 @@ int ensure_diag(Ctx &c) {
     Diag *d = new Diag();
     c.diag = d;
     constexpr int NMAX = DIAG_CELL_MAXES + FEDM_MAX_SPECIES;
-    if (hipMalloc((void **)&d->sum_part, sizeof(double) * DIAG_SUMS * DIAG_BLOCKS) != hipSuccess ||
-        hipMalloc((void **)&d->max_part, sizeof(double) * NMAX * DIAG_BLOCKS) != hipSuccess ||
-        hipMalloc((void **)&d->idx_part, sizeof(int) * NMAX * DIAG_BLOCKS) != hipSuccess ||
-        hipMalloc((void **)&d->flag_part, sizeof(int) * 2 * DIAG_BLOCKS) != hipSuccess ||
+    if (hipMalloc((void **)&d->sum_part, sizeof(double) * DIAG_SUMS * POST_BLOCKS) != hipSuccess ||
+        hipMalloc((void **)&d->max_part, sizeof(double) * NMAX * POST_BLOCKS) != hipSuccess ||
+        hipMalloc((void **)&d->idx_part, sizeof(int) * NMAX * POST_BLOCKS) != hipSuccess ||
+        hipMalloc((void **)&d->flag_part, sizeof(int) * 2 * POST_BLOCKS) != hipSuccess ||
         hipMalloc((void **)&d->result, sizeof(DiagResult)) != hipSuccess) {
         diag_release(c);
         set_error("fedm_diagnostics: out of device memory for the reductions' buffers");
@@ -380,32 +307,11 @@ int ensure_diag(Ctx &c) {
     return 0;
 }
 
-// The model's compile-time switches from its run-time flags: fn(NS, PO, TAB) -- the instantiations the assembly has
-// (one or two species without a Poisson equation, one to four with; tables need |E|, hence a Poisson equation)
-template <class Fn>
-void with_model_flags(const Ctx &c, Fn &&fn) {
-    auto tab = [&](auto ns) {
-        if (c.model_tables) fn(ns, std::true_type{}, std::true_type{});
-        else fn(ns, std::true_type{}, std::false_type{});
-    };
-    if (!c.poisson) {
-        if (c.ns == 1) fn(std::integral_constant<int, 1>{}, std::false_type{}, std::false_type{});
-        else fn(std::integral_constant<int, 2>{}, std::false_type{}, std::false_type{});
-        return;
-    }
-    switch (c.ns) {
-        case 1: tab(std::integral_constant<int, 1>{}); break;
-        case 2: tab(std::integral_constant<int, 2>{}); break;
-        case 3: tab(std::integral_constant<int, 3>{}); break;
-        default: tab(std::integral_constant<int, 4>{}); break;
-    }
-}
-
 void launch_diagnostics(Ctx &c, const double *u, const DiagWindow &win) {
     Diag &d = *c.diag;
-    const int nbc = std::min((c.nc + DIAG_THREADS - 1) / DIAG_THREADS, DIAG_BLOCKS);
-    const int nbv = std::max(std::min((c.n_owned + DIAG_THREADS - 1) / DIAG_THREADS, DIAG_BLOCKS), 1);
-    const dim3 b(DIAG_THREADS);
+    const int nbc = std::min((c.nc + POST_THREADS - 1) / POST_THREADS, POST_BLOCKS);
+    const int nbv = std::max(std::min((c.n_owned + POST_THREADS - 1) / POST_THREADS, POST_BLOCKS), 1);
+    const dim3 b(POST_THREADS);
     with_model_flags(c, [&](auto ns, auto po, auto tab) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool PO = decltype(po)::value, TAB = decltype(tab)::value;
@@ -431,37 +337,7 @@ int fedm_diag_setup(fedm_ctx *h, const double *psi, const int8_t *group, int n_g
     if (!h) return refuse(who, "null context");
     Ctx &c = h->c;
     if (const int rc = check_ctx(c, who)) return rc;
-    if (n_groups < 0 || n_groups > FEDM_DIAG_MAX_GROUPS)
-        return refuse(who, std::to_string(n_groups) + " groups, 0 to " + std::to_string(FEDM_DIAG_MAX_GROUPS) + " are possible");
-    if ((n_groups > 0) != (group != nullptr)) return refuse(who, "groups go with their array and the array with n_groups > 0");
-    if (group && !c.poisson) return refuse(who, "vertex groups need the Poisson row, and the model has no Poisson equation");
-    for (int v = 0; group && v < c.nv; ++v)
-        if (group[v] < 0 || group[v] > n_groups)
-            return refuse(who, "group[" + std::to_string(v) + "] = " + std::to_string((int)group[v]) + " outside 0.." +
-                                   std::to_string(n_groups));
-    for (int v = 0; psi && v < c.nv; ++v)
-        if (!std::isfinite(psi[v])) return refuse(who, "psi[" + std::to_string(v) + "] is not finite");
-    FEDM_HIP_CHECK(hipSetDevice(c.device));
-    if (const int rc = ensure_diag(c)) return rc;
-    Diag &d = *c.diag;
-    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
-    if (d.psi) hipFree(d.psi);
-    if (d.group) hipFree(d.group);
-    d.psi = nullptr;
-    d.group = nullptr;
-    d.n_groups = 0;
-    if (psi) {
-        FEDM_HIP_CHECK(hipMalloc((void **)&d.psi, sizeof(double) * c.nvp));
-        FEDM_HIP_CHECK(hipMemset(d.psi, 0, sizeof(double) * c.nvp));
-        FEDM_HIP_CHECK(hipMemcpy(d.psi, psi, sizeof(double) * c.nv, hipMemcpyHostToDevice));
-    }
-    if (group) {
-        FEDM_HIP_CHECK(hipMalloc((void **)&d.group, c.nvp));
-        FEDM_HIP_CHECK(hipMemset(d.group, 0, c.nvp));
-        FEDM_HIP_CHECK(hipMemcpy(d.group, group, c.nv, hipMemcpyHostToDevice));
-        d.n_groups = n_groups;
-    }
-    return 0;
+    return weighting_setup(c, who, FEDM_DIAG_MAX_GROUPS, true, psi, group, n_groups, c.diag, ensure_diag);
 }
 
 int fedm_diagnostics(fedm_ctx *h, const fedm_diag_opts *opts, fedm_diag *out) {
@@ -481,9 +357,7 @@ int fedm_diagnostics(fedm_ctx *h, const fedm_diag_opts *opts, fedm_diag *out) {
     }
     launch_diagnostics(c, opts->state == 0 ? c.d_u : c.d_uold, DiagWindow{opts->r_lo, opts->r_hi, opts->z_lo, opts->z_hi});
     DiagResult r;
-    FEDM_HIP_CHECK(hipMemcpyAsync(&r, c.diag->result, sizeof(DiagResult), hipMemcpyDeviceToHost, c.stream));
-    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
-    FEDM_HIP_CHECK(hipGetLastError());
+    if (const int rc = read_result(c, r, c.diag->result)) return rc;
     *out = fedm_diag{};
     for (int s = 0; s < c.ns; ++s) {
         out->species_integral[s] = r.sum[s];

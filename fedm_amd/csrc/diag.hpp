@@ -5,8 +5,6 @@
 
 namespace fedm {
 
-constexpr int DIAG_BLOCKS = 256;   // workgroups of a first pass at the most (beyond: a stride loop); the second pass is one workgroup
-constexpr int DIAG_THREADS = 256;
 // slots of the cell pass's sums: species integrals, the induced current, the groups
 constexpr int DIAG_SUM_CURRENT = FEDM_MAX_SPECIES, DIAG_SUM_GROUP0 = FEDM_MAX_SPECIES + 1;
 constexpr int DIAG_SUMS = DIAG_SUM_GROUP0 + FEDM_DIAG_MAX_GROUPS;
@@ -25,11 +23,11 @@ struct Diag {
     double *psi = nullptr;        // [nvp] weighting potential, or null
     int8_t *group = nullptr;      // [nvp] 0 or 1..n_groups, or null
     int n_groups = 0;
-    // slot-major partials of the two first passes, one entry per workgroup
-    double *sum_part = nullptr;   // [DIAG_SUMS][DIAG_BLOCKS]
-    double *max_part = nullptr;   // [DIAG_CELL_MAXES + FEDM_MAX_SPECIES][DIAG_BLOCKS]
+    // slot-major partials of the two first passes, one entry per workgroup (postproc.hpp, POST_BLOCKS at the most)
+    double *sum_part = nullptr;   // [DIAG_SUMS][POST_BLOCKS]
+    double *max_part = nullptr;   // [DIAG_CELL_MAXES + FEDM_MAX_SPECIES][POST_BLOCKS]
     int *idx_part = nullptr;      // the same shape: where each maximum sits
-    int *flag_part = nullptr;     // [2][DIAG_BLOCKS] not-finite flags of the cell and the vertex pass
+    int *flag_part = nullptr;     // [2][POST_BLOCKS] not-finite flags of the cell and the vertex pass
     DiagResult *result = nullptr;
 };
 

@@ -6,17 +6,16 @@
 // launches on the context's stream; no kernel caps its grid, none waits for another workgroup, and nothing adds with
 // floating-point atomics: a call is bitwise reproducible.  The set-up, the consistent solve, the blend, the probes and
 // the read-back serve the LMEA family's fedm_gd_fields as well (gd_fields.hip has its cell and vertex pass): fields.hpp
-// declares what the two share.
+// declares what the two share; the host's helpers are postproc.hpp's.
 #include "fields.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <type_traits>
 
 #include "comm.hpp"
-#include "device_util.hpp"
 #include "element.hpp"
+#include "postproc.hpp"
 #include "solver.hpp"
 
 namespace fedm {
@@ -232,9 +231,7 @@ void fields_release(Ctx &c) {
     if (!f) return;
     f->M.release();
     if (f->cg) {
-        void *cgp[] = {f->cg->r, f->cg->z, f->cg->p, f->cg->q, f->cg->partials, f->cg->red};
-        for (void *p : cgp)
-            if (p) hipFree(p);
+        photo_cg_free(*f->cg);
         delete f->cg;
     }
     void *ptrs[] = {f->v_ptr, f->v_idx, f->m, f->cell_b, f->out, f->first, f->flag, f->rhs, f->p_vert, f->p_w, f->p_out};
@@ -245,28 +242,13 @@ void fields_release(Ctx &c) {
     c.fields = nullptr;
 }
 
-int fields_refuse(const char *who, const std::string &why) {
-    set_error(std::string(who) + ": " + why);
-    return -2;
-}
-
 namespace {
-
-int refuse(const char *who, const std::string &why) { return fields_refuse(who, why); }
 
 // the contexts the cell kernel is instantiated for (0), or the refusal
 int check_ctx(const Ctx &c, const char *who) {
     if (c.model_kind != 0) return refuse(who, "the LMEA family has no field output (LFA models only)");
     if (!c.poisson && c.ns > 2)
         return refuse(who, std::to_string(c.ns) + " species without a Poisson equation: at most 2 are built");
-    return 0;
-}
-
-template <class T>
-int device_array(T *&dst, const T *src, size_t n) {
-    FEDM_HIP_CHECK(hipMalloc((void **)&dst, sizeof(T) * std::max<size_t>(n, 1)));
-    if (src) FEDM_HIP_CHECK(hipMemcpy(dst, src, sizeof(T) * n, hipMemcpyHostToDevice));
-    else FEDM_HIP_CHECK(hipMemset(dst, 0, sizeof(T) * std::max<size_t>(n, 1)));
     return 0;
 }
 
@@ -311,36 +293,11 @@ int setup_impl(Ctx &c, const fedm_csr *mass, const char *who) {
         }
         if (f.M.n_rows_p != c.nvp) return refuse(who, "the mass matrix's padded rows differ from the context's");
         f.cg = new Photo();
-        if (device_array<double>(f.rhs, nullptr, nvp) || device_array<double>(f.cg->r, nullptr, nvp) ||
-            device_array<double>(f.cg->z, nullptr, nvp) || device_array<double>(f.cg->p, nullptr, nvp) ||
-            device_array<double>(f.cg->q, nullptr, nvp) ||
-            device_array<double>(f.cg->partials, nullptr, (size_t)2 * PHOTO_RED_BLOCKS) ||
-            device_array<double>(f.cg->red, nullptr, 4))
-            return -1;
+        if (device_array<double>(f.rhs, nullptr, nvp) || photo_cg_alloc(*f.cg, nvp)) return -1;
         f.have_mass = true;
     }
     FEDM_HIP_CHECK(hipDeviceSynchronize());
     return 0;
-}
-
-// The model's compile-time switches from its run-time flags: fn(NS, PO, TAB) -- the instantiations the assembly has
-template <class Fn>
-void with_model_flags(const Ctx &c, Fn &&fn) {
-    auto tab = [&](auto ns) {
-        if (c.model_tables) fn(ns, std::true_type{}, std::true_type{});
-        else fn(ns, std::true_type{}, std::false_type{});
-    };
-    if (!c.poisson) {
-        if (c.ns == 1) fn(std::integral_constant<int, 1>{}, std::false_type{}, std::false_type{});
-        else fn(std::integral_constant<int, 2>{}, std::false_type{}, std::false_type{});
-        return;
-    }
-    switch (c.ns) {
-        case 1: tab(std::integral_constant<int, 1>{}); break;
-        case 2: tab(std::integral_constant<int, 2>{}); break;
-        case 3: tab(std::integral_constant<int, 3>{}); break;
-        default: tab(std::integral_constant<int, 4>{}); break;
-    }
 }
 
 bool projected(int kind) { return kind >= FEDM_FIELD_E_R && kind <= FEDM_FIELD_FLUX_Z; }
@@ -506,9 +463,7 @@ int fields_run(Ctx &c, const fedm_field_opts &o, int n_req, const int *slot, boo
     if (nodal)
         FEDM_HIP_CHECK(hipMemcpyAsync(f.h_out, f.out, sizeof(double) * n_req * c.nvp, hipMemcpyDeviceToHost, c.stream));
     int flag = 0;
-    FEDM_HIP_CHECK(hipMemcpyAsync(&flag, f.flag, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
-    FEDM_HIP_CHECK(hipGetLastError());
+    if (const int rc2 = read_result(c, flag, f.flag)) return rc2;
     for (int k = 0; nodal && k < n_req; ++k)
         std::memcpy(nodal + (size_t)k * c.nv, f.h_out + (size_t)k * c.nvp, sizeof(double) * c.nv);
     *finite = flag ? 0 : 1;

@@ -35,7 +35,6 @@ struct Fields {
 // ---- what the two families' entry points share (fields.hip) -------------------------------------------
 // Ctx::fields serves both: a context is of one family for life, so it can only ever have had its own set-up.
 // `who`, `setup_name`, `probe_name`: the entry points a refusal names.
-int fields_refuse(const char *who, const std::string &why);   // sets the error, returns -2
 // the mass matrix's checks, then the vertex lists, the lumped mass and every buffer of a call; replaces an earlier set-up
 int fields_setup_shared(Ctx &c, const fedm_csr *mass, const char *who);
 int fields_probe_setup_shared(Ctx &c, int n_points, const int32_t *vertices, const double *weights, const char *who,

@@ -7,7 +7,8 @@
 // context's stream and one copy to the host.  Every sum and maximum has a fixed order (thread, wave by shuffles, the
 // workgroup's waves one after the other, the partials) and nothing adds with floating-point atomics or waits for
 // another workgroup, so a call is bitwise reproducible.  The point functions are gd_balance.hpp's value-only copies
-// of gd.hip's; tests/test_gpu_balance.py holds their sums to the assembled residual.
+// of gd.hip's; tests/test_gpu_balance.py holds their sums to the assembled residual.  The reductions' cores and the
+// host's helpers are postproc.hpp's.
 #include "gd_balance.hpp"
 
 #include <algorithm>
@@ -15,98 +16,16 @@
 #include <cmath>
 #include <vector>
 
-#include "device_util.hpp"
+#include "postproc.hpp"
 #include "solver.hpp"
 
 namespace fedm {
 
-// ---- reductions ----------------------------------------------------------------------------------
-constexpr int BAL_WAVES = BAL_THREADS / 64;
-
-// a maximum with the index it sits at; on an exact tie the lower index stays.  Nothing compares greater than or equal
-// to a NaN, so a NaN is never taken: the not-finite flag reports it.
-struct BalMax {
-    double v;
-    int i;
-    __device__ __forceinline__ void take(double ov, int oi) {
-        if (ov > v || (ov == v && oi < i)) {
-            v = ov;
-            i = oi;
-        }
-    }
-};
-
-__device__ __forceinline__ BalMax bal_wave_max(BalMax m) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_down(m.v, off, 64);
-        const int oi = __shfl_down(m.i, off, 64);
-        m.take(ov, oi);
-    }
-    return m;
-}
-
-// K values per thread -> thread k holds sum k: lanes by shuffles, then the waves in ascending order
-template <int K>
-__device__ __forceinline__ double bal_block_sums(const double (&v)[K], double (*lds)[BAL_WAVES]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) lds[k][wave] = s;
-    }
-    __syncthreads();
-    double s = 0.0;
-    if ((int)threadIdx.x < K)
-        for (int w = 0; w < BAL_WAVES; ++w) s += lds[threadIdx.x][w];
-    __syncthreads();
-    return s;
-}
-
-template <int K>
-__device__ __forceinline__ BalMax bal_block_maxes(const BalMax (&m)[K], double (*lv)[BAL_WAVES], int (*li)[BAL_WAVES]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const BalMax r = bal_wave_max(m[k]);
-        if (lane == 0) {
-            lv[k][wave] = r.v;
-            li[k][wave] = r.i;
-        }
-    }
-    __syncthreads();
-    BalMax r{-INFINITY, INT_MAX};
-    if ((int)threadIdx.x < K)
-        for (int w = 0; w < BAL_WAVES; ++w) r.take(lv[threadIdx.x][w], li[threadIdx.x][w]);
-    __syncthreads();
-    return r;
-}
-
-template <int NEQ>
-__device__ __forceinline__ bool bal_load_cell(int cell, const fedm_gd_desc *__restrict__ md,
-                                              const double *__restrict__ coords, const int *__restrict__ cells,
-                                              const double *__restrict__ u, BalCell &c, double U[3][NEQ]) {
-    bool bad = false;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        c.v[a] = cells[3 * (size_t)cell + a];
-        c.x[a][0] = coords[2 * (size_t)c.v[a]];
-        c.x[a][1] = coords[2 * (size_t)c.v[a] + 1];
-#pragma unroll
-        for (int e = 0; e < NEQ; ++e) {
-            U[a][e] = u[(size_t)c.v[a] * NEQ + e];
-            bad |= !isfinite(U[a][e]);
-        }
-    }
-    bal_cell_init(c, md->axisymmetric != 0);
-    return bad;
-}
-
 // ---- the cells -------------------------------------------------------------------------------------
-// A thread per cell (a stride loop beyond BAL_BLOCKS workgroups).  The accumulators are indexed by compile-time
+// A thread per cell (a stride loop beyond POST_BLOCKS workgroups).  The accumulators are indexed by compile-time
 // numbers only (the species' loops are unrolled, the groups' to their maximum with a guard).
 template <int NEQ>
-__global__ __launch_bounds__(BAL_THREADS) void gd_balance_cell_kernel(
+__global__ __launch_bounds__(POST_THREADS) void gd_balance_cell_kernel(
     int nc, int nv, const fedm_gd_desc *__restrict__ md, const double *__restrict__ fields,
     const double *__restrict__ coords, const int *__restrict__ cells, const double *__restrict__ u,
     const double *__restrict__ uold, const double *__restrict__ uold1, double dt, double dt_old,
@@ -114,22 +33,22 @@ __global__ __launch_bounds__(BAL_THREADS) void gd_balance_cell_kernel(
     double *__restrict__ max_part, int *__restrict__ idx_part, int *__restrict__ flag_part) {
     constexpr int ns = NEQ - 1, IPHI = NEQ - 1, ie = ns - 1;
     const double two_pi = 6.283185307179586476925286766559;
-    __shared__ double lds_sum[BAL_CELL_SUMS][BAL_WAVES];
-    __shared__ double lds_mv[1][BAL_WAVES];
-    __shared__ int lds_mi[1][BAL_WAVES];
+    __shared__ double lds_sum[BAL_CELL_SUMS][POST_WAVES];
+    __shared__ double lds_mv[1][POST_WAVES];
+    __shared__ int lds_mi[1][POST_WAVES];
     const int nr = md->n_reactions, nq = md->n_qp;
     const bool groups = group && n_groups > 0;
     const double tr = dt / dt_old, trp1 = 1.0 + tr, tr2p1 = 1.0 + 2.0 * tr;
     // the reactions' running sums live in LDS, a column per thread: their loop stays rolled (unrolled to the
     // descriptor's 16 reactions the kernel wanted more than 512 registers: 360 spilled bytes a lane for five
     // equations), and a run-time reaction index into LDS costs nothing
-    __shared__ double lds_reac[BAL_GR][BAL_THREADS];
+    __shared__ double lds_reac[BAL_GR][POST_THREADS];
     double acc[BAL_CELL_SUMS];
 #pragma unroll
     for (int k = 0; k < BAL_CELL_SUMS; ++k) acc[k] = 0.0;
 #pragma unroll
     for (int j = 0; j < BAL_GR; ++j) lds_reac[j][threadIdx.x] = 0.0;
-    BalMax mx[1] = {{-1.0, INT_MAX}};   // |E| >= 0: -1 stands for 'no cell'
+    MaxIdx mx[1] = {{-1.0, INT_MAX}};   // |E| >= 0: -1 stands for 'no cell'
     bool bad = false;
     for (int cell = blockIdx.x * blockDim.x + threadIdx.x; cell < nc; cell += gridDim.x * blockDim.x) {
         BalCell c;
@@ -247,10 +166,10 @@ __global__ __launch_bounds__(BAL_THREADS) void gd_balance_cell_kernel(
     }
 #pragma unroll
     for (int j = 0; j < BAL_GR; ++j) acc[BAL_REACTION + j] = lds_reac[j][threadIdx.x];
-    const double s = bal_block_sums(acc, lds_sum);
-    const BalMax m = bal_block_maxes(mx, lds_mv, lds_mi);
+    const double s = block_sums(acc, lds_sum);
+    const MaxIdx m = block_maxes(mx, lds_mv, lds_mi);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
-    if ((int)threadIdx.x < BAL_CELL_SUMS) sum_part[(size_t)threadIdx.x * BAL_BLOCKS + blockIdx.x] = s;
+    if ((int)threadIdx.x < BAL_CELL_SUMS) sum_part[(size_t)threadIdx.x * POST_BLOCKS + blockIdx.x] = s;
     if (threadIdx.x == 0) {
         max_part[blockIdx.x] = m.v;
         idx_part[blockIdx.x] = m.i;
@@ -259,16 +178,16 @@ __global__ __launch_bounds__(BAL_THREADS) void gd_balance_cell_kernel(
 }
 
 // ---- the tagged facets -----------------------------------------------------------------------------
-// Workgroup t owns tag t + 1 and walks its list; thread k the facets k, k + BAL_THREADS, ...  The integrands are the
+// Workgroup t owns tag t + 1 and walks its list; thread k the facets k, k + POST_THREADS, ...  The integrands are the
 // facet block of gd_element: the accumulators are indexed by the component, never by the tag.
 template <int NEQ>
-__global__ __launch_bounds__(BAL_THREADS) void gd_balance_facet_kernel(
+__global__ __launch_bounds__(POST_THREADS) void gd_balance_facet_kernel(
     int nv, const fedm_gd_desc *__restrict__ md, const double *__restrict__ fields, const double *__restrict__ coords,
     const int *__restrict__ cells, const double *__restrict__ u, BalFacets facets, const int *__restrict__ list,
     double *__restrict__ facet_part, int *__restrict__ flag_part) {
     constexpr int ns = NEQ - 1, ie = ns - 1;
     const double two_pi = 6.283185307179586476925286766559;
-    __shared__ double lds_sum[BAL_FACET_SUMS][BAL_WAVES];
+    __shared__ double lds_sum[BAL_FACET_SUMS][POST_WAVES];
     const int tag = blockIdx.x + 1, nr = md->n_reactions;
     double acc[BAL_FACET_SUMS];
 #pragma unroll
@@ -338,26 +257,26 @@ __global__ __launch_bounds__(BAL_THREADS) void gd_balance_facet_kernel(
         }
         bad |= !isfinite(chk);
     }
-    const double s = bal_block_sums(acc, lds_sum);
+    const double s = block_sums(acc, lds_sum);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
     if ((int)threadIdx.x < BAL_FACET_SUMS) facet_part[(size_t)threadIdx.x * FEDM_MAX_TAGS + blockIdx.x] = s;
-    if (threadIdx.x == 0) flag_part[2 * BAL_BLOCKS + blockIdx.x] = any_bad;
+    if (threadIdx.x == 0) flag_part[2 * POST_BLOCKS + blockIdx.x] = any_bad;
 }
 
 // ---- the vertices ----------------------------------------------------------------------------------
 // A thread per vertex: the nodal maxima of the components below the potential and of u_0 - u_e (the log of the mean
 // energy); every component is looked at for the flag.
 template <int NEQ>
-__global__ __launch_bounds__(BAL_THREADS) void gd_balance_vertex_kernel(int nv, const double *__restrict__ u,
+__global__ __launch_bounds__(POST_THREADS) void gd_balance_vertex_kernel(int nv, const double *__restrict__ u,
                                                                         double *__restrict__ max_part,
                                                                         int *__restrict__ idx_part,
                                                                         int *__restrict__ flag_part) {
     constexpr int ns = NEQ - 1, NM = ns + 1;
-    __shared__ double lds_mv[NM][BAL_WAVES];
-    __shared__ int lds_mi[NM][BAL_WAVES];
-    BalMax mx[NM];
+    __shared__ double lds_mv[NM][POST_WAVES];
+    __shared__ int lds_mi[NM][POST_WAVES];
+    MaxIdx mx[NM];
 #pragma unroll
-    for (int s = 0; s < NM; ++s) mx[s] = BalMax{-INFINITY, INT_MAX};
+    for (int s = 0; s < NM; ++s) mx[s] = MaxIdx{-INFINITY, INT_MAX};
     bool bad = false;
     for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += gridDim.x * blockDim.x) {
         double val[NEQ];
@@ -370,45 +289,45 @@ __global__ __launch_bounds__(BAL_THREADS) void gd_balance_vertex_kernel(int nv, 
         for (int s = 0; s < ns; ++s) mx[s].take(val[s], v);
         mx[ns].take(val[0] - val[ns - 1], v);
     }
-    const BalMax m = bal_block_maxes(mx, lds_mv, lds_mi);
+    const MaxIdx m = block_maxes(mx, lds_mv, lds_mi);
     const int any_bad = __syncthreads_or(bad ? 1 : 0);
     if ((int)threadIdx.x < NM) {
         // (slot ns of this model goes to the last slot: the finish reads BAL_NODAL slots whatever the model)
         const int slot = (int)threadIdx.x == ns ? BAL_NODAL - 1 : (int)threadIdx.x;
-        max_part[(size_t)(1 + slot) * BAL_BLOCKS + blockIdx.x] = m.v;
-        idx_part[(size_t)(1 + slot) * BAL_BLOCKS + blockIdx.x] = m.i;
+        max_part[(size_t)(1 + slot) * POST_BLOCKS + blockIdx.x] = m.v;
+        idx_part[(size_t)(1 + slot) * POST_BLOCKS + blockIdx.x] = m.i;
     }
-    if (threadIdx.x == 0) flag_part[BAL_BLOCKS + blockIdx.x] = any_bad;
+    if (threadIdx.x == 0) flag_part[POST_BLOCKS + blockIdx.x] = any_bad;
 }
 
 // ---- second pass -----------------------------------------------------------------------------------
 // One workgroup: thread t brings the partials of workgroup t (nbc of the cell pass, nbv of the vertex pass, both at
-// most BAL_BLOCKS = BAL_THREADS), reduced slot by slot in the same fixed order; the tags' sums are final already.
+// most POST_BLOCKS = POST_THREADS), reduced slot by slot in the same fixed order; the tags' sums are final already.
 // `ns`: the model's; the nodal slots ns .. BAL_NODAL - 2 were never written and are not read.
-__global__ __launch_bounds__(BAL_THREADS) void gd_balance_finish_kernel(
+__global__ __launch_bounds__(POST_THREADS) void gd_balance_finish_kernel(
     int nbc, int nbv, int ns, const double *__restrict__ coords, const int *__restrict__ cells,
     const double *__restrict__ sum_part, const double *__restrict__ facet_part, const double *__restrict__ max_part,
     const int *__restrict__ idx_part, const int *__restrict__ flag_part, BalResult *__restrict__ res) {
     constexpr int NM = 1 + BAL_NODAL;
-    __shared__ double lds_sum[BAL_CELL_SUMS][BAL_WAVES];
-    __shared__ double lds_mv[NM][BAL_WAVES];
-    __shared__ int lds_mi[NM][BAL_WAVES];
+    __shared__ double lds_sum[BAL_CELL_SUMS][POST_WAVES];
+    __shared__ double lds_mv[NM][POST_WAVES];
+    __shared__ int lds_mi[NM][POST_WAVES];
     const int t = threadIdx.x;
     double sv[BAL_CELL_SUMS];
 #pragma unroll
-    for (int k = 0; k < BAL_CELL_SUMS; ++k) sv[k] = t < nbc ? sum_part[(size_t)k * BAL_BLOCKS + t] : 0.0;
-    BalMax mv[NM];
+    for (int k = 0; k < BAL_CELL_SUMS; ++k) sv[k] = t < nbc ? sum_part[(size_t)k * POST_BLOCKS + t] : 0.0;
+    MaxIdx mv[NM];
 #pragma unroll
     for (int k = 0; k < NM; ++k) {
         const bool used = k == 0 || k - 1 < ns || k == NM - 1;
         const bool have = used && t < (k == 0 ? nbc : nbv);
-        mv[k].v = have ? max_part[(size_t)k * BAL_BLOCKS + t] : -INFINITY;
-        mv[k].i = have ? idx_part[(size_t)k * BAL_BLOCKS + t] : INT_MAX;
+        mv[k].v = have ? max_part[(size_t)k * POST_BLOCKS + t] : -INFINITY;
+        mv[k].i = have ? idx_part[(size_t)k * POST_BLOCKS + t] : INT_MAX;
     }
-    const int bad = (t < nbc && flag_part[t]) || (t < nbv && flag_part[BAL_BLOCKS + t]) ||
-                    (t < FEDM_MAX_TAGS && flag_part[2 * BAL_BLOCKS + t]);
-    const double s = bal_block_sums(sv, lds_sum);
-    const BalMax m = bal_block_maxes(mv, lds_mv, lds_mi);
+    const int bad = (t < nbc && flag_part[t]) || (t < nbv && flag_part[POST_BLOCKS + t]) ||
+                    (t < FEDM_MAX_TAGS && flag_part[2 * POST_BLOCKS + t]);
+    const double s = block_sums(sv, lds_sum);
+    const MaxIdx m = block_maxes(mv, lds_mv, lds_mi);
     const int any_bad = __syncthreads_or(bad);
     if (t < BAL_CELL_SUMS) res->sum[t] = s;
     if (t < BAL_FACET_SUMS * FEDM_MAX_TAGS) (&res->facet[0][0])[t] = facet_part[t];
@@ -417,11 +336,7 @@ __global__ __launch_bounds__(BAL_THREADS) void gd_balance_finish_kernel(
         res->field_max = none ? 0.0 : m.v;
         res->cell = none ? -1 : m.i;
         double cr = 0.0, cz = 0.0;
-        if (!none) {
-            const int v0 = cells[3 * (size_t)m.i], v1 = cells[3 * (size_t)m.i + 1], v2 = cells[3 * (size_t)m.i + 2];
-            cr = (coords[2 * (size_t)v0] + coords[2 * (size_t)v1] + coords[2 * (size_t)v2]) / 3.0;
-            cz = (coords[2 * (size_t)v0 + 1] + coords[2 * (size_t)v1 + 1] + coords[2 * (size_t)v2 + 1]) / 3.0;
-        }
+        if (!none) cell_centroid(coords, cells, m.i, cr, cz);
         res->centroid[0] = cr;
         res->centroid[1] = cz;
         res->not_finite = any_bad;
@@ -446,14 +361,9 @@ void gd_balance_release(Ctx &c) {
 
 namespace {
 
-int bal_refuse(const char *who, const std::string &why) {
-    set_error(std::string(who) + ": " + why);
-    return -2;
-}
-
 int bal_check_ctx(const Ctx &c, const char *who) {
-    if (c.model_kind != 1) return bal_refuse(who, "an LFA context (the balance is the LMEA family's; fedm_diagnostics has the LFA observables)");
-    if (c.n_owned != c.nv) return bal_refuse(who, "a context with ghost vertices (one GPU only)");
+    if (c.model_kind != 1) return refuse(who, "an LFA context (the balance is the LMEA family's; fedm_diagnostics has the LFA observables)");
+    if (c.n_owned != c.nv) return refuse(who, "a context with ghost vertices (one GPU only)");
     return 0;
 }
 
@@ -475,11 +385,11 @@ int ensure_balance(Ctx &c) {
     }
     b->facets.ptr[FEDM_MAX_TAGS] = (int)list.size();
     constexpr int NM = 1 + BAL_NODAL;
-    bool ok = hipMalloc((void **)&b->sum_part, sizeof(double) * BAL_CELL_SUMS * BAL_BLOCKS) == hipSuccess &&
+    bool ok = hipMalloc((void **)&b->sum_part, sizeof(double) * BAL_CELL_SUMS * POST_BLOCKS) == hipSuccess &&
               hipMalloc((void **)&b->facet_part, sizeof(double) * BAL_FACET_SUMS * FEDM_MAX_TAGS) == hipSuccess &&
-              hipMalloc((void **)&b->max_part, sizeof(double) * NM * BAL_BLOCKS) == hipSuccess &&
-              hipMalloc((void **)&b->idx_part, sizeof(int) * NM * BAL_BLOCKS) == hipSuccess &&
-              hipMalloc((void **)&b->flag_part, sizeof(int) * (2 * BAL_BLOCKS + FEDM_MAX_TAGS)) == hipSuccess &&
+              hipMalloc((void **)&b->max_part, sizeof(double) * NM * POST_BLOCKS) == hipSuccess &&
+              hipMalloc((void **)&b->idx_part, sizeof(int) * NM * POST_BLOCKS) == hipSuccess &&
+              hipMalloc((void **)&b->flag_part, sizeof(int) * (2 * POST_BLOCKS + FEDM_MAX_TAGS)) == hipSuccess &&
               hipMalloc((void **)&b->result, sizeof(BalResult)) == hipSuccess &&
               hipMalloc((void **)&b->facet_list, sizeof(int) * std::max<size_t>(list.size(), 1)) == hipSuccess;
     if (ok && !list.empty())
@@ -495,9 +405,9 @@ int ensure_balance(Ctx &c) {
 template <int NEQ>
 void launch_balance(Ctx &c) {
     GdBalance &b = *c.gd_balance;
-    const int nbc = std::max(std::min((c.nc + BAL_THREADS - 1) / BAL_THREADS, BAL_BLOCKS), 1);
-    const int nbv = std::max(std::min((c.nv + BAL_THREADS - 1) / BAL_THREADS, BAL_BLOCKS), 1);
-    const dim3 t(BAL_THREADS);
+    const int nbc = std::max(std::min((c.nc + POST_THREADS - 1) / POST_THREADS, POST_BLOCKS), 1);
+    const int nbv = std::max(std::min((c.nv + POST_THREADS - 1) / POST_THREADS, POST_BLOCKS), 1);
+    const dim3 t(POST_THREADS);
     hipLaunchKernelGGL((gd_balance_cell_kernel<NEQ>), dim3(nbc), t, 0, c.stream, c.nc, c.nv, c.d_gd, c.d_gd_fields,
                        c.d_coords, c.d_cells, c.d_u, c.d_uold, c.d_uold1, c.dt, c.dt_old, b.psi, b.group, b.n_groups,
                        b.sum_part, b.max_part, b.idx_part, b.flag_part);
@@ -518,59 +428,23 @@ extern "C" {
 
 int fedm_gd_balance_setup(fedm_ctx *h, const double *psi, const int8_t *group, int n_groups) {
     const char *who = "fedm_gd_balance_setup";
-    if (!h) return bal_refuse(who, "null context");
+    if (!h) return refuse(who, "null context");
     Ctx &c = h->c;
     if (const int rc = bal_check_ctx(c, who)) return rc;
-    if (n_groups < 0 || n_groups > FEDM_GD_BAL_MAX_GROUPS)
-        return bal_refuse(who, std::to_string(n_groups) + " groups, 0 to " + std::to_string(FEDM_GD_BAL_MAX_GROUPS) + " are possible");
-    if ((n_groups > 0) != (group != nullptr)) return bal_refuse(who, "groups go with their array and the array with n_groups > 0");
-    for (int v = 0; group && v < c.nv; ++v)
-        if (group[v] < 0 || group[v] > n_groups)
-            return bal_refuse(who, "group[" + std::to_string(v) + "] = " + std::to_string((int)group[v]) + " outside 0.." +
-                                       std::to_string(n_groups));
-    for (int v = 0; psi && v < c.nv; ++v)
-        if (!std::isfinite(psi[v])) return bal_refuse(who, "psi[" + std::to_string(v) + "] is not finite");
-    FEDM_HIP_CHECK(hipSetDevice(c.device));
-    if (const int rc = ensure_balance(c)) return rc;
-    GdBalance &b = *c.gd_balance;
-    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
-    if (b.psi) hipFree(b.psi);
-    if (b.group) hipFree(b.group);
-    b.psi = nullptr;
-    b.group = nullptr;
-    b.n_groups = 0;
-    if (psi) {
-        FEDM_HIP_CHECK(hipMalloc((void **)&b.psi, sizeof(double) * c.nvp));
-        FEDM_HIP_CHECK(hipMemset(b.psi, 0, sizeof(double) * c.nvp));
-        FEDM_HIP_CHECK(hipMemcpy(b.psi, psi, sizeof(double) * c.nv, hipMemcpyHostToDevice));
-    }
-    if (group) {
-        FEDM_HIP_CHECK(hipMalloc((void **)&b.group, c.nvp));
-        FEDM_HIP_CHECK(hipMemset(b.group, 0, c.nvp));
-        FEDM_HIP_CHECK(hipMemcpy(b.group, group, c.nv, hipMemcpyHostToDevice));
-        b.n_groups = n_groups;
-    }
-    return 0;
+    return weighting_setup(c, who, FEDM_GD_BAL_MAX_GROUPS, false, psi, group, n_groups, c.gd_balance, ensure_balance);
 }
 
 int fedm_gd_balance(fedm_ctx *h, struct fedm_gd_balance *out) {
     const char *who = "fedm_gd_balance";
-    if (!h || !out) return bal_refuse(who, "null argument");
+    if (!h || !out) return refuse(who, "null argument");
     Ctx &c = h->c;
     if (const int rc = bal_check_ctx(c, who)) return rc;
     FEDM_HIP_CHECK(hipSetDevice(c.device));
     if (const int rc = ensure_balance(c)) return rc;
-    switch (c.neq) {   // (what launch_assemble_gd instantiates)
-        case 3: launch_balance<3>(c); break;
-        case 4: launch_balance<4>(c); break;
-        case 5: launch_balance<5>(c); break;
-        case 6: launch_balance<6>(c); break;
-        default: return bal_refuse(who, std::to_string(c.neq) + " equations: 3 to 6 are built");
-    }
+    if (c.neq < 3 || c.neq > 6) return refuse(who, std::to_string(c.neq) + " equations: 3 to 6 are built");
+    with_gd_neq(c, [&](auto neq) { launch_balance<decltype(neq)::value>(c); });
     BalResult r;
-    FEDM_HIP_CHECK(hipMemcpyAsync(&r, c.gd_balance->result, sizeof(BalResult), hipMemcpyDeviceToHost, c.stream));
-    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
-    FEDM_HIP_CHECK(hipGetLastError());
+    if (const int rc = read_result(c, r, c.gd_balance->result)) return rc;
     const int ns = c.neq - 1, nr = c.gd.n_reactions;
     *out = {};
     for (int s = 0; s < ns; ++s) {

@@ -7,8 +7,6 @@
 
 namespace fedm {
 
-constexpr int BAL_BLOCKS = 256;   // workgroups of the cell and the vertex pass at the most (beyond: a stride loop)
-constexpr int BAL_THREADS = 256;
 constexpr int BAL_GS = FEDM_GD_MAX_SPECIES, BAL_GR = FEDM_GD_MAX_REACTIONS;
 // slots of the cell pass's sums
 constexpr int BAL_CONTENT = 0, BAL_RATE = BAL_GS, BAL_REACTION = 2 * BAL_GS, BAL_LOSS = BAL_REACTION + BAL_GR,
@@ -39,12 +37,12 @@ struct GdBalance {
     int n_groups = 0;
     BalFacets facets{};
     int *facet_list = nullptr;    // [facets.ptr[FEDM_MAX_TAGS]]
-    // slot-major partials, one entry per workgroup
-    double *sum_part = nullptr;   // [BAL_CELL_SUMS][BAL_BLOCKS]
+    // slot-major partials, one entry per workgroup (postproc.hpp, POST_BLOCKS at the most)
+    double *sum_part = nullptr;   // [BAL_CELL_SUMS][POST_BLOCKS]
     double *facet_part = nullptr; // [BAL_FACET_SUMS][FEDM_MAX_TAGS]: a workgroup owns a tag
-    double *max_part = nullptr;   // [1 + BAL_NODAL][BAL_BLOCKS]: the field maximum, then the nodal maxima
+    double *max_part = nullptr;   // [1 + BAL_NODAL][POST_BLOCKS]: the field maximum, then the nodal maxima
     int *idx_part = nullptr;      // the same shape: where each maximum sits
-    int *flag_part = nullptr;     // [2][BAL_BLOCKS] + [FEDM_MAX_TAGS] not-finite flags of the cell, the vertex and the facet pass
+    int *flag_part = nullptr;     // [2][POST_BLOCKS] + [FEDM_MAX_TAGS] not-finite flags of the cell, the vertex and the facet pass
     BalResult *result = nullptr;
 };
 
@@ -71,6 +69,27 @@ __device__ __forceinline__ void bal_cell_init(BalCell &c, bool axisymmetric) {
     c.G[1][1] = (c.x[0][0] - c.x[2][0]) / det;
     c.G[2][0] = (c.x[0][1] - c.x[1][1]) / det;
     c.G[2][1] = (c.x[1][0] - c.x[0][0]) / det;
+}
+
+// the cell's vertices, coordinates and unknowns, then bal_cell_init; true: an unknown is not finite
+template <int NEQ>
+__device__ __forceinline__ bool bal_load_cell(int cell, const fedm_gd_desc *__restrict__ md,
+                                              const double *__restrict__ coords, const int *__restrict__ cells,
+                                              const double *__restrict__ u, BalCell &c, double U[3][NEQ]) {
+    bool bad = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        c.v[a] = cells[3 * (size_t)cell + a];
+        c.x[a][0] = coords[2 * (size_t)c.v[a]];
+        c.x[a][1] = coords[2 * (size_t)c.v[a] + 1];
+#pragma unroll
+        for (int e = 0; e < NEQ; ++e) {
+            U[a][e] = u[(size_t)c.v[a] * NEQ + e];
+            bad |= !isfinite(U[a][e]);
+        }
+    }
+    bal_cell_init(c, md->axisymmetric != 0);
+    return bad;
 }
 
 __device__ __forceinline__ BalSG bal_sg(double a0, double a1, double a2, const BalCell &c, const double phi[3]) {

@@ -12,6 +12,7 @@
 
 #include "fields.hpp"
 #include "gd_balance.hpp"
+#include "postproc.hpp"
 #include "solver.hpp"
 
 namespace fedm {
@@ -228,9 +229,9 @@ const char *gd_kind_name(int kind) {
 
 int gd_check_ctx(const Ctx &c, const char *who) {
     if (c.model_kind != 1)
-        return fields_refuse(who, "an LFA context (these are the LMEA family's fields; fedm_fields has the LFA family's)");
-    if (c.n_owned != c.nv) return fields_refuse(who, "a context with ghost vertices (one GPU only)");
-    if (c.neq < 3 || c.neq > 6) return fields_refuse(who, std::to_string(c.neq) + " equations: 3 to 6 are built");
+        return refuse(who, "an LFA context (these are the LMEA family's fields; fedm_fields has the LFA family's)");
+    if (c.n_owned != c.nv) return refuse(who, "a context with ghost vertices (one GPU only)");
+    if (c.neq < 3 || c.neq > 6) return refuse(who, std::to_string(c.neq) + " equations: 3 to 6 are built");
     return 0;
 }
 
@@ -249,7 +250,7 @@ extern "C" {
 
 int fedm_gd_fields_setup(fedm_ctx *h, const fedm_csr *mass) {
     const char *who = "fedm_gd_fields_setup";
-    if (!h) return fields_refuse(who, "null context");
+    if (!h) return refuse(who, "null context");
     Ctx &c = h->c;
     if (const int rc = gd_check_ctx(c, who)) return rc;
     return fields_setup_shared(c, mass, who);
@@ -257,7 +258,7 @@ int fedm_gd_fields_setup(fedm_ctx *h, const fedm_csr *mass) {
 
 int fedm_gd_probe_setup(fedm_ctx *h, int n_points, const int32_t *vertices, const double *weights) {
     const char *who = "fedm_gd_probe_setup";
-    if (!h) return fields_refuse(who, "null context");
+    if (!h) return refuse(who, "null context");
     Ctx &c = h->c;
     if (const int rc = gd_check_ctx(c, who)) return rc;
     return fields_probe_setup_shared(c, n_points, vertices, weights, who, "fedm_gd_fields_setup");
@@ -266,7 +267,7 @@ int fedm_gd_probe_setup(fedm_ctx *h, int n_points, const int32_t *vertices, cons
 int fedm_gd_fields(fedm_ctx *h, const fedm_field_opts *opts, int n_req, const fedm_field_req *req, double *nodal,
                    double *probes, int32_t *finite, int32_t *cg_iterations) {
     const char *who = "fedm_gd_fields";
-    if (!h || !opts || !req || !finite) return fields_refuse(who, "null argument");
+    if (!h || !opts || !req || !finite) return refuse(who, "null argument");
     Ctx &c = h->c;
     if (const int rc = gd_check_ctx(c, who)) return rc;
     if (const int rc = fields_check_opts(c, *opts, n_req, who, "fedm_gd_fields_setup")) return rc;
@@ -296,14 +297,14 @@ int fedm_gd_fields(fedm_ctx *h, const fedm_field_opts *opts, int n_req, const fe
             case FEDM_GD_FIELD_JOULE:
             case FEDM_GD_FIELD_CURRENT_R:
             case FEDM_GD_FIELD_CURRENT_Z: break;
-            default: return fields_refuse(who, r + "unknown kind " + std::to_string(kind));
+            default: return refuse(who, r + "unknown kind " + std::to_string(kind));
         }
         if (idx < first || idx >= limit)
-            return fields_refuse(who, r + "index " + std::to_string(idx) + " out of range (" + std::to_string(first) + " to " +
-                                          std::to_string(limit - 1) + ")");
+            return refuse(who, r + "index " + std::to_string(idx) + " out of range (" + std::to_string(first) + " to " +
+                                   std::to_string(limit - 1) + ")");
         if (gd_of_the_step(kind) && opts->num != opts->den)
-            return fields_refuse(who, r + gd_kind_name(kind) + " is what the residual of the current step evaluates (u_new, the "
-                                          "field table as it stands): no blend, num == den only");
+            return refuse(who, r + gd_kind_name(kind) + " is what the residual of the current step evaluates (u_new, the "
+                                   "field table as it stands): no blend, num == den only");
         vq.kind[k] = kind;
         vq.index[k] = idx;
         vq.slot[k] = -1;
@@ -323,12 +324,8 @@ int fedm_gd_fields(fedm_ctx *h, const fedm_field_opts *opts, int n_req, const fe
     Fields &f = *c.fields;
     return fields_run(c, *opts, n_req, vq.slot, cq.n > 0,
                       [&](const double *u, int raw_sums, double *dst) {
-                          if (cq.n > 0) switch (c.neq) {   // (what launch_assemble_gd instantiates)
-                                  case 3: launch_gd_cells<3>(c, u, cq); break;
-                                  case 4: launch_gd_cells<4>(c, u, cq); break;
-                                  case 5: launch_gd_cells<5>(c, u, cq); break;
-                                  default: launch_gd_cells<6>(c, u, cq); break;
-                              }
+                          // (gd_check_ctx has refused the equation counts that are not built)
+                          if (cq.n > 0) with_gd_neq(c, [&](auto neq) { launch_gd_cells<decltype(neq)::value>(c, u, cq); });
                           hipLaunchKernelGGL(gd_fields_vertex_kernel, dim3((c.nvp + FIELDS_THREADS - 1) / FIELDS_THREADS, vq.n),
                                              dim3(FIELDS_THREADS), 0, c.stream, c.nv, c.nvp, c.nc, ns, c.d_gd, c.d_gd_fields, u,
                                              f.v_ptr, f.v_idx, f.m, f.cell_b, vq, raw_sums, dst, f.flag);

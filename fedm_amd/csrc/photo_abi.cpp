@@ -3,7 +3,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "photo.hpp"
+#include "postproc.hpp"
 #include "solver.hpp"
 
 namespace fedm {
@@ -18,8 +18,8 @@ void photo_release(Ctx &c) {
             delete ph->M[m];
         }
     }
-    void *ptrs[] = {ph->y, ph->g, ph->cell_g, ph->v_ptr, ph->v_idx, ph->zero, ph->r, ph->z, ph->p, ph->q,
-                    ph->partials, ph->red};
+    photo_cg_free(*ph);
+    void *ptrs[] = {ph->y, ph->g, ph->cell_g, ph->v_ptr, ph->v_idx, ph->zero};
     for (void *p : ptrs)
         if (p) hipFree(p);
     delete ph;
@@ -28,53 +28,42 @@ void photo_release(Ctx &c) {
 
 namespace {
 
-int refuse(const std::string &why) {
-    set_error("fedm_photo_setup: " + why);
-    return -2;
-}
-
 // 0, or -2 with the message set: nothing has been allocated
 int check_desc(const Ctx &c, const fedm_photo_desc &d) {
-    if (c.model_kind != 0) return refuse("the LMEA family has no photoionisation source (LFA models only)");
+    const char *who = "fedm_photo_setup";
+    if (c.model_kind != 0) return refuse(who, "the LMEA family has no photoionisation source (LFA models only)");
     if (c.comm || c.n_owned != c.nv)
-        return refuse("photoionisation runs on one GPU (this context has a transport or ghost vertices)");
+        return refuse(who, "photoionisation runs on one GPU (this context has a transport or ghost vertices)");
     if (d.n_terms < 1 || d.n_terms > PHOTO_MAX_TERMS)
-        return refuse(std::to_string(d.n_terms) + " Helmholtz terms, 1 to " + std::to_string(PHOTO_MAX_TERMS) + " are possible");
+        return refuse(who, std::to_string(d.n_terms) + " Helmholtz terms, 1 to " + std::to_string(PHOTO_MAX_TERMS) + " are possible");
     for (int m = 0; m < d.n_terms; ++m) {
         if (!(d.kappa[m] > 0.0) || !std::isfinite(d.kappa[m]))
-            return refuse("kappa[" + std::to_string(m) + "] must be positive and finite");
-        if (!std::isfinite(d.c[m])) return refuse("c[" + std::to_string(m) + "] is not finite");
+            return refuse(who, "kappa[" + std::to_string(m) + "] must be positive and finite");
+        if (!std::isfinite(d.c[m])) return refuse(who, "c[" + std::to_string(m) + "] is not finite");
     }
-    if (!std::isfinite(d.efficiency)) return refuse("the efficiency is not finite");
+    if (!std::isfinite(d.efficiency)) return refuse(who, "the efficiency is not finite");
     if (d.n_src < 1 || d.n_src > FEDM_MAX_REACTIONS)
-        return refuse(std::to_string(d.n_src) + " source reactions, 1 to " + std::to_string(FEDM_MAX_REACTIONS) + " are possible");
+        return refuse(who, std::to_string(d.n_src) + " source reactions, 1 to " + std::to_string(FEDM_MAX_REACTIONS) + " are possible");
     for (int k = 0; k < d.n_src; ++k)
         if (d.src_reaction[k] < 0 || d.src_reaction[k] >= c.model.n_reactions)
-            return refuse("source reaction index " + std::to_string(d.src_reaction[k]) + " out of range (the model has " +
-                          std::to_string(c.model.n_reactions) + " reactions)");
-    if (d.target_species_mask == 0) return refuse("no target species");
-    if (d.target_species_mask >> c.ns) return refuse("a target species beyond the model's " + std::to_string(c.ns));
+            return refuse(who, "source reaction index " + std::to_string(d.src_reaction[k]) + " out of range (the model has " +
+                               std::to_string(c.model.n_reactions) + " reactions)");
+    if (d.target_species_mask == 0) return refuse(who, "no target species");
+    if (d.target_species_mask >> c.ns) return refuse(who, "a target species beyond the model's " + std::to_string(c.ns));
     for (int s = 0; s < c.ns; ++s) {
         if (!((d.target_species_mask >> s) & 1u)) continue;
         if (c.model.ext_nodes[s] != 3 || !c.d_ext[s])
-            return refuse("target species " + std::to_string(s) + " has no degree-1 source table (ext_nodes = 3)");
+            return refuse(who, "target species " + std::to_string(s) + " has no degree-1 source table (ext_nodes = 3)");
         if (c.expr_n_ops[s] != 0)
-            return refuse("target species " + std::to_string(s) + " has an Expression program: one source table cannot hold both");
+            return refuse(who, "target species " + std::to_string(s) + " has an Expression program: one source table cannot hold both");
     }
     if (c.model.n_tags < 32 && (d.zero_tag_mask >> c.model.n_tags))
-        return refuse("a zero tag beyond the model's " + std::to_string(c.model.n_tags) + " boundary tags");
-    return 0;
-}
-
-template <class T>
-int device_array(T *&dst, const T *src, size_t n) {
-    FEDM_HIP_CHECK(hipMalloc((void **)&dst, sizeof(T) * std::max<size_t>(n, 1)));
-    if (src) FEDM_HIP_CHECK(hipMemcpy(dst, src, sizeof(T) * n, hipMemcpyHostToDevice));
-    else FEDM_HIP_CHECK(hipMemset(dst, 0, sizeof(T) * std::max<size_t>(n, 1)));
+        return refuse(who, "a zero tag beyond the model's " + std::to_string(c.model.n_tags) + " boundary tags");
     return 0;
 }
 
 int setup_impl(Ctx &c, const fedm_photo_desc &d, const fedm_photo_hierarchy *terms) {
+    const char *who = "fedm_photo_setup";
     Photo &ph = *c.photo;
     ph.desc = d;
     // the mesh as the context holds it: vertex -> (cell, corner) in ascending order, and the zero vertices
@@ -102,27 +91,24 @@ int setup_impl(Ctx &c, const fedm_photo_desc &d, const fedm_photo_hierarchy *ter
         return -1;
     const size_t nvp = (size_t)c.nvp;
     if (device_array<double>(ph.y, nullptr, nvp * d.n_terms) || device_array<double>(ph.g, nullptr, nvp) ||
-        device_array<double>(ph.cell_g, nullptr, (size_t)3 * c.nc) || device_array<double>(ph.r, nullptr, nvp) ||
-        device_array<double>(ph.z, nullptr, nvp) || device_array<double>(ph.p, nullptr, nvp) ||
-        device_array<double>(ph.q, nullptr, nvp) ||
-        device_array<double>(ph.partials, nullptr, (size_t)2 * PHOTO_RED_BLOCKS) || device_array<double>(ph.red, nullptr, 4))
+        device_array<double>(ph.cell_g, nullptr, (size_t)3 * c.nc) || photo_cg_alloc(ph, nvp))
         return -1;
     for (int m = 0; m < d.n_terms; ++m) {
         const fedm_photo_hierarchy &t = terms[m];
         const std::string term = "term " + std::to_string(m);
         if (t.n_levels < 1 || !t.A || (t.n_levels > 1 && (!t.P || !t.R || !t.coarse_inverse || t.nu < 1)))
-            return refuse(term + ": bad hierarchy (levels with their prolongators, restrictions and a dense coarsest "
-                                 "inverse; V(nu,nu) with nu >= 1)");
+            return refuse(who, term + ": bad hierarchy (levels with their prolongators, restrictions and a dense coarsest "
+                                      "inverse; V(nu,nu) with nu >= 1)");
         if (t.A[0].n_rows != c.nv || t.A[0].n_cols != c.nv)
-            return refuse(term + ": the operator has " + std::to_string(t.A[0].n_rows) + " rows, the mesh " +
-                          std::to_string(c.nv) + " vertices");
+            return refuse(who, term + ": the operator has " + std::to_string(t.A[0].n_rows) + " rows, the mesh " +
+                               std::to_string(c.nv) + " vertices");
         // the zero vertices' rows must be unit rows: y stays 0 there through every sweep and product
         for (int v = 0; v < c.nv; ++v) {
             if (!zero[v]) continue;
             const int64_t b = t.A[0].indptr[v], e = t.A[0].indptr[v + 1];
             for (int64_t k = b; k < e; ++k)
                 if (t.A[0].values[k] != (t.A[0].indices[k] == v ? 1.0 : 0.0))
-                    return refuse(term + ": the row of zero vertex " + std::to_string(v) + " is not a unit row");
+                    return refuse(who, term + ": the row of zero vertex " + std::to_string(v) + " is not a unit row");
         }
         ph.A[m].single = false;
         const int rc = ph.A[m].from_csr(t.A[0], true);
