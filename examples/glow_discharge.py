@@ -21,6 +21,9 @@ whole per-step pipeline on the GPU.
 conduction currents into the two electrodes, Joule power, collision loss, the imbalances of the energy and particle
 balances and the Shockley-Ramo current with psi = z / gap, all formed on the device without downloading the state (an
 extension: `fedm.Discharge_balance`); off by default.
+`--ballast OHMS [--stray-capacitance F] [--circuit-log FILE]` runs the powered electrode behind a series resistor with a
+stray capacitance to ground, closed on the device (an extension: `fedm.External_circuit`), and writes t, the source's
+voltage, the electrode's potential, the lead current, e cond and e G per accepted step; off by default.
 `--currents FILE` writes t and the conduction, displacement and total current of the powered and of the grounded
 electrode per accepted step (every N-th with `--currents-every N`): the Shockley-Ramo currents with weighting potentials
 solved for on the device, the displacement part that of the rising voltage (an extension: `fedm.Electrode_currents`);
@@ -261,9 +264,12 @@ def currents_row(t, c):
     return [t] + [x for g in range(len(c.conduction)) for x in (c.conduction[g], c.displacement[g], c.total[g])]
 
 
+CIRCUIT_COLUMNS = ("t", "V_s", "U", "lead_current", "conduction", "conductance")
+
+
 def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", quiet=True, ttol=2e-3,
          stop_before_device=None, balance=None, balance_every=1, fields=None, fields_every=1, axis_profile=None,
-         currents=None, currents_every=1):
+         currents=None, currents_every=1, ballast=None, stray_capacitance=0.0, circuit_log=None):
     fem.parameters["form_compiler"]["quadrature_degree"] = 4
     deck = read_deck(input_dir)
     file_io.files.output_folder_path = Path(output_dir)
@@ -323,6 +329,17 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
         currents_of = fedm.Electrode_currents(problem, boundary_tags=(1, 2))
         current_rows = open(currents, "w")
         current_rows.write("# " + " ".join(CURRENTS_COLUMNS) + "\n")
+    circuit = circuit_rows = None
+    timed = [voltage]
+    if ballast is not None:
+        # the powered electrode (tag 1) behind the ballast and its stray capacitance, the grounded one (tag 2) ideal
+        electrodes = currents_of or fedm.Electrode_currents(problem, boundary_tags=(1, 2))
+        circuit = fedm.External_circuit(problem, electrodes, [lambda s: VOLTAGE * (1.0 - np.exp(-s / 1e-9)), lambda s: 0.0],
+                                        [float(ballast), 0.0], [float(stray_capacitance), 0.0]).bind(problem)
+        timed = [voltage, circuit]
+        if circuit_log is not None:
+            circuit_rows = open(circuit_log, "w")
+            circuit_rows.write("# " + " ".join(CIRCUIT_COLUMNS) + "\n")
     field_out = field_files = profile = profile_rows = None
     if fields:
         fields = [name.strip() for name in (fields.split(",") if isinstance(fields, str) else fields) if name.strip()]
@@ -354,8 +371,13 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
         with contextlib.redirect_stdout(io.StringIO() if quiet else sys.stdout):
             t = fedm.adaptive_solver(newton, problem, t, dt, dt_before, dis.now, dis.before, parts_now, parts_before,
                                      dis.split, step_errors, file_io.files.error_file, recent_errors, ttol,
-                                     dt_limits["dt_min"], time_dependent_arguments=[voltage], approximation="LMEA")
+                                     dt_limits["dt_min"], time_dependent_arguments=timed, approximation="LMEA")
         file_io.log("time", file_io.files.model_log, t)
+        if circuit is not None:     # the accepted step: the history moves on, conduction and conductance of the new state
+            circuit.accept()
+            if circuit_rows is not None:
+                circuit_rows.write(" ".join(repr(v) for v in circuit.log_row(t, 0)) + "\n")
+                circuit_rows.flush()
         if balance_of is not None and steps % max(1, int(balance_every)) == 0:
             # (here, before anything of the next step reaches the device: the balance of the residual just solved)
             rows.write(" ".join(repr(float(v)) for v in balance_row(t, balance_of())) + "\n")
@@ -390,6 +412,8 @@ def main(nx=100, ny=100, T_final=1e-11, input_dir=None, output_dir="gd_output", 
         profile_rows.close()
     if current_rows is not None:
         current_rows.close()
+    if circuit_rows is not None:
+        circuit_rows.close()
     return dict(t=t, steps=steps, output=str(file_io.files.output_folder_path), species=deck["file_names"],
                 error_file=str(file_io.files.error_file), problem=problem)
 
@@ -402,6 +426,11 @@ if __name__ == "__main__":
     ap.add_argument("--currents", metavar="FILE",
                     help="write t and the conduction, displacement and total current of both electrodes per accepted step")
     ap.add_argument("--currents-every", type=int, default=1, metavar="N", help="... every N-th accepted step")
+    ap.add_argument("--ballast", type=float, metavar="OHMS",
+                    help="run the powered electrode behind a series resistor (fedm.External_circuit); off by default")
+    ap.add_argument("--stray-capacitance", type=float, default=0.0, metavar="F", help="... with this capacitance to ground in parallel")
+    ap.add_argument("--circuit-log", metavar="FILE",
+                    help="... and write %s of the powered electrode per accepted step" % ", ".join(CIRCUIT_COLUMNS))
     ap.add_argument("--fields", metavar="LIST",
                     help="comma-separated derived fields written at the output times: mean_energy, reduced_field, E_norm, "
                          "E_r, E_z, charge, density:s, state:e, table:f, rate:j, source:s, collision_loss, joule, "
@@ -411,5 +440,6 @@ if __name__ == "__main__":
     a = ap.parse_args()
     result = main(output_dir=a.out, quiet=False, balance=a.balance, balance_every=a.balance_every, fields=a.fields,
                   fields_every=a.fields_every, axis_profile=a.axis_profile, currents=a.currents,
-                  currents_every=a.currents_every)
+                  currents_every=a.currents_every, ballast=a.ballast, stray_capacitance=a.stray_capacitance,
+                  circuit_log=a.circuit_log)
     print({k: v for k, v in result.items() if k != "problem"})

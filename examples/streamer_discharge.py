@@ -21,6 +21,9 @@ E/N tables (an extension: `fedm.Coefficient_table`, looked up in the element ker
 `--diagnostics FILE` writes one row per accepted step (every N-th with `--diagnostics-every N`): head position, field
 maximum in the channel, particle numbers, net charge, electrode charges and the induced current, computed on the
 device without downloading the state (an extension: `fedm.Discharge_diagnostics`); off by default.
+`--ballast OHMS [--stray-capacitance F] [--circuit-log FILE]` runs the anode behind a series resistor with a stray
+capacitance to ground, closed on the device (an extension: `fedm.External_circuit`), and writes t, the source's voltage,
+the anode's potential, the lead current, e cond and e G per accepted step; off by default.
 `--currents FILE` writes t and the conduction, displacement and total current of the cathode and of the anode per
 accepted step (every N-th with `--currents-every N`), with weighting potentials solved for on the device (an extension:
 `fedm.Electrode_currents`); off by default.
@@ -243,10 +246,13 @@ def currents_row(t, c):
     return [t] + [x for g in range(len(c.conduction)) for x in (c.conduction[g], c.displacement[g], c.total[g])]
 
 
+CIRCUIT_COLUMNS = ("t", "V_s", "U", "lead_current", "conduction", "conductance")
+
+
 def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_dir=None, output_dir=None,
          quiet=False, stop_before_device=None, coupling="coupled", model="benchmark_model", photoionization=False,
          diagnostics=None, diagnostics_every=1, fields=None, fields_every=1, axis_profile=None, currents=None,
-         currents_every=1):
+         currents_every=1, ballast=None, stray_capacitance=0.0, circuit_log=None):
     """Runs the case; returns (state as (n_vertices, 3) array of ln n_i, ln n_e, Phi; error-log path).
     `model`: the deck folder under the input directory ("benchmark_model", "tabulated_model").
     `photoionization`: add the Helmholtz photoionisation source (coupled step only).
@@ -255,7 +261,10 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
     times (every `fields_every`-th of them).  `axis_profile`: a file that receives, per accepted step, t followed by
     E_z and then n_e at the AXIS_POINTS points of the axis (the first row holds their z).  `currents`: a file that
     receives, per accepted step (every `currents_every`-th), t and then conduction, displacement and total current [A] of
-    the cathode and of the anode (fedm.Electrode_currents, their weighting potentials solved for on the device)."""
+    the cathode and of the anode (fedm.Electrode_currents, their weighting potentials solved for on the device).
+    `ballast`: a series resistance [ohm] between the source and the anode, with `stray_capacitance` [F] to ground in
+    parallel (fedm.External_circuit; the cathode stays an ideal ground); `circuit_log`: a file that receives
+    CIRCUIT_COLUMNS of the anode per accepted step."""
     case = Case(deck=model) if end_time is None else Case(deck=model, end_time=end_time)
     fem.parameters["form_compiler"]["quadrature_degree"] = 2
     deck = read_deck(case, input_dir)
@@ -303,6 +312,18 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
         currents_of = fedm.Electrode_currents(problem, boundary_tags=(1, 2))
         current_rows = open(currents, "w")
         current_rows.write("# " + " ".join(CURRENTS_COLUMNS) + "\n")
+    circuit = circuit_rows = None
+    timed = []
+    if ballast is not None:
+        # the anode (tag 2) behind the resistor, starting at the source's voltage; the cathode (tag 1) an ideal ground
+        electrodes = currents_of or fedm.Electrode_currents(problem, boundary_tags=(1, 2))
+        circuit = fedm.External_circuit(problem, electrodes, [lambda s: 0.0, lambda s: case.anode_voltage],
+                                        [0.0, float(ballast)], [0.0, float(stray_capacitance)],
+                                        [0.0, case.anode_voltage]).bind(problem)
+        timed = [circuit]
+        if circuit_log is not None:
+            circuit_rows = open(circuit_log, "w")
+            circuit_rows.write("# " + " ".join(CIRCUIT_COLUMNS) + "\n")
     field_out = field_files = profile = profile_rows = None
     if fields:
         fields = [name.strip() for name in (fields.split(",") if isinstance(fields, str) else fields) if name.strip()]
@@ -342,8 +363,13 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
             t = fedm.adaptive_solver(newton, problem, t, dt, dt_before, fl.now, fl.before, list(fl.parts_now),
                                      list(fl.parts_before), fl.split, step_errors, file_io.files.error_file,
                                      recent_errors, case.step_tolerance, case.shortest_step,
-                                     time_dependent_arguments=[], approximation="LFA")
+                                     time_dependent_arguments=timed, approximation="LFA")
         file_io.log("time", file_io.files.model_log, t)
+        if circuit is not None:     # the accepted step: the history moves on, conduction and conductance of the new state
+            circuit.accept()
+            if circuit_rows is not None:
+                circuit_rows.write(" ".join(f"{x:.17g}" for x in circuit.log_row(t, 1)) + "\n")
+                circuit_rows.flush()
         dt_before.time_step = dt.time_step
         dt.time_step = fedm.adaptive_timestep(dt.time_step, recent_errors, case.step_tolerance, case.shortest_step,
                                               case.longest_step)
@@ -380,6 +406,8 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
         profile_rows.close()
     if current_rows is not None:
         current_rows.close()
+    if circuit_rows is not None:
+        circuit_rows.close()
     return problem.device.get_state(), file_io.files.error_file
 
 
@@ -407,13 +435,19 @@ if __name__ == "__main__":
     ap.add_argument("--currents", metavar="FILE",
                     help="write t and the conduction, displacement and total current of cathode and anode per accepted step")
     ap.add_argument("--currents-every", type=int, default=1, metavar="N", help="... every N-th accepted step")
+    ap.add_argument("--ballast", type=float, metavar="OHMS",
+                    help="run the anode behind a series resistor (fedm.External_circuit); off by default")
+    ap.add_argument("--stray-capacitance", type=float, default=0.0, metavar="F", help="... with this capacitance to ground in parallel")
+    ap.add_argument("--circuit-log", metavar="FILE",
+                    help="... and write %s of the anode per accepted step" % ", ".join(CIRCUIT_COLUMNS))
     ap.add_argument("--save-state", metavar="FILE", help="write the final state (n_vertices, 3) as a .npy file")
     a = ap.parse_args()
     state, log_path = main(cells=a.cells, mesh_spacing=a.mesh_spacing, mesh_file=a.mesh, end_time=a.end,
                            output_dir=a.out, coupling=a.coupling, model=a.model, photoionization=a.photoionization,
                            diagnostics=a.diagnostics, diagnostics_every=a.diagnostics_every, fields=a.fields,
                            fields_every=a.fields_every, axis_profile=a.axis_profile, currents=a.currents,
-                           currents_every=a.currents_every)
+                           currents_every=a.currents_every, ballast=a.ballast, stray_capacitance=a.stray_capacitance,
+                           circuit_log=a.circuit_log)
     if a.save_state:
         import numpy
         numpy.save(a.save_state, state)

@@ -176,6 +176,21 @@ class CurrentsOut(C.Structure):
                 ("n_psi", C.c_int32), ("finite", C.c_int32)]
 
 
+class CircuitDesc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad_", C.c_int32), ("R", C.c_double * CURRENTS_MAX), ("Cp", C.c_double * CURRENTS_MAX),
+                ("U0", C.c_double * CURRENTS_MAX), ("electrode_of_entry", C.POINTER(C.c_int8))]
+
+
+CIRCUIT_FLAGS = {1: "not finite", 2: "singular", 4: "bad result"}      # include/fedm_hip.h, FEDM_CIRCUIT_*
+
+
+class CircuitState(C.Structure):
+    _fields_ = [("U", C.c_double * CURRENTS_MAX), ("U_old", C.c_double * CURRENTS_MAX),
+                ("U_old1", C.c_double * CURRENTS_MAX), ("dUdt", C.c_double * CURRENTS_MAX),
+                ("lead_current", C.c_double * CURRENTS_MAX), ("conduction", C.c_double * CURRENTS_MAX),
+                ("conductance", (C.c_double * CURRENTS_MAX) * CURRENTS_MAX), ("n", C.c_int32), ("flag", C.c_int32)]
+
+
 FIELDS_MAX_REQ = 8
 
 
@@ -267,6 +282,10 @@ _SIGNATURES = {
     "fedm_currents_solve": (C.c_int, [_P, C.POINTER(PhotoHierarchy), _D, C.c_double, C.c_int, C.POINTER(C.c_int)]),
     "fedm_currents_get_psi": (C.c_int, [_P, _D]),
     "fedm_currents": (C.c_int, [_P, C.POINTER(CurrentsOut)]),
+    "fedm_circuit_setup": (C.c_int, [_P, C.POINTER(CircuitDesc)]),
+    "fedm_circuit_measure": (C.c_int, [_P]),
+    "fedm_circuit_advance": (C.c_int, [_P, _D, C.POINTER(CircuitState)]),
+    "fedm_circuit_get": (C.c_int, [_P, C.POINTER(CircuitState)]),
     "fedm_fields_setup": (C.c_int, [_P, C.POINTER(Csr)]),
     "fedm_probe_setup": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), _D]),
     "fedm_fields": (C.c_int, [_P, C.POINTER(FieldOpts), C.c_int, C.POINTER(FieldReq), _D, _D, C.POINTER(C.c_int32),

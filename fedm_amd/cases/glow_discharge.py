@@ -31,7 +31,7 @@ class Case:
     def __init__(self, nx=100, ny=100, file_input=DECK, device=0, T_final=1e-11,
                  relative_tolerance=1e-4, maximum_iterations=20, quiet=True, error_file=None,
                  device_pipeline=True, mesh=None, energy_loss=None, energy_Ei=0.0, quadrature_degree=4,
-                 keep_balance=False, keep_currents=False):
+                 keep_balance=False, keep_currents=False, circuit=None):
         import tempfile
         self.quiet = quiet
         model = "4_particles"
@@ -146,6 +146,19 @@ class Case:
         self.keep_balance, self.last_balance = keep_balance, None
         # keep_currents: every step leaves the electrode currents of the residual it solved in last_currents
         self.keep_currents, self.last_currents = keep_currents, None
+        # circuit: dict(resistance=ohms, capacitance=farads) -- the powered electrode behind a series resistor with a
+        # stray capacitance to ground (fedm.External_circuit; the grounded electrode stays an ideal ground), advanced
+        # before every solve attempt in place of the prescribed voltage; None: the voltage source alone, as ever
+        self.circuit = None
+        if circuit is not None:
+            self.currents()         # (sets the electrodes up)
+            self.circuit = ff.External_circuit(self.prob, self._currents,
+                                               [lambda t: self.U_w * (1.0 - np.exp(-t / 1e-9)), lambda t: 0.0],
+                                               [float(circuit["resistance"]), 0.0],
+                                               [float(circuit.get("capacitance", 0.0)), 0.0]).bind(self.problem)
+            self._timed = [self.Phi_powered, self.circuit]
+        else:
+            self._timed = [self.Phi_powered]
 
     def dirichlet_values(self, t):
         return np.concatenate([np.full(self.powered.size, self.U_w * (1.0 - np.exp(-t / 1e-9))),
@@ -248,9 +261,11 @@ class Case:
             self.t = ff.adaptive_solver(self.solver, self.problem, self.t, self.dt, self.dt_old,
                                         self.u_new, self.u_old, None, None, self.assigner, self.error,
                                         self.error_file, self.max_error, self.ttol, self.dt_min,
-                                        time_dependent_arguments=[self.Phi_powered], approximation="LMEA")
+                                        time_dependent_arguments=self._timed, approximation="LMEA")
         self.newton_iterations += prob.last_report.iterations
         self.linear_iterations += prob.last_report.linear_iterations
+        if self.circuit is not None:
+            self.circuit.accept()
         if self.keep_balance:
             self.last_balance = self.balance()
         if self.keep_currents:
@@ -272,9 +287,11 @@ class Case:
             self.t = ff.adaptive_solver(self.solver, self.problem, self.t, self.dt, self.dt_old,
                                         self.u_new, self.u_old, None, None, self.assigner, self.error,
                                         self.error_file, self.max_error, self.ttol, self.dt_min,
-                                        time_dependent_arguments=[self.Phi_powered], approximation="LMEA")
+                                        time_dependent_arguments=self._timed, approximation="LMEA")
         self.newton_iterations += self.prob.last_report.iterations
         self.linear_iterations += self.prob.last_report.linear_iterations
+        if self.circuit is not None:        # the accepted step: the history moves on, measured with the table of this step
+            self.circuit.accept()
 
     def _step_on_device(self, t_old):
         """Same step with the coefficient refresh and the mean-energy update on the device: no

@@ -221,7 +221,7 @@ class Stepper:
 
     def __init__(self, prob, dt_init=5e-12, dt_max=5e-12, dt_min=1e-15, ttol=1e-3,
                  relative_tolerance=1e-4, maximum_iterations=20, error_file=None, quiet=True,
-                 coupling="coupled"):
+                 coupling="coupled", circuit=None):
         import tempfile
         from .. import functions as ff
         from ..forms import DeviceState, Expression, FunctionAssigner
@@ -244,6 +244,18 @@ class Stepper:
         self.t, self.steps, self.newton_iterations, self.linear_iterations = 0.0, 0, 0, 0
         self.quiet = quiet
         self.total_dofs = prob.n
+        # circuit: dict(resistance=ohms, capacitance=farads) -- the anode behind a series resistor with a stray capacitance
+        # to ground (fedm.External_circuit; the cathode stays an ideal ground), advanced before every solve attempt;
+        # None: the ideal source, as ever.  Set up at the first step, once the initial state stands.
+        self._circuit_spec, self.circuit, self._timed = circuit, None, []
+
+    def _circuit_setup(self):
+        spec = self._circuit_spec
+        self.currents()             # (sets the electrodes up)
+        self.circuit = self.ff.External_circuit(self.prob, self._currents, [lambda t: 0.0, lambda t: U_W],
+                                                [0.0, float(spec["resistance"])],
+                                                [0.0, float(spec.get("capacitance", 0.0))], [0.0, U_W]).bind(self.problem)
+        self._timed = [self.circuit]
 
     def initialise(self):
         return initialise(self.prob)
@@ -251,14 +263,18 @@ class Stepper:
     def step(self):
         import contextlib, io
         ff = self.ff
+        if self._circuit_spec is not None and self.circuit is None:
+            self._circuit_setup()
         self.prob.shift_state()                              # :306-307
         sink = io.StringIO() if self.quiet else None
         with (contextlib.redirect_stdout(sink) if sink else contextlib.nullcontext()):
             self.t = ff.adaptive_solver(self.solver, self.problem, self.t, self.dt, self.dt_old,
                                         self.u_new, self.u_old, None, None, self.assigner,
                                         self.error, self.error_file, self.max_error, self.ttol,
-                                        self.dt_min, time_dependent_arguments=[],
+                                        self.dt_min, time_dependent_arguments=self._timed,
                                         approximation="LFA")
+        if self.circuit is not None:
+            self.circuit.accept()
         self.newton_iterations += self.prob.last_report.iterations
         self.linear_iterations += self.prob.last_report.linear_iterations
         self.dt_old.time_step = self.dt.time_step            # :335

@@ -760,6 +760,7 @@ void fedm_ctx_destroy(fedm_ctx *h) {
     diag_release(c);
     fields_release(c);
     gd_balance_release(c);
+    circuit_release(c);
     currents_release(c);
     fs_tiles_release(c);
     for (auto &e : c.prof.ev) hipEventDestroy(e);

@@ -30,16 +30,6 @@ __device__ __forceinline__ double cur_rate(double un, double uo, double uo1, dou
     return (un * tr2p1 - (trp1 * trp1) * uo + (tr * tr) * uo1) * (1.0 / trp1) * inv_dt;
 }
 
-// sum W grad a . grad b of two P1 functions on a cell: displacement and coupling with grad psi, the capacitance
-__device__ __forceinline__ double cur_grad_dot(double cW, const double a[2], const double b[2]) {
-    return cW * (a[0] * b[0] + a[1] * b[1]);
-}
-
-__device__ __forceinline__ void cur_grad(const double G[3][2], double p0, double p1, double p2, double g[2]) {
-    g[0] = p0 * G[0][0] + p1 * G[1][0] + p2 * G[2][0];
-    g[1] = p0 * G[0][1] + p1 * G[1][1] + p2 * G[2][1];
-}
-
 struct CurCell {
     double cW;              // sum_q W
     double J[2];            // sum_s Z_s sum_q W Gamma_s
@@ -69,16 +59,6 @@ __device__ __forceinline__ double cur_accumulate(double (&acc)[CUR_SUMS], const 
         chk += (cond + disp) + (coup + chg);
     }
     return chk;
-}
-
-template <int K>
-__device__ __forceinline__ void cur_write_partials(const double (&acc)[K], bool bad, double *__restrict__ sum_part,
-                                                   int *__restrict__ flag_part) {
-    __shared__ double lds_sum[K][POST_WAVES];
-    const double s = block_sums(acc, lds_sum);
-    const int any_bad = __syncthreads_or(bad ? 1 : 0);
-    if ((int)threadIdx.x < K) sum_part[(size_t)threadIdx.x * POST_BLOCKS + blockIdx.x] = s;
-    if (threadIdx.x == 0) flag_part[blockIdx.x] = any_bad;
 }
 
 // ---- the cells, LFA ----------------------------------------------------------------------------------
@@ -377,6 +357,30 @@ int form_capacitance(Ctx &c, const double *psi, int n_psi, double cap[CUR_MAX][C
     return 0;
 }
 
+int ensure_solve_buffers(Ctx &c) {
+    Currents &k = *c.currents;
+    if (k.cg) return 0;
+    const size_t nvp = (size_t)c.nvp;
+    k.cg = new Photo();
+    if (device_array<double>(k.psi_new, nullptr, nvp * CUR_MAX) || device_array<double>(k.rhs, nullptr, nvp * CUR_MAX) ||
+        device_array<double>(k.x, nullptr, nvp) || device_array<double>(k.b, nullptr, nvp) ||
+        device_array<unsigned char>(k.fixed, nullptr, nvp) || photo_cg_alloc(*k.cg, nvp)) {
+        // nothing half-made stays behind (photo_cg_alloc has freed its own): the next call starts from nothing again
+        void *ptrs[] = {k.psi_new, k.rhs, k.x, k.b, k.fixed};
+        for (void *p : ptrs)
+            if (p) hipFree(p);
+        k.psi_new = k.rhs = k.x = k.b = nullptr;
+        k.fixed = nullptr;
+        delete k.cg;
+        k.cg = nullptr;
+        return -1;
+    }
+    return 0;
+}
+
+}  // namespace
+
+// (not in the unnamed namespace: fedm_circuit_measure runs the same pass and keeps its sums on the device)
 void launch_currents(Ctx &c) {
     Currents &k = *c.currents;
     const int nb = cur_blocks(c);
@@ -401,29 +405,6 @@ void launch_currents(Ctx &c) {
     }
     hipLaunchKernelGGL(currents_finish_kernel, dim3(1), t, 0, c.stream, nb, CUR_SUMS, k.sum_part, k.flag_part, k.result);
 }
-
-int ensure_solve_buffers(Ctx &c) {
-    Currents &k = *c.currents;
-    if (k.cg) return 0;
-    const size_t nvp = (size_t)c.nvp;
-    k.cg = new Photo();
-    if (device_array<double>(k.psi_new, nullptr, nvp * CUR_MAX) || device_array<double>(k.rhs, nullptr, nvp * CUR_MAX) ||
-        device_array<double>(k.x, nullptr, nvp) || device_array<double>(k.b, nullptr, nvp) ||
-        device_array<unsigned char>(k.fixed, nullptr, nvp) || photo_cg_alloc(*k.cg, nvp)) {
-        // nothing half-made stays behind (photo_cg_alloc has freed its own): the next call starts from nothing again
-        void *ptrs[] = {k.psi_new, k.rhs, k.x, k.b, k.fixed};
-        for (void *p : ptrs)
-            if (p) hipFree(p);
-        k.psi_new = k.rhs = k.x = k.b = nullptr;
-        k.fixed = nullptr;
-        delete k.cg;
-        k.cg = nullptr;
-        return -1;
-    }
-    return 0;
-}
-
-}  // namespace
 }  // namespace fedm
 
 using namespace fedm;

@@ -2,6 +2,7 @@
 // and the C ABI in currents.hip share with the context's teardown.
 #pragma once
 #include "photo.hpp"
+#include "postproc.hpp"
 
 namespace fedm {
 
@@ -31,5 +32,28 @@ struct Currents {
     unsigned char *fixed = nullptr;      // [nvp] 1: a unit row of the operator (a conductor's vertex), and the padding
     Photo *cg = nullptr;          // r, z, p, q, partials, red alone: Ctx::photo points here for the duration of a solve
 };
+
+#ifdef __HIPCC__
+// ---- device: what the cell passes of currents.hip and circuit.hip share ------------------------------
+// sum W grad a . grad b of two P1 functions on a cell: displacement and coupling with grad psi, the capacitance
+__device__ __forceinline__ double cur_grad_dot(double cW, const double a[2], const double b[2]) {
+    return cW * (a[0] * b[0] + a[1] * b[1]);
+}
+
+__device__ __forceinline__ void cur_grad(const double G[3][2], double p0, double p1, double p2, double g[2]) {
+    g[0] = p0 * G[0][0] + p1 * G[1][0] + p2 * G[2][0];
+    g[1] = p0 * G[0][1] + p1 * G[1][1] + p2 * G[2][1];
+}
+
+template <int K>
+__device__ __forceinline__ void cur_write_partials(const double (&acc)[K], bool bad, double *__restrict__ sum_part,
+                                                   int *__restrict__ flag_part) {
+    __shared__ double lds_sum[K][POST_WAVES];
+    const double s = block_sums(acc, lds_sum);
+    const int any_bad = __syncthreads_or(bad ? 1 : 0);
+    if ((int)threadIdx.x < K) sum_part[(size_t)threadIdx.x * POST_BLOCKS + blockIdx.x] = s;
+    if (threadIdx.x == 0) flag_part[blockIdx.x] = any_bad;
+}
+#endif  // __HIPCC__
 
 }  // namespace fedm

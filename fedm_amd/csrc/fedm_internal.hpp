@@ -78,6 +78,7 @@ struct Diag;
 struct Fields;
 struct GdBalance;
 struct Currents;
+struct Circuit;
 
 // Optional in-run kernel timing with HIP events on the library's stream (bench.py roofline).
 // kinds: 0 assembly F+J, 1 Jacobian SpMV, 2 assembly F only, 3 multigrid V-cycle
@@ -318,6 +319,7 @@ struct Ctx {
     Fields *fields = nullptr; // field output: the vertex lists, the lumped mass, the results' buffers (fields.hpp; fedm_fields_setup)
     GdBalance *gd_balance = nullptr;   // LMEA balance: psi, groups, the tags' facet lists and the reductions' buffers (gd_balance.hpp; allocated at first use)
     Currents *currents = nullptr;      // electrode currents: the weighting potentials, the capacitance and the reductions' buffers (currents.hpp; fedm_currents_setup)
+    Circuit *circuit = nullptr;        // external circuit of the driven electrodes: the potentials' history, the conductance and the Dirichlet map (circuit.hpp; fedm_circuit_setup)
 };
 
 // Indices of Ctx::path_stats, in the order fedm_solver_path_stats documents (include/fedm_hip.h)
@@ -443,6 +445,10 @@ void fields_release(Ctx &c);
 void gd_balance_release(Ctx &c);
 // ---- currents.hip (currents.hpp has the rest) -------------------------------------------------
 void currents_release(Ctx &c);
+// the cell pass and its finish on the context's stream: the sums stay in Currents::result (no read-back)
+void launch_currents(Ctx &c);
+// ---- circuit.hip (circuit.hpp has the rest) ---------------------------------------------------
+void circuit_release(Ctx &c);
 // ---- spmv.hip -------------------------------------------------------------------------------
 void launch_block_inverse(Ctx &c);                              // d_dinv from diagonal blocks
 void launch_row_scale(Ctx &c, double *d2, double *d_out);       // d^2 (and d, unless null) of the rows' equilibration

@@ -394,6 +394,27 @@ class Currents:
 
 
 @dataclass
+class CircuitState:
+    """What the device holds of the external circuit (``fedm_circuit_get`` / ``fedm_circuit_advance``,
+    include/fedm_hip.h has the scheme), in SI units: entry ``g`` belongs to electrode ``g``.  Axisymmetric: volts, amperes,
+    siemens; planar: per metre of depth.  ``raw`` keeps the library's own ``conduction`` [1/s] and ``conductance``
+    [1/(V s)]."""
+    U: np.ndarray                     # the last advance's U^{n+1} (before the first: the initial potentials)  [V]
+    U_old: np.ndarray                 # U^n
+    U_old1: np.ndarray                # U^{n-1}
+    dUdt: np.ndarray                  # the BDF2 quotient of the last advance  [V/s]
+    lead_current: np.ndarray          # (V - U)/R of the last advance; an ideal source's linearised current  [A]
+    conduction: np.ndarray            # e cond_g of the last measure  [A]
+    conductance: np.ndarray           # e G_gh of the last measure  [S]
+    flag: int                         # 0, or FEDM_CIRCUIT_* bits: U was left as it was
+    raw: dict = field(default_factory=dict)
+
+    @property
+    def finite(self):
+        return self.flag == 0
+
+
+@dataclass
 class FieldValues:
     """One call of :meth:`DeviceProblem.fields` (``fedm_fields``): ``nodal[k]`` the nodal values of request ``k`` in the
     caller's vertex order (None with ``nodal=False``), ``probes[k]`` its values at the probe points (None without
@@ -1150,6 +1171,77 @@ class DeviceProblem:
         return Currents(conduction=elementary_charge * raw["conduction"], displacement=epsilon_0 * raw["displacement"],
                         induced_charge=elementary_charge * raw["induced_charge"], coupling=raw["coupling"].copy(),
                         capacitance=epsilon_0 * raw["capacitance"], finite=bool(out.finite), raw=raw)
+
+    # -- external circuit (csrc/circuit.hip) ----------------------------------------------
+    def circuit_setup(self, resistance, capacitance=0.0, initial=0.0, electrode_of_entry=None, boundary_tags=None):
+        """What :meth:`circuit_measure` and :meth:`circuit_advance` need once (``fedm_circuit_setup``), after
+        :meth:`currents_setup`: per electrode of that set-up a series ``resistance`` [ohm] (0: an ideal source), a stray
+        ``capacitance`` to ground [F] and the ``initial`` potential [V] -- scalars or one value each.  The Dirichlet
+        entries that get an electrode's potential: ``electrode_of_entry``, ``int8`` per entry of ``dirichlet_dofs`` in
+        the order :meth:`set_dirichlet_values` takes (-1: left alone); or ``boundary_tags``: electrode ``g`` is the
+        potential's Dirichlet entries on the vertices of the facets tagged ``boundary_tags[g]``
+        (:func:`boundary_vertex_groups`, as :meth:`currents_setup` groups them).  Replaces an earlier set-up."""
+        n = int(getattr(self, "_currents_n", 0))
+        if n == 0:
+            raise RuntimeError("circuit_setup: currents_setup has not been called")
+        if (electrode_of_entry is None) == (boundary_tags is None):
+            raise ValueError("circuit_setup: give either electrode_of_entry or boundary_tags")
+        d = _lib.CircuitDesc()
+        for name, val in (("R", resistance), ("Cp", capacitance), ("U0", initial)):
+            v = np.broadcast_to(np.asarray(val, dtype=np.float64), (n,)) if np.ndim(val) == 0 else np.asarray(val, dtype=np.float64)
+            if v.shape != (n,):
+                raise ValueError(f"circuit_setup: {n} electrodes, got {v.shape} values")
+            for g in range(n):
+                getattr(d, name)[g] = float(v[g])
+        if boundary_tags is not None:
+            tags = [int(t) for t in boundary_tags]
+            if len(tags) != n:
+                raise ValueError(f"circuit_setup: {n} electrodes, got {len(tags)} boundary tags")
+            group = boundary_vertex_groups(self.cells, self.facet_tags(), self.nv, self.dirichlet_vertices(), tags)
+            dd = self._ddofs.astype(np.int64)
+            entry = np.where(dd % self.n_eq == self.n_eq - 1, group[self._order[dd // self.n_eq]].astype(np.int64) - 1, -1)
+        else:
+            entry = np.asarray(electrode_of_entry).reshape(-1)
+            if entry.size != self._ddofs.size:
+                raise ValueError(f"circuit_setup: {self._ddofs.size} Dirichlet entries, got {entry.size}")
+        entry = np.ascontiguousarray(entry, dtype=np.int8)
+        d.n = n
+        d.electrode_of_entry = entry.ctypes.data_as(C.POINTER(C.c_int8))
+        self._check(self.lib.fedm_circuit_setup(self._h, C.byref(d)), "fedm_circuit_setup")
+        self.circuit_entries = entry
+
+    def circuit_measure(self):
+        """After an accepted step (and once before the first): the history of the electrodes' potentials moves on and the
+        conduction and the conductance of ``u_new`` are formed, all on the device (``fedm_circuit_measure``)."""
+        self._check(self.lib.fedm_circuit_measure(self._h), "fedm_circuit_measure")
+
+    def _circuit_state(self, out):
+        n = int(out.n)
+        raw = dict(conduction=np.array(out.conduction[:n]),
+                   conductance=np.array([list(out.conductance[g][:n]) for g in range(n)]).reshape(n, n))
+        return CircuitState(U=np.array(out.U[:n]), U_old=np.array(out.U_old[:n]), U_old1=np.array(out.U_old1[:n]),
+                            dUdt=np.array(out.dUdt[:n]), lead_current=np.array(out.lead_current[:n]),
+                            conduction=elementary_charge * raw["conduction"],
+                            conductance=elementary_charge * raw["conductance"], flag=int(out.flag), raw=raw)
+
+    def circuit_advance(self, voltages, read=False):
+        """The electrodes' potentials at the end of the step ``set_step`` has set, for the sources' ``voltages`` there,
+        written into the Dirichlet values the next solve reads (``fedm_circuit_advance``).  ``read``: read the record
+        back (a :class:`CircuitState`; the call's only synchronisation); otherwise None."""
+        V = np.zeros(_lib.CURRENTS_MAX)
+        v = np.asarray(voltages, dtype=np.float64).reshape(-1)
+        if v.size != getattr(self, "_currents_n", 0):
+            raise ValueError(f"circuit_advance: {getattr(self, '_currents_n', 0)} electrodes, got {v.size} voltages")
+        V[:v.size] = v
+        out = _lib.CircuitState() if read else None
+        self._check(self.lib.fedm_circuit_advance(self._h, _dp(V), C.byref(out) if read else None), "fedm_circuit_advance")
+        return self._circuit_state(out) if read else None
+
+    def circuit_get(self):
+        """What the device holds of the circuit (``fedm_circuit_get``): a :class:`CircuitState`."""
+        out = _lib.CircuitState()
+        self._check(self.lib.fedm_circuit_get(self._h, C.byref(out)), "fedm_circuit_get")
+        return self._circuit_state(out)
 
     # -- field output (csrc/fields.hip) ---------------------------------------------------
     def fields_setup(self, consistent=False):

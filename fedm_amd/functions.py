@@ -1007,7 +1007,8 @@ def Electrode_currents(problem, boundary_tags=None, weighting_potentials=None, r
     Dirichlet vertex of the potential, and solved for on the device with natural conditions elsewhere (conjugate
     gradients to ``rtol``); a vertex that would fall into two electrodes raises ``ValueError``.
     ``weighting_potentials``: nodal values ``[n_psi, n_vertices]`` taken as they are instead.  At most 8 potentials; the
-    conductors are the Dirichlet boundaries of the potential; no dielectric solids; no circuit feedback.
+    conductors are the Dirichlet boundaries of the potential; no dielectric solids.  :func:`External_circuit` closes the
+    loop through a series resistance.
 
     Returns a callable: ``currents()`` gives a :class:`fedm_amd.device.Currents` in SI units -- ``conduction``,
     ``displacement`` (of the variable-step BDF2 rate of change of the potential), ``total``, ``induced_charge``,
@@ -1024,7 +1025,70 @@ def Electrode_currents(problem, boundary_tags=None, weighting_potentials=None, r
         return dev.currents()
     currents.psi = dev.currents_psi()
     currents.iterations = its
+    currents.boundary_tags = None if boundary_tags is None else tuple(int(t) for t in boundary_tags)
     return currents
+
+
+class External_circuit:
+    """Extension (a discharge is never run from an ideal voltage source): each electrode of an
+    :func:`Electrode_currents` set-up behind a source voltage, a series ``resistance`` [ohm] (0: an ideal source) and a
+    stray ``capacitance`` to ground [F], closed on the device -- the conduction and the plasma's conductance seen from
+    the electrodes are measured there, a dense system of at most 8 x 8 gives the electrodes' potentials at the end of
+    the step, and they are written into the Dirichlet values the solve reads; nothing is read back on the way.
+    ``problem``: a :class:`Problem` (or its device problem).  ``currents``: the :func:`Electrode_currents` callable with
+    ``boundary_tags`` (its electrodes are the circuit's).  ``source``: a callable ``t -> V`` or one per electrode.
+    ``resistance``, ``capacitance``, ``initial`` (the electrodes' potentials at the start): a scalar or one per electrode.
+    Limits: one GPU; at most 8 electrodes; series R and parallel C only; first order in ``dt`` (the conduction is lagged
+    and linearised with a frozen-coefficient conductance); state snapshots do not cover the circuit's history.
+
+    ``advance(t)`` before a solve that ends at ``t`` (again for a retried step, after ``set_step``), ``accept()`` after
+    each accepted step, ``state()`` for a :class:`fedm_amd.device.CircuitState`."""
+
+    def __init__(self, problem, currents, source, resistance, capacitance=0.0, initial=0.0):
+        self.dev = dev = getattr(problem, "device", problem)
+        tags = getattr(currents, "boundary_tags", None)
+        if tags is None:
+            raise ValueError("fedm.External_circuit: currents must be an Electrode_currents with boundary_tags (the electrodes "
+                             "are Dirichlet boundaries of the potential)")
+        self.n = len(tags)
+        self.sources = [source] * self.n if callable(source) else list(source)
+        if len(self.sources) != self.n or not all(callable(f) for f in self.sources):
+            raise ValueError(f"fedm.External_circuit: one source or {self.n}, each a callable t -> V")
+        dev.circuit_setup(resistance, capacitance, initial, boundary_tags=tags)
+        dev.circuit_measure()
+
+    def voltages(self, t):
+        return [float(f(t)) for f in self.sources]
+
+    def advance(self, t, read=False):
+        return self.dev.circuit_advance(self.voltages(t), read=read)
+
+    def accept(self):
+        self.dev.circuit_measure()
+
+    def state(self):
+        return self.dev.circuit_get()
+
+    def bind(self, problem):
+        """Every solve of ``problem`` then starts with ``advance(self.t)``, after the problem's own refresh of its
+        Dirichlet values (which the electrodes' entries overwrite).  Returns the object itself, which carries the ``t``
+        that :func:`adaptive_solver` advances for its ``time_dependent_arguments``."""
+        self.t = 0.0
+        before = getattr(problem, "before_solve", None)
+
+        def before_solve():
+            if before is not None:
+                before()
+            self.advance(self.t)
+        problem.before_solve = before_solve
+        return self
+
+    def log_row(self, t, electrode=0):
+        """After ``accept()``: t, the source's voltage, U and the lead current of the step that ended at ``t``, and
+        e cond [A] and e G [S] of the state it left, for one electrode."""
+        s, g = self.state(), int(electrode)
+        return [float(t), float(self.sources[g](t)), float(s.U[g]), float(s.lead_current[g]), float(s.conduction[g]),
+                float(s.conductance[g, g])]
 
 
 def Field_output(problem, fields, probes=None, projection="lumped", species_names=None):

@@ -248,7 +248,9 @@ const char *fedm_last_error(void);
  *    fedm_fields_setup, fedm_probe_setup and fedm_fields with fedm_field_req and fedm_field_opts.
  *    fedm_gd_balance_setup and fedm_gd_balance with fedm_gd_balance.
  *    fedm_gd_fields_setup, fedm_gd_probe_setup and fedm_gd_fields with the FEDM_GD_FIELD_* kinds.
- *    fedm_currents_setup, fedm_currents_solve, fedm_currents_get_psi and fedm_currents with fedm_currents. */
+ *    fedm_currents_setup, fedm_currents_solve, fedm_currents_get_psi and fedm_currents with fedm_currents.
+ *    fedm_circuit_setup, fedm_circuit_measure, fedm_circuit_advance and fedm_circuit_get with fedm_circuit_desc and
+ *    fedm_circuit_state. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -1029,6 +1031,82 @@ int fedm_currents_get_psi(fedm_ctx *ctx, double *psi);
 /* One pass over the cells, a one-workgroup finish, one read-back.  Touches no state and no field table; returns 0 also
  * when out->finite is 0, and the next call is unaffected.  Refused (-2): as fedm_currents_setup; no set-up. */
 int fedm_currents(fedm_ctx *ctx, struct fedm_currents *out);
+
+/* ---- external circuit of the driven electrodes (both families; what the electrode currents need; one GPU) -------------
+ * The n conductors of the fedm_currents_setup in force, weighting potentials psi_g, each behind a source voltage
+ * V_g(t), a series resistance R_g >= 0 and a stray capacitance Cp_g >= 0 to ground in parallel; the unknown is the
+ * conductor's potential U_g.  R_g = 0 is an ideal source: U_g = V_g(t), which still enters the others' equations
+ * through C_gh and G_gh.  For time-varying electrode voltages Ramo's theorem gives the current from the lead into
+ * electrode g as
+ *     I_g = e cond_g + eps0 sum_h C_gh dU_h/dt
+ * (cond_g: fedm_currents.conduction[g]; C_gh: fedm_currents.capacitance[g][h]): fedm_currents' total written without
+ * the state's time derivative -- the two differ by eps0 sum W grad(D_t Phi_sc) . grad psi_g, which vanishes for a
+ * discretely harmonic psi_g.  Kirchhoff at a driven electrode:
+ *     (V_g - U_g)/R_g - Cp_g dU_g/dt = I_g.
+ * (The signs follow from Q_g = -q psi_g(x); with them a vacuum gap charges as the capacitor eps0 C + Cp through R.)
+ * In time: dU/dt = a U^{n+1} + (-(1 + w)^2 U^n + w^2 U^{n-1}) / ((1 + w) dt), a = (1 + 2w)/((1 + w) dt), w = dt/dt_old --
+ * the variable-step BDF2 quotient of the species rows and of fedm_currents' D_t Phi, implicit in U^{n+1}; dt_old = 1e30
+ * on the first step makes it BDF1, as everywhere.  The conduction is linearised about the accepted state,
+ *     cond_g^{n+1} ~ cond_g(u^n) + sum_h G_gh (U_h^{n+1} - U_h^n),
+ * with the conductance G_gh = sum_cells sum_s Z_s^2 sum_q W mu_s n_s grad psi_g . grad psi_h, the derivative of the
+ * conduction sum with respect to U_h at frozen densities and frozen coefficients.  LFA: mu_s at the cell's |E| as the
+ * conduction has it, n_s = exp(u_s) or u_s (linear representation); species with a prescribed drift and species that are
+ * not 'drift-diffusion-reaction' add 0.  LMEA: the semi-implicit nodal mobilities and the densities at the quadrature
+ * points as the residual of the current step has them, species s >= 1 with sign_s^2, those whose flux has a drift part.
+ * G is symmetric and not negative; it decides stability, not consistency (U^{n+1} - U^n -> 0 with dt): the coupling is
+ * first order in dt.  The driven electrodes' U^{n+1} solve one dense system of at most 8 x 8,
+ *     [diag(1/R_g + a Cp_g) + a eps0 C + e G] U = V_g/R_g - e cond_g + e sum_h G_gh U_h^n - Cp_g hist_g
+ *                                                 - eps0 sum_h C_gh hist_h - sum_(h ideal) (a eps0 C_gh + e G_gh) V_h,
+ * rows and columns of the driven ones, by Gaussian elimination with partial pivoting on the device.
+ * Units: axisymmetric models give amperes, farads, ohms and siemens; in planar models everything is per metre of depth
+ * (A/m, F/m, ohm m, S/m).
+ * fedm_state_snapshot and fedm_state_restore do NOT cover the circuit's history (U, U_old, U_old1 and the measured
+ * quantities): a caller that restores a snapshot sets the circuit up again or keeps its own copy (fedm_circuit_get). */
+#define FEDM_VACUUM_PERMITTIVITY 8.854187817e-12   /* fedm/physical_constants.py:7 */
+typedef struct {
+    int32_t n, pad_;                            /* the n_psi of the currents set-up                                     */
+    double R[FEDM_CURRENTS_MAX];                /* series resistance [ohm], 0: ideal source                             */
+    double Cp[FEDM_CURRENTS_MAX];               /* stray capacitance to ground [F]                                      */
+    double U0[FEDM_CURRENTS_MAX];               /* the conductors' potentials at the start: U = U_old = U_old1          */
+    const int8_t *electrode_of_entry;           /* [n_dirichlet] in the order of fedm_mesh_desc.dirichlet_dofs (that of
+                                                   fedm_set_dirichlet_values): the electrode whose U the entry gets, -1:
+                                                   the entry is left alone                                              */
+} fedm_circuit_desc;
+#define FEDM_CIRCUIT_NOT_FINITE 1   /* the measured state, cond or G was not finite                                     */
+#define FEDM_CIRCUIT_SINGULAR 2     /* the system's pivot was 0 or not finite                                           */
+#define FEDM_CIRCUIT_BAD_RESULT 4   /* a U^{n+1} was not finite (a V, dt)                                               */
+struct fedm_circuit_state {
+    double U[FEDM_CURRENTS_MAX];                /* the last advance's U^{n+1}; before the first, U0                     */
+    double U_old[FEDM_CURRENTS_MAX];            /* U^n                                                                  */
+    double U_old1[FEDM_CURRENTS_MAX];           /* U^{n-1}                                                              */
+    double dUdt[FEDM_CURRENTS_MAX];             /* the BDF2 quotient of the last advance [V/s]                          */
+    double lead_current[FEDM_CURRENTS_MAX];     /* of the last advance: (V - U)/R [A]; for an ideal source the linearised
+                                                   I_g + Cp_g dU_g/dt                                                   */
+    double conduction[FEDM_CURRENTS_MAX];       /* cond_g of the last measure [1/s]                                     */
+    double conductance[FEDM_CURRENTS_MAX][FEDM_CURRENTS_MAX];   /* G_gh of the last measure [1/(V s)]                   */
+    int32_t n, flag;                            /* flag: 0 or FEDM_CIRCUIT_* of the last advance (before it: of the
+                                                   last measure)                                                        */
+};
+/* Copies the descriptor; U = U_old = U_old1 = U0; the capacitance of the currents set-up goes to the device.  Replaces
+ * an earlier set-up.  Refused (-2, fedm_last_error says why): no Poisson equation; a context with ghost vertices or a
+ * transport; no currents set-up, or one with another n; an R, Cp or U0 that is negative (R, Cp) or not finite; an entry
+ * mapped to an electrode outside 0..n-1 (-1 apart); a null argument, or no map in a context with Dirichlet entries. */
+int fedm_circuit_setup(fedm_ctx *ctx, const fedm_circuit_desc *desc);
+/* After an accepted step (and once before the first): U_old1 <- U_old <- U, then the currents' cell pass and the
+ * conductance pass at u_new (LMEA: with the field table as it stands), finished on the device in a fixed order without
+ * floating-point atomics.  No read-back and no synchronisation.  Refused (-2): no circuit set-up; a currents set-up
+ * that has since changed its n. */
+int fedm_circuit_measure(fedm_ctx *ctx);
+/* U^{n+1} for the context's dt and dt_old (fedm_set_step) and the sources' voltages V at the new time, written into
+ * the Dirichlet values of the mapped entries; every other entry keeps its value.  A pure function of the last measure,
+ * the history, the step and V: a rejected step that is retried with a smaller dt calls it again.  A state that was not
+ * finite, a singular system or a result that is not finite set the flag and leave U as it was (the entries then get
+ * that U).  out (unless NULL) is read back -- the only synchronisation; U_old, U_old1, conduction and conductance as
+ * fedm_circuit_get.  Returns 0 also with a flag.  Refused (-2): no set-up; no fedm_circuit_measure since the set-up; a
+ * null V. */
+int fedm_circuit_advance(fedm_ctx *ctx, const double V[FEDM_CURRENTS_MAX], struct fedm_circuit_state *out);
+/* What the device holds.  Refused (-2): no set-up; a null argument. */
+int fedm_circuit_get(fedm_ctx *ctx, struct fedm_circuit_state *out);
 
 /* timed micro-benchmarks on the resident state (HIP events on the library's stream):
  * kind 0 = residual+Jacobian assembly, 1 = SpMV, 2 = residual only, 3 = one multigrid cycle on the
