@@ -24,6 +24,10 @@ device without downloading the state (an extension: `fedm.Discharge_diagnostics`
 `--ballast OHMS [--stray-capacitance F] [--circuit-log FILE]` runs the anode behind a series resistor with a stray
 capacitance to ground, closed on the device (an extension: `fedm.External_circuit`), and writes t, the source's voltage,
 the anode's potential, the lead current, e cond and e G per accepted step; off by default.
+`--dielectric TAG:THICKNESS[:EPS_R] [--surface-charge-log FILE]` makes the boundary with that tag a dielectric layer
+with the electrode's conductor behind it and the surface charge built implicitly on the device (an extension:
+`fedm.Dielectric_layer`; 1 coats the cathode, 2 the anode), and writes t, the surface charge, the layer's displacement
+charge and its voltage per accepted step; off by default.
 `--currents FILE` writes t and the conduction, displacement and total current of the cathode and of the anode per
 accepted step (every N-th with `--currents-every N`), with weighting potentials solved for on the device (an extension:
 `fedm.Electrode_currents`); off by default.
@@ -149,15 +153,26 @@ class Fields:
         self.scratch = fem.Function(self.scalar)
 
 
-def electrode_conditions(case, space):
-    """Dirichlet values of the potential on the two electrodes for `space` (scalar or a sub-space)."""
+def electrode_conditions(case, space, coated=None):
+    """Dirichlet values of the potential on the two electrodes for `space` (scalar or a sub-space); `coated`: the tag
+    of an electrode behind a dielectric layer (1: the cathode, 2: the anode), which gets none -- the conductor is behind
+    the layer, and the layer's own condition stands on that boundary."""
     def on_cathode(x, on_boundary):
         return on_boundary and fem.near(x[1], 0)
 
     def on_anode(x, on_boundary):
         return on_boundary and fem.near(x[1], case.side)
-    return [fem.DirichletBC(space, fem.Constant(0.0), on_cathode),
-            fem.DirichletBC(space, fem.Constant(case.anode_voltage), on_anode)]
+    conditions = {1: fem.DirichletBC(space, fem.Constant(0.0), on_cathode),
+                  2: fem.DirichletBC(space, fem.Constant(case.anode_voltage), on_anode)}
+    return [bc for tag, bc in conditions.items() if tag != coated]
+
+
+def parse_dielectric(text):
+    """`TAG:THICKNESS[:EPS_R]` -> (tag, thickness [m], eps_r); eps_r = 1 where it is not given"""
+    parts = str(text).split(":")
+    if len(parts) not in (2, 3):
+        raise ValueError(f"--dielectric {text!r}: expected TAG:THICKNESS[:EPS_R]")
+    return int(parts[0]), float(parts[1]), float(parts[2]) if len(parts) == 3 else 1.0
 
 
 def initial_state(case, deck, fl, dx, radius, writers, t):
@@ -185,8 +200,10 @@ def initial_state(case, deck, fl, dx, radius, writers, t):
         target[-1].assign(potential)
 
 
-def coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before, photoionization=False):
-    """Ion and electron balance in logarithmic variables + Poisson, local field approximation."""
+def coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before, photoionization=False, dielectric=None):
+    """Ion and electron balance in logarithmic variables + Poisson, local field approximation.  `dielectric`: (tag,
+    thickness, eps_r) of a boundary that is a dielectric layer; the conductor behind it has the voltage of the electrode
+    the layer coats (0 V on any other boundary)."""
     wall_tags = fedm.Marking_boundaries(mesh, list(case.wall_lines().values()))
     ds = fem.Measure("ds", domain=mesh, subdomain_data=wall_tags)
     outward = fem.FacetNormal(mesh)
@@ -230,6 +247,10 @@ def coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before, photoionizatio
         for k in range(n_sp):
             form += fedm.Boundary_flux(case.walls[wall][k], case.kinds[k], case.roles[k], deck["charge_numbers"][k],
                                        mobility[k], field_vector, outward, u[k], 0.0, v[k], ds(tag), radius)
+    if dielectric is not None:
+        tag, thickness, eps_r = dielectric
+        form += fedm.Dielectric_layer(u[i_phi], v[i_phi], ds(tag), thickness, eps_r,
+                                      voltage={1: 0.0, 2: case.anode_voltage}.get(tag, 0.0), r=radius)
     return form, wall_tags
 
 
@@ -247,12 +268,14 @@ def currents_row(t, c):
 
 
 CIRCUIT_COLUMNS = ("t", "V_s", "U", "lead_current", "conduction", "conductance")
+SURFACE_CHARGE_COLUMNS = ("t", "surface_charge", "displacement_charge", "voltage")
 
 
 def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_dir=None, output_dir=None,
          quiet=False, stop_before_device=None, coupling="coupled", model="benchmark_model", photoionization=False,
          diagnostics=None, diagnostics_every=1, fields=None, fields_every=1, axis_profile=None, currents=None,
-         currents_every=1, ballast=None, stray_capacitance=0.0, circuit_log=None):
+         currents_every=1, ballast=None, stray_capacitance=0.0, circuit_log=None, dielectric=None,
+         surface_charge_log=None):
     """Runs the case; returns (state as (n_vertices, 3) array of ln n_i, ln n_e, Phi; error-log path).
     `model`: the deck folder under the input directory ("benchmark_model", "tabulated_model").
     `photoionization`: add the Helmholtz photoionisation source (coupled step only).
@@ -264,7 +287,16 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
     the cathode and of the anode (fedm.Electrode_currents, their weighting potentials solved for on the device).
     `ballast`: a series resistance [ohm] between the source and the anode, with `stray_capacitance` [F] to ground in
     parallel (fedm.External_circuit; the cathode stays an ideal ground); `circuit_log`: a file that receives
-    CIRCUIT_COLUMNS of the anode per accepted step."""
+    CIRCUIT_COLUMNS of the anode per accepted step.
+    `dielectric`: `TAG:THICKNESS[:EPS_R]`, the boundary with that tag becomes a dielectric layer (fedm.Dielectric_layer:
+    tag 1 coats the cathode, tag 2 the anode, whose Dirichlet values leave; coupled step only; the initial potential is
+    that of the bare electrodes); `surface_charge_log`: a file that receives SURFACE_CHARGE_COLUMNS per accepted step.
+    None: the path as it was."""
+    layer = parse_dielectric(dielectric) if dielectric is not None else None
+    if layer is not None and coupling != "coupled":
+        raise ValueError("--dielectric runs with the coupled step only")
+    if surface_charge_log is not None and layer is None:
+        raise ValueError("--surface-charge-log needs --dielectric")
     case = Case(deck=model) if end_time is None else Case(deck=model, end_time=end_time)
     fem.parameters["form_compiler"]["quadrature_degree"] = 2
     deck = read_deck(case, input_dir)
@@ -289,7 +321,7 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
     t = 0.0
     file_io.log("initial time", file_io.files.model_log, t)
     initial_state(case, deck, fl, dx, radius, writers, t)
-    form, wall_tags = coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before, photoionization)
+    form, wall_tags = coupled_form(case, deck, fl, mesh, dx, radius, dt, dt_before, photoionization, layer)
     fem.File(str(out / "mesh" / "boundary_mesh_function.pvd")) << wall_tags
     fl.join.assign(fl.before, list(fl.parts_before))
     fl.join.assign(fl.now, list(fl.parts_now))
@@ -297,7 +329,8 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
     residual = fem.action(form, fl.now)
     jacobian = fem.derivative(residual, fl.now, fl.trial)
     build_problem = stop_before_device or fedm.Problem
-    problem = build_problem(jacobian, residual, electrode_conditions(case, fl.mixed.sub(deck["n_equations"] - 1)))
+    problem = build_problem(jacobian, residual, electrode_conditions(case, fl.mixed.sub(deck["n_equations"] - 1),
+                                                                     coated=layer[0] if layer is not None else None))
     problem.device.setup_multigrid(nu=1)                 # preconditioner of the device's GMRES (no script counterpart)
     diagnose = rows = None
     if diagnostics is not None:
@@ -312,6 +345,10 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
         currents_of = fedm.Electrode_currents(problem, boundary_tags=(1, 2))
         current_rows = open(currents, "w")
         current_rows.write("# " + " ".join(CURRENTS_COLUMNS) + "\n")
+    charge_rows = None
+    if surface_charge_log is not None:
+        charge_rows = open(surface_charge_log, "w")
+        charge_rows.write("# " + " ".join(SURFACE_CHARGE_COLUMNS) + "\n")
     circuit = circuit_rows = None
     timed = []
     if ballast is not None:
@@ -370,6 +407,13 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
             if circuit_rows is not None:
                 circuit_rows.write(" ".join(f"{x:.17g}" for x in circuit.log_row(t, 1)) + "\n")
                 circuit_rows.flush()
+        if charge_rows is not None:
+            # (the accept of this step, which the next state shift would make: made here, once, so the row does not lag)
+            problem.device.accept_layers()
+            charge = problem.device.dielectric_charge(vertices=False)
+            charge_rows.write(" ".join(f"{x:.17g}" for x in (t, charge["charge"][layer[0]], charge["displacement"][layer[0]],
+                                                              charge["voltage"][layer[0]])) + "\n")
+            charge_rows.flush()
         dt_before.time_step = dt.time_step
         dt.time_step = fedm.adaptive_timestep(dt.time_step, recent_errors, case.step_tolerance, case.shortest_step,
                                               case.longest_step)
@@ -408,6 +452,8 @@ def main(cells=None, mesh_spacing=2.5e-5, mesh_file=None, end_time=None, input_d
         current_rows.close()
     if circuit_rows is not None:
         circuit_rows.close()
+    if charge_rows is not None:
+        charge_rows.close()
     return problem.device.get_state(), file_io.files.error_file
 
 
@@ -440,6 +486,11 @@ if __name__ == "__main__":
     ap.add_argument("--stray-capacitance", type=float, default=0.0, metavar="F", help="... with this capacitance to ground in parallel")
     ap.add_argument("--circuit-log", metavar="FILE",
                     help="... and write %s of the anode per accepted step" % ", ".join(CIRCUIT_COLUMNS))
+    ap.add_argument("--dielectric", metavar="TAG:THICKNESS[:EPS_R]",
+                    help="make the boundary with that tag a dielectric layer (fedm.Dielectric_layer; 1: the cathode, 2: the "
+                         "anode); off by default")
+    ap.add_argument("--surface-charge-log", metavar="FILE",
+                    help="... and write %s of the layer per accepted step" % ", ".join(SURFACE_CHARGE_COLUMNS))
     ap.add_argument("--save-state", metavar="FILE", help="write the final state (n_vertices, 3) as a .npy file")
     a = ap.parse_args()
     state, log_path = main(cells=a.cells, mesh_spacing=a.mesh_spacing, mesh_file=a.mesh, end_time=a.end,
@@ -447,7 +498,7 @@ if __name__ == "__main__":
                            diagnostics=a.diagnostics, diagnostics_every=a.diagnostics_every, fields=a.fields,
                            fields_every=a.fields_every, axis_profile=a.axis_profile, currents=a.currents,
                            currents_every=a.currents_every, ballast=a.ballast, stray_capacitance=a.stray_capacitance,
-                           circuit_log=a.circuit_log)
+                           circuit_log=a.circuit_log, dielectric=a.dielectric, surface_charge_log=a.surface_charge_log)
     if a.save_state:
         import numpy
         numpy.save(a.save_state, state)

@@ -191,6 +191,16 @@ class CircuitState(C.Structure):
                 ("conductance", (C.c_double * CURRENTS_MAX) * CURRENTS_MAX), ("n", C.c_int32), ("flag", C.c_int32)]
 
 
+class DielectricDesc(C.Structure):
+    _fields_ = [("is_layer", C.c_int32 * MAX_TAGS), ("thickness", C.c_double * MAX_TAGS), ("eps_r", C.c_double * MAX_TAGS),
+                ("voltage", C.c_double * MAX_TAGS)]
+
+
+class DielectricTotals(C.Structure):
+    _fields_ = [("charge", C.c_double * MAX_TAGS), ("displacement", C.c_double * MAX_TAGS),
+                ("voltage", C.c_double * MAX_TAGS), ("n_layer_vertices", C.c_int32), ("pad_", C.c_int32)]
+
+
 FIELDS_MAX_REQ = 8
 
 
@@ -235,6 +245,13 @@ _SIGNATURES = {
                                             _D, _D, C.c_int, C.POINTER(_P)]),
     "fedm_ctx_create_walls": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(ModelDesc), C.POINTER(WallDesc), C.c_int,
                                         C.POINTER(C.c_int32), _D, _D, C.c_int, C.POINTER(_P)]),
+    "fedm_ctx_create_dielectric": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(ModelDesc), C.POINTER(WallDesc),
+                                             C.POINTER(DielectricDesc), C.c_int, C.POINTER(C.c_int32), _D, _D, C.c_int,
+                                             C.POINTER(_P)]),
+    "fedm_dielectric_set_voltage": (C.c_int, [_P, _D]),
+    "fedm_dielectric_accept": (C.c_int, [_P]),
+    "fedm_dielectric_get": (C.c_int, [_P, C.POINTER(DielectricTotals), _D, _D]),
+    "fedm_dielectric_set": (C.c_int, [_P, _D, _D]),
     "fedm_ctx_create_gd": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(GdDesc), C.c_int, C.POINTER(_P)]),
     "fedm_gd_set_fields": (C.c_int, [_P, _D]),
     "fedm_gd_get_fields": (C.c_int, [_P, _D]),

@@ -139,14 +139,26 @@ def default_photoionization(**overrides):
     return Photoionization(**kw)
 
 
-def device_problem(coords, cells, device=0, deck_model=None, photoionization=None, **model_kw):
+def device_problem(coords, cells, device=0, deck_model=None, photoionization=None, dielectric=None, **model_kw):
     """``deck_model``: the model of that deck folder (``model_from_deck``: "benchmark_model", "tabulated_model")
     instead of the built-in strings.  ``photoionization``: a :class:`fedm_amd.device.Photoionization` (``True``: the
-    case's own, :func:`default_photoionization`); None: none, as the benchmark's case 1."""
+    case's own, :func:`default_photoionization`); None: none, as the benchmark's case 1.  ``dielectric``: a
+    :class:`fedm_amd.device.Dielectric`; an electrode it coats (tag 1: the cathode, tag 2: the anode) loses its
+    Dirichlet values -- the conductor is behind the layer, at the electrode's voltage unless the description names
+    another; None: the path as it was."""
+    import copy
     msh = Mesh(coords, cells)
     tags = Marking_boundaries(msh, BOUNDARIES)
     dofs, vals = dirichlet(msh.coords)
     lfa = model_from_deck(model_name=deck_model, **model_kw) if deck_model else model(**model_kw)
+    if dielectric is not None:
+        dielectric = copy.deepcopy(dielectric)      # (the caller's description stays as it was given)
+        z = msh.coords[dofs // lfa.n_eq, 1]
+        for tag, on, volts in ((1, np.abs(z) < 3e-16, 0.0), (2, np.abs(z - BOX) < 3e-16, U_W)):
+            if tag in dielectric.thickness:
+                dofs, vals, z = dofs[~on], vals[~on], z[~on]
+                dielectric.voltage.setdefault(tag, volts)
+    lfa.dielectric = dielectric
     if photoionization is not None and photoionization is not False:
         lfa.photoionization = default_photoionization() if photoionization is True else photoionization
     return DeviceProblem(msh.coords, msh.cells, lfa, facet_tags=tags,
@@ -266,6 +278,7 @@ class Stepper:
         if self._circuit_spec is not None and self.circuit is None:
             self._circuit_setup()
         self.prob.shift_state()                              # :306-307
+        self.prob.accept_layers()                            # (dielectric layers: the charge of the step just accepted)
         sink = io.StringIO() if self.quiet else None
         with (contextlib.redirect_stdout(sink) if sink else contextlib.nullcontext()):
             self.t = ff.adaptive_solver(self.solver, self.problem, self.t, self.dt, self.dt_old,
@@ -298,6 +311,15 @@ class Stepper:
             self.t, d.z_head, d.window_max, d.field_max, d.species_integral[0], d.species_integral[1], d.net_charge,
             d.surface_charge[0], d.surface_charge[1], d.current, dens[0], dens[1])))
 
+    def surface_charge(self):
+        """Per dielectric layer tag the surface charge, the layer's displacement charge [C] and its voltage, of the
+        last accepted step (``DeviceProblem.dielectric_charge``; one small read-back).  The time loop leaves the accept
+        of a step to the state shift of the next one; a step that is still waiting for it is accepted here first, so
+        the figures never lag (the accept depends on ``u_new`` and the step sizes alone: before or behind the shift it
+        gives the same charge, and it is made once)."""
+        self.prob.accept_layers()
+        return self.prob.dielectric_charge(vertices=False)
+
     def currents(self):
         """The electrode currents of the device-resident state (``fedm_amd.functions.Electrode_currents``; no download):
         electrode 0 the cathode (tag 1), electrode 1 the anode (tag 2), their weighting potentials solved for on the
@@ -320,14 +342,22 @@ class Stepper:
 
     def snapshot(self):
         """Checkpoint of the time loop: the three states stay on the device (fedm_state_snapshot), the
-        script-level scalars (time, step sizes, error history, counters) are returned."""
+        script-level scalars (time, step sizes, error history, counters) are returned -- and, for a problem with
+        dielectric layers, the layers' charge and its predecessor, which the device-side snapshot does not cover."""
         self.prob.snapshot_state()
-        return dict(t=self.t, steps=self.steps, dt=self.dt.time_step, dt_old=self.dt_old.time_step,
+        snap = dict(t=self.t, steps=self.steps, dt=self.dt.time_step, dt_old=self.dt_old.time_step,
                     error=list(self.error), max_error=list(self.max_error),
                     newton=self.newton_iterations, linear=self.linear_iterations)
+        if getattr(self.prob.model, "dielectric", None) is not None:
+            self.prob.accept_layers()           # (a step still waiting for its accept belongs to the checkpoint)
+            charge = self.prob.dielectric_charge()
+            snap["layer_charge"] = (charge["q"], charge["q_old"])
+        return snap
 
     def restore(self, snap):
         self.prob.restore_state()
+        if "layer_charge" in snap:
+            self.prob.set_dielectric_charge(*snap["layer_charge"])
         self.t, self.steps = snap["t"], snap["steps"]
         self.dt.time_step, self.dt_old.time_step = snap["dt"], snap["dt_old"]
         self.error[:], self.max_error[:] = snap["error"], snap["max_error"]

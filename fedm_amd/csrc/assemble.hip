@@ -6,6 +6,7 @@
 
 #include "comm.hpp"
 #include "device_util.hpp"
+#include "dielectric.hpp"
 #include "element.hpp"
 #include "element_lean.hpp"
 #include "fedm_internal.hpp"
@@ -644,6 +645,9 @@ void launch_assemble(Ctx &c, bool jacobian, int mode) {
     else if (c.ns == 3 && c.poisson) assemble_dispatch<3, true>(c, jacobian, mode);
     else if (c.ns == 4 && c.poisson) assemble_dispatch<4, true>(c, jacobian, mode);
     prof_end(c);
+    // dielectric layers: the Robin term and the charge's history in the Poisson rows, in both modes (the mirrored
+    // facet terms come with the facets below, in the full assembly alone)
+    if (c.diel) launch_layer_rows(c, jacobian, mode);
     if (mode == 0) {
         static const bool fuse_off = [] {
             const char *e = std::getenv("FEDM_FUSED_BOUNDARY");

@@ -1350,8 +1350,9 @@ bool lean3_applies(const Ctx &c) {
     // (FEDM_ASSEMBLY_LEAN below 3 keeps the earlier generations: Ctx::assembly_lean, read when the context is created)
     // (a wall model: its emission term fills a species plane that the precompiled plane masks of these kernels leave
     // out, and the species-only variant's facet kernel has no wall twin: the second generation takes it, as a table model)
+    // (a layer model: its facets add to the potential-potential plane, which these kernels' plane masks keep)
     if (c.assembly_lean < 3 || c.ns != 2 || !c.poisson || c.model.n_reactions > 1 || c.pat.max_patch_cells > 2 * 192 ||
-        c.model_walls)
+        c.model_walls || c.diel)
         return false;
     Lean3Plan<2, 1> plan;
     return lean3_build_plan<2, 1>(c.model, plan);

@@ -3,6 +3,7 @@
 #include <cassert>
 #include <type_traits>
 
+#include "dielectric.hpp"
 #include "element.hpp"
 #include "fedm_internal.hpp"
 
@@ -42,17 +43,41 @@ struct JacobianSink {
     }
 };
 
+// A facet of a dielectric layer (dielectric.hpp): q_a(u) of the Poisson row is dt (1 + w)/(1 + 2w) e sum_s Z_s W_a,s(u)
+// plus history, W_a,s being exactly what goes through the sinks above for species row s.  So every residual term
+// (a, s, v) goes once more to (a, Phi, -kappa Z_s v) and every Jacobian entry (a, b, s, col, v) to (a, b, Phi, col,
+// -kappa Z_s v), the potential column included: the mirror is made here, where the terms are placed, and the wall
+// formulas of element.hpp stay the one copy.  Facets of other tags pass through unchanged.
+template <int NS, bool TAB, bool WALL, class AddR, class AddJ>
+__device__ __forceinline__ void mirrored_facet(const fedm_model_desc *__restrict__ md, const double x[3][2],
+                                               const double Uc[3][NS + 1], int fi, int tag, bool jacobian, AddR addR,
+                                               AddJ addJ, const LayerMirror &lm) {
+    const bool on = (lm.tags >> (tag - 1)) & 1u;
+    auto mirrorR = [&](int a, int s, double value) {
+        addR(a, s, value);
+        if (on) addR(a, NS, lm.kz[s] * value);
+    };
+    auto mirrorJ = [&](int a, int b, int sr, int scol, double value) {
+        addJ(a, b, sr, scol, value);
+        if (on) addJ(a, b, NS, scol, lm.kz[sr] * value);
+    };
+    boundary_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian, mirrorR, mirrorJ);
+}
+
 // The facet record and the gather of its cell stand in both facet kernels, not in a helper: a device function that does
 // them is optimised on its own, with generic pointers, before it is inlined, and kernels come out with other registers,
 // scratch or spills than before the split (profiles/boundary_split_resources.md).
 // WALL: the 'flux source' wall terms besides (element.hpp, wall_facet; Ctx::model_walls)
-template <int NS, bool ATOMIC, bool SPECIES_COLS = false, bool TAB = false, bool WALL = false>
+// Layer: empty, or -- the DIEL switch, for a model with dielectric layers (Ctx::diel) -- one LayerMirror, which the
+// kernel then takes as its last argument.  A pack, so that without it the kernel has the signature and the body it had.
+template <int NS, bool ATOMIC, bool SPECIES_COLS = false, bool TAB = false, bool WALL = false, class... Layer>
 __global__ void boundary_kernel(const fedm_model_desc *__restrict__ md, int n_facets,
                                 const int *__restrict__ facets /* [n][3] = cell, local facet, tag */,
                                 const int *__restrict__ cells, const double *__restrict__ coords,
                                 const uint32_t *__restrict__ cell_slots,
                                 const double *__restrict__ u, double *__restrict__ val,
-                                double *__restrict__ F, int jacobian) {
+                                double *__restrict__ F, int jacobian, Layer... layer) {
+    static_assert(sizeof...(Layer) <= 1 && !(SPECIES_COLS && sizeof...(Layer)), "one LayerMirror, full assembly only");
     constexpr int NEQ = NS + 1;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_facets) return;
@@ -67,18 +92,24 @@ __global__ void boundary_kernel(const fedm_model_desc *__restrict__ md, int n_fa
     }
     ResidualSink<NEQ, ATOMIC> addR{F, v};
     JacobianSink<NEQ, ATOMIC, SPECIES_COLS> addJ{val, cell_slots, c};
-    boundary_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
+    if constexpr (sizeof...(Layer) == 0) boundary_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
+    else mirrored_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ, layer...);
 }
 
-// The model's compile-time switches from its run-time flags: fn(NS, TAB, WALL) with std::integral_constants for
-// (c.ns, c.model_tables, c.model_walls) -- the one place that turns them into template arguments of the kernels here
+// The model's compile-time switches from its run-time flags: fn(NS, TAB, WALL, DIEL) with std::integral_constants for
+// (c.ns, c.model_tables, c.model_walls, c.diel != null) -- the one place that turns them into template arguments of the
+// kernels here
 template <class Fn>
 static void with_model_flags(const Ctx &c, Fn &&fn) {
+    auto layers = [&](auto ns, auto tab, auto wall) {
+        if (c.diel) fn(ns, tab, wall, std::true_type{});
+        else fn(ns, tab, wall, std::false_type{});
+    };
     auto flags = [&](auto ns) {
-        if (c.model_walls && c.model_tables) fn(ns, std::true_type{}, std::true_type{});
-        else if (c.model_walls) fn(ns, std::false_type{}, std::true_type{});
-        else if (c.model_tables) fn(ns, std::true_type{}, std::false_type{});
-        else fn(ns, std::false_type{}, std::false_type{});
+        if (c.model_walls && c.model_tables) layers(ns, std::true_type{}, std::true_type{});
+        else if (c.model_walls) layers(ns, std::false_type{}, std::true_type{});
+        else if (c.model_tables) layers(ns, std::true_type{}, std::false_type{});
+        else layers(ns, std::false_type{}, std::false_type{});
     };
     switch (c.ns) {
         case 1: flags(std::integral_constant<int, 1>{}); break;
@@ -92,11 +123,16 @@ template <bool ATOMIC>
 static void launch_boundary_range(Ctx &c, bool jacobian, int f0, int n) {
     const dim3 g((n + 127) / 128), b(128);
     const int *fl = c.d_bfacets + 3 * f0;
-    with_model_flags(c, [&](auto ns, auto tab, auto wall) {
+    with_model_flags(c, [&](auto ns, auto tab, auto wall, auto diel) {
         constexpr int NS = decltype(ns)::value;
         constexpr bool TAB = decltype(tab)::value, WALL = decltype(wall)::value;
-        hipLaunchKernelGGL((boundary_kernel<NS, ATOMIC, false, TAB, WALL>), g, b, 0, c.stream, c.d_model, n, fl,
-                           c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0);
+        if constexpr (decltype(diel)::value)
+            hipLaunchKernelGGL((boundary_kernel<NS, ATOMIC, false, TAB, WALL, LayerMirror>), g, b, 0, c.stream, c.d_model, n,
+                               fl, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0,
+                               layer_mirror(c));
+        else
+            hipLaunchKernelGGL((boundary_kernel<NS, ATOMIC, false, TAB, WALL>), g, b, 0, c.stream, c.d_model, n, fl,
+                               c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0);
     });
 }
 
@@ -119,10 +155,10 @@ void launch_boundary(Ctx &c, bool jacobian) {
 // columns only.  Instantiated, like that kernel, for two species without tables or walls (assemble3.hip, lean3_applies).
 void launch_boundary_species_cols(Ctx &c, bool jacobian) {
     if (c.n_bfacets == 0) return;
-    assert(c.ns == 2 && !c.model_tables && !c.model_walls);
+    assert(c.ns == 2 && !c.model_tables && !c.model_walls && !c.diel);
     const dim3 g((c.n_bfacets + 127) / 128), b(128);
-    with_model_flags(c, [&](auto ns, auto tab, auto wall) {
-        if constexpr (decltype(ns)::value == 2 && !decltype(tab)::value && !decltype(wall)::value)
+    with_model_flags(c, [&](auto ns, auto tab, auto wall, auto diel) {
+        if constexpr (decltype(ns)::value == 2 && !decltype(tab)::value && !decltype(wall)::value && !decltype(diel)::value)
             hipLaunchKernelGGL((boundary_kernel<2, true, true>), g, b, 0, c.stream, c.d_model, c.n_bfacets, c.d_bfacets,
                                c.d_cells, c.d_coords, c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0);
     });
@@ -193,13 +229,15 @@ __global__ void identity_rows_kernel(int nv, int nvp, int neq, int ns_frozen,
 
 // boundary_kernel<NS, true> and dirichlet_kernel in one launch (128-thread blocks: the first ones take the facets, the
 // rest the Dirichlet and padding rows) -- allowed when no row belongs to both (Ctx::boundary_rows_disjoint)
-template <int NS, bool TAB, bool WALL = false>
+// Layer: as boundary_kernel's
+template <int NS, bool TAB, bool WALL = false, class... Layer>
 __global__ __launch_bounds__(128) void boundary_dirichlet_kernel(
     const fedm_model_desc *__restrict__ md, int n_facets, int facet_blocks, const int *__restrict__ facets,
     const int *__restrict__ cells, const double *__restrict__ coords, const uint32_t *__restrict__ cell_slots,
     const double *__restrict__ u, double *__restrict__ val, double *__restrict__ F, int jacobian, int n_dir,
     const int *__restrict__ dofs, const double *__restrict__ vals, const int *__restrict__ boff,
-    const uint32_t *__restrict__ diag_slot, int id_first, int n_id) {
+    const uint32_t *__restrict__ diag_slot, int id_first, int n_id, Layer... layer) {
+    static_assert(sizeof...(Layer) <= 1, "one LayerMirror");
     constexpr int NEQ = NS + 1;
     if ((int)blockIdx.x < facet_blocks) {
         const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -215,7 +253,8 @@ __global__ __launch_bounds__(128) void boundary_dirichlet_kernel(
         }
         ResidualSink<NEQ, true> addR{F, v};
         JacobianSink<NEQ, true, false> addJ{val, cell_slots, c};
-        boundary_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
+        if constexpr (sizeof...(Layer) == 0) boundary_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ);
+        else mirrored_facet<NS, TAB, WALL>(md, x, Uc, fi, tag, jacobian != 0, addR, addJ, layer...);
         return;
     }
     // the rows of dirichlet_kernel (one GPU: Dirichlet dofs, then the padding vertices [id_first, id_first + n_id))
@@ -241,13 +280,19 @@ void launch_finalize(Ctx &c, bool jacobian, int mode) {
         if (mode == 0 && jac == jacobian) {
             const int fb = (c.n_bfacets + 127) / 128, n_id = c.nvp - c.nv;
             const int rb = (c.n_dir_rows + n_id + 127) / 128;   // (no identity vertices here: n_dir_rows == n_dir)
-            with_model_flags(c, [&](auto ns, auto tab, auto wall) {
+            with_model_flags(c, [&](auto ns, auto tab, auto wall, auto diel) {
                 constexpr int NS = decltype(ns)::value;
                 constexpr bool TAB = decltype(tab)::value, WALL = decltype(wall)::value;
-                hipLaunchKernelGGL((boundary_dirichlet_kernel<NS, TAB, WALL>), dim3(fb + rb), dim3(128), 0, c.stream,
-                                   c.d_model, c.n_bfacets, fb, c.d_bfacets, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u,
-                                   c.d_val, c.d_F, jacobian ? 1 : 0, c.n_dir_rows, c.d_dir_dofs, c.d_dir_vals,
-                                   c.d_slice_boff, c.d_diag_slot, c.nv, n_id);
+                if constexpr (decltype(diel)::value)
+                    hipLaunchKernelGGL((boundary_dirichlet_kernel<NS, TAB, WALL, LayerMirror>), dim3(fb + rb), dim3(128), 0,
+                                       c.stream, c.d_model, c.n_bfacets, fb, c.d_bfacets, c.d_cells, c.d_coords,
+                                       c.d_cell_slots, c.d_u, c.d_val, c.d_F, jacobian ? 1 : 0, c.n_dir_rows, c.d_dir_dofs,
+                                       c.d_dir_vals, c.d_slice_boff, c.d_diag_slot, c.nv, n_id, layer_mirror(c));
+                else
+                    hipLaunchKernelGGL((boundary_dirichlet_kernel<NS, TAB, WALL>), dim3(fb + rb), dim3(128), 0, c.stream,
+                                       c.d_model, c.n_bfacets, fb, c.d_bfacets, c.d_cells, c.d_coords, c.d_cell_slots, c.d_u,
+                                       c.d_val, c.d_F, jacobian ? 1 : 0, c.n_dir_rows, c.d_dir_dofs, c.d_dir_vals,
+                                       c.d_slice_boff, c.d_diag_slot, c.nv, n_id);
             });
             return;
         }

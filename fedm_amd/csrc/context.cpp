@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "dielectric.hpp"
 #include "photo.hpp"
 #include "solver.hpp"
 
@@ -86,6 +87,7 @@ struct HostTables {
     const double *x = nullptr, *y = nullptr;
     const char *who = "fedm_ctx_create";   // the entry point, for the messages
     const fedm_wall_desc *walls = nullptr; // fedm_ctx_create_walls (checked by check_walls)
+    const fedm_dielectric_desc *layers = nullptr;   // fedm_ctx_create_dielectric (checked by check_layers); null: no layer
 };
 
 // Every table reference of the model against the tables: 0, or 1 with the message set.  The kernels trust both.
@@ -225,6 +227,42 @@ static int check_walls(const fedm_model_desc &m, const HostTables &t) {
     return 0;
 }
 
+// Every layer of the description against the model and the mesh: 0, or 1 with the message set (it names the tag as the
+// mesh numbers it, from 1).
+static int check_layers(const fedm_model_desc &m, const fedm_mesh_desc &mesh, const HostTables &t) {
+    const std::string who = std::string(t.who) + ": ";
+    if (!t.layers) return 0;
+    for (int tg = 0; tg < FEDM_MAX_TAGS; ++tg) {
+        if (!t.layers->is_layer[tg]) continue;
+        const std::string at = "the dielectric layer on tag " + std::to_string(tg + 1);
+        if (tg >= m.n_tags) {
+            set_error(who + at + ": the model has " + std::to_string(m.n_tags) + " boundary tags");
+            return 1;
+        }
+        if (!m.poisson) {
+            set_error(who + at + ": the model has no Poisson equation (the layer is a condition on the potential)");
+            return 1;
+        }
+        if (mesh.n_owned_vertices > 0 && mesh.n_owned_vertices < mesh.n_vertices) {
+            set_error(who + at + ": the mesh has ghost vertices; layers run on one GPU only");
+            return 1;
+        }
+        if (!std::isfinite(t.layers->thickness[tg]) || t.layers->thickness[tg] <= 0.0) {
+            set_error(who + at + ": the thickness d must be finite and positive");
+            return 1;
+        }
+        if (!std::isfinite(t.layers->eps_r[tg]) || t.layers->eps_r[tg] <= 0.0) {
+            set_error(who + at + ": the relative permittivity eps_r must be finite and positive");
+            return 1;
+        }
+        if (!std::isfinite(t.layers->voltage[tg])) {
+            set_error(who + at + ": the voltage is not finite");
+            return 1;
+        }
+    }
+    return 0;
+}
+
 // {fedm_model_desc; ModelTables; x; y; [fedm_wall_desc]} in one device allocation (fedm_internal.hpp, ModelTables)
 static int upload_model(fedm_model_desc *&dst, const fedm_model_desc &m, const HostTables &t) {
     const int total = t.n > 0 ? t.ptr[t.n] : 0;
@@ -307,7 +345,7 @@ static int ctx_create_lfa(const fedm_mesh_desc *mesh, const fedm_model_desc *mod
                   " quadrature points)");
         return -2;
     }
-    if (check_tables(*model, tables) || check_walls(*model, tables)) return -2;
+    if (check_tables(*model, tables) || check_walls(*model, tables) || check_layers(*model, *mesh, tables)) return -2;
     return ctx_create_guarded(mesh, model, nullptr, tables, device, out);
 }
 
@@ -345,6 +383,27 @@ int fedm_ctx_create_walls(const fedm_mesh_desc *mesh, const fedm_model_desc *mod
     t.walls = walls;
     if (n_tables > 0 && !tab_ptr) {
         set_error("fedm_ctx_create_walls: null tab_ptr");
+        return -2;
+    }
+    if (n_tables == 0) t.ptr = nullptr;
+    return ctx_create_lfa(mesh, model, t, device, out);
+}
+
+int fedm_ctx_create_dielectric(const fedm_mesh_desc *mesh, const fedm_model_desc *model, const fedm_wall_desc *walls,
+                               const fedm_dielectric_desc *layers, int n_tables, const int32_t *tab_ptr,
+                               const double *tab_x, const double *tab_y, int device, fedm_ctx **out) {
+    HostTables t;
+    t.n = n_tables;
+    t.ptr = tab_ptr;
+    t.x = tab_x;
+    t.y = tab_y;
+    t.who = "fedm_ctx_create_dielectric";
+    t.walls = walls;
+    // (a description without a layer: fedm_ctx_create_walls, kernel for kernel)
+    for (int tg = 0; layers && tg < FEDM_MAX_TAGS; ++tg)
+        if (layers->is_layer[tg]) t.layers = layers;
+    if (n_tables > 0 && !tab_ptr) {
+        set_error("fedm_ctx_create_dielectric: null tab_ptr");
         return -2;
     }
     if (n_tables == 0) t.ptr = nullptr;
@@ -590,6 +649,13 @@ static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *mo
             for (int a = 0; a < 3; ++a)
                 for (int sp = 0; sp < c.ns; ++sp)
                     if (is_dirichlet[(size_t)mesh->cells[3 * fcell[f] + a] * c.neq + sp]) c.boundary_rows_disjoint = false;
+        if (tables.layers) {
+            // a layer's facets add to the Poisson rows of its vertices as well: a Dirichlet row of the potential
+            // among them belongs to both the facets and the Dirichlet rows, so the two keep their own launches
+            bool dirichlet_on_layer = false;
+            if (const int rc = dielectric_setup(c, *tables.layers, *mesh, &dirichlet_on_layer)) return rc;
+            if (dirichlet_on_layer) c.boundary_rows_disjoint = false;
+        }
         // the rows that change behind the volume assembly (Ctx::planes_fused): vertices of boundary-facet cells, of
         // Dirichlet values, and the padding of the last slice
         {
@@ -658,6 +724,9 @@ static int ctx_create_impl(const fedm_mesh_desc *mesh, const fedm_model_desc *mo
                     if (!coupled) c.const_plane_mask |= 1u << (s_ * c.neq + i);
                 }
             c.zero_plane_mask = c.const_plane_mask & ~(1u << (c.ns * c.neq + c.ns));
+            // a layer's facets add the mirrored potential column and the Robin term to the potential-potential plane
+            // after every volume assembly: it is written afresh each time, like an emission plane
+            if (tables.layers) c.const_plane_mask &= ~(1u << (c.ns * c.neq + c.ns));
             if (const char *e = getenv("FEDM_SPMV_SKIP_ZERO_PLANES"))
                 if (e[0] == '0') c.zero_plane_mask = 0;
         }
@@ -761,6 +830,7 @@ void fedm_ctx_destroy(fedm_ctx *h) {
     fields_release(c);
     gd_balance_release(c);
     circuit_release(c);
+    dielectric_release(c);
     currents_release(c);
     fs_tiles_release(c);
     for (auto &e : c.prof.ev) hipEventDestroy(e);

@@ -79,6 +79,7 @@ struct Fields;
 struct GdBalance;
 struct Currents;
 struct Circuit;
+struct Dielectric;
 
 // Optional in-run kernel timing with HIP events on the library's stream (bench.py roofline).
 // kinds: 0 assembly F+J, 1 Jacobian SpMV, 2 assembly F only, 3 multigrid V-cycle
@@ -320,6 +321,7 @@ struct Ctx {
     GdBalance *gd_balance = nullptr;   // LMEA balance: psi, groups, the tags' facet lists and the reductions' buffers (gd_balance.hpp; allocated at first use)
     Currents *currents = nullptr;      // electrode currents: the weighting potentials, the capacitance and the reductions' buffers (currents.hpp; fedm_currents_setup)
     Circuit *circuit = nullptr;        // external circuit of the driven electrodes: the potentials' history, the conductance and the Dirichlet map (circuit.hpp; fedm_circuit_setup)
+    Dielectric *diel = nullptr;        // dielectric layers on boundary tags: the DIEL facet kernels, the layer vertices, their charge and its history (dielectric.hpp; fedm_ctx_create_dielectric)
 };
 
 // Indices of Ctx::path_stats, in the order fedm_solver_path_stats documents (include/fedm_hip.h)

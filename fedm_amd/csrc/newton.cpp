@@ -107,6 +107,11 @@ int segregated_refusal(Ctx &c, const char *who, bool species) {
                   "not been tried with (coupled step only: fedm_newton_solve)");
         return -2;
     }
+    if (c.diel) {
+        set_error(std::string(who) + ": this context has a dielectric layer, whose surface charge is built inside the coupled "
+                  "residual (coupled step only: fedm_newton_solve)");
+        return -2;
+    }
     if (species && c.krylov_scaling != 0) {
         set_error(std::string(who) + ": krylov scaling 'rows' is not defined for the species block (its own equilibration "
                   "is not implemented): set the krylov scaling to 'none'");

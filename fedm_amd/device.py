@@ -56,6 +56,30 @@ class Walls:
 
 
 @dataclass
+class Dielectric:
+    """Dielectric layers on boundary tags of an LFA model (thin-layer approximation, ``fedm_ctx_create_dielectric``): per
+    layer tag (as the mesh numbers it, from 1) the thickness [m], the relative permittivity and the voltage of the
+    conductor behind it at the start (:meth:`DeviceProblem.set_layer_voltage` changes it)."""
+    thickness: dict                            # {tag: d}
+    eps_r: dict = field(default_factory=dict)  # {tag: eps_r}, 1 where missing
+    voltage: dict = field(default_factory=dict)   # {tag: U}, 0 where missing
+
+    def tags(self):
+        return sorted(int(t) for t in self.thickness)
+
+    def to_c(self):
+        dd = _lib.DielectricDesc()
+        for t in self.tags():
+            if not 1 <= t <= _lib.MAX_TAGS:
+                raise ValueError(f"Dielectric: tag {t} outside 1..{_lib.MAX_TAGS}")
+            dd.is_layer[t - 1] = 1
+            dd.thickness[t - 1] = float(self.thickness[t])
+            dd.eps_r[t - 1] = float(self.eps_r.get(t, 1.0))
+            dd.voltage[t - 1] = float(self.voltage.get(t, 0.0))
+        return dd
+
+
+@dataclass
 class Model:
     """What fedm.functions' weak-form builders describe (see functions.py)."""
     n_species: int
@@ -74,6 +98,7 @@ class Model:
     walls: Optional[Walls] = None              # for the 'flux source' entries of bc_kind
     # Helmholtz photoionisation source (fedm_amd.photo): its targets get degree-1 source tables, which the device fills
     photoionization: Optional[Photoionization] = None
+    dielectric: Optional[Dielectric] = None    # dielectric layers on boundary tags (None: the model as it was)
 
     @property
     def n_eq(self):
@@ -710,7 +735,15 @@ class DeviceProblem:
             mesh.halo_depth = self.halo_depth
         handle = C.c_void_p()
         wd = None if isinstance(model, GdModel) else model.walls_to_c()
-        if wd is not None:      # 'flux source' walls (with or without tables)
+        layers = None if isinstance(model, GdModel) else model.dielectric
+        if layers is not None:  # dielectric layers (with or without walls and tables)
+            tab_ptr, tab_x, tab_y = tab if tab is not None else (np.zeros(1, dtype=np.int32), np.zeros(0), np.zeros(0))
+            dd = layers.to_c()
+            rc = self.lib.fedm_ctx_create_dielectric(C.byref(mesh), C.byref(md), None if wd is None else C.byref(wd),
+                                                     C.byref(dd), tab_ptr.size - 1,
+                                                     tab_ptr.ctypes.data_as(C.POINTER(C.c_int32)), _dp(tab_x), _dp(tab_y),
+                                                     int(device), C.byref(handle))
+        elif wd is not None:    # 'flux source' walls (with or without tables)
             tab_ptr, tab_x, tab_y = tab if tab is not None else (np.zeros(1, dtype=np.int32), np.zeros(0), np.zeros(0))
             rc = self.lib.fedm_ctx_create_walls(C.byref(mesh), C.byref(md), C.byref(wd), tab_ptr.size - 1,
                                                 tab_ptr.ctypes.data_as(C.POINTER(C.c_int32)), _dp(tab_x), _dp(tab_y),
@@ -1171,6 +1204,63 @@ class DeviceProblem:
         return Currents(conduction=elementary_charge * raw["conduction"], displacement=epsilon_0 * raw["displacement"],
                         induced_charge=elementary_charge * raw["induced_charge"], coupling=raw["coupling"].copy(),
                         capacitance=epsilon_0 * raw["capacitance"], finite=bool(out.finite), raw=raw)
+
+    # -- dielectric layers (csrc/dielectric.hip) ------------------------------------------
+    def set_layer_voltage(self, voltages):
+        """The voltage of the conductor behind every layer, ``{tag: U}`` (tags as the mesh numbers them; a layer that
+        is not named keeps its voltage), from the next assembly on (``fedm_dielectric_set_voltage``)."""
+        layers = getattr(self.model, "dielectric", None)
+        if layers is None:
+            raise ValueError("set_layer_voltage: this problem has no dielectric layer")
+        if not hasattr(self, "_layer_voltage"):      # what the context was created with, then what was set here
+            self._layer_voltage = {t: float(layers.voltage.get(t, 0.0)) for t in layers.tags()}
+        new = dict(self._layer_voltage)
+        for t, u in dict(voltages).items():
+            if int(t) not in new:
+                raise ValueError(f"set_layer_voltage: tag {t} is no dielectric layer of this problem")
+            new[int(t)] = float(u)
+        U = (C.c_double * _lib.MAX_TAGS)()
+        for t, u in new.items():
+            U[t - 1] = u
+        self._check(self.lib.fedm_dielectric_set_voltage(self._h, U), "fedm_dielectric_set_voltage")
+        self._layer_voltage = new
+
+    def dielectric_accept(self):
+        """After an accepted step (and its state shift): the surface charge of the accepted state becomes q^n, the
+        one before it q^(n-1) (``fedm_dielectric_accept``; no read-back)."""
+        self._check(self.lib.fedm_dielectric_accept(self._h), "fedm_dielectric_accept")
+        self._layers_solved = False
+
+    def accept_layers(self):
+        """What the time loops call after their state shift: :meth:`dielectric_accept` if the model has layers and a
+        Newton solve has succeeded since the last accept (the first shift of a run comes before any solve)."""
+        if getattr(self.model, "dielectric", None) is not None and getattr(self, "_layers_solved", False):
+            self.dielectric_accept()
+
+    def dielectric_charge(self, vertices=True):
+        """Per layer tag the surface charge ``sum_a q_a`` and the layer's displacement charge ``eps0 eps_r/d int (Phi -
+        U) 2 pi r ds`` [C; C/m planar] and its voltage; with ``vertices`` also ``q`` and ``q_old`` per vertex in the
+        caller's numbering, 0 off the layers (``fedm_dielectric_get``)."""
+        tot = _lib.DielectricTotals()
+        q, qo = (np.zeros(self.nv), np.zeros(self.nv)) if vertices else (None, None)
+        self._check(self.lib.fedm_dielectric_get(self._h, C.byref(tot), None if q is None else _dp(q),
+                                                 None if qo is None else _dp(qo)), "fedm_dielectric_get")
+        tags = self.model.dielectric.tags() if getattr(self.model, "dielectric", None) is not None else []
+        out = dict(charge={t: tot.charge[t - 1] for t in tags}, displacement={t: tot.displacement[t - 1] for t in tags},
+                   voltage={t: tot.voltage[t - 1] for t in tags}, n_layer_vertices=int(tot.n_layer_vertices))
+        if vertices:
+            out["q"], out["q_old"] = q[self._inv], qo[self._inv]
+        return out
+
+    def set_dielectric_charge(self, q=None, q_old=None):
+        """``q^n`` and ``q^(n-1)`` per vertex (caller's numbering; entries off the layers are ignored), for restarts
+        (``fedm_dielectric_set``).  A solved step that was still waiting for its accept is dropped with the history
+        it belonged to."""
+        self._layers_solved = False
+        dev = [None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(self.nv)[self._order])
+               for a in (q, q_old)]
+        self._check(self.lib.fedm_dielectric_set(self._h, *[None if a is None else _dp(a) for a in dev]),
+                    "fedm_dielectric_set")
 
     # -- external circuit (csrc/circuit.hip) ----------------------------------------------
     def circuit_setup(self, resistance, capacitance=0.0, initial=0.0, electrode_of_entry=None, boundary_tags=None):
@@ -1694,6 +1784,7 @@ class DeviceProblem:
         self.last_report = NewtonReport(r.iterations, bool(r.converged), r.linear_iterations,
                                         r.fnorm0, r.fnorm)
         self._check(rc, "fedm_newton_solve")
+        self._layers_solved = True     # (accept_layers: there is a solved step to accept)
         return r.iterations, True
 
     def poisson_solve(self, rtol=1e-10, max_it=20000):

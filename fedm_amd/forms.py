@@ -434,6 +434,10 @@ class DeviceState:
             # (fedm-streamer.py:306-307): the rotation happens on the second call
             if pair == ("old", "new"):
                 self.device.shift_state()
+                # a model with dielectric layers: the accepted step's charge (a device without layers has nothing to accept)
+                accept_layers = getattr(self.device, "accept_layers", None)
+                if accept_layers is not None:
+                    accept_layers()
         else:
             self.device.set_state(**{"u_" + self.which: np.asarray(other)})
 

@@ -177,6 +177,51 @@ def Boundary_flux(bc_type, equation_type, particle_type, sign, mu, E, normal, u,
     return 0.0
 
 
+class DielectricTerm(FormPiece):
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def Dielectric_layer(u, v, ds_temp, thickness, eps_r, voltage=0.0, r=0.5 / np.pi):
+    """A dielectric layer on the boundary ``ds_temp`` marks (no counterpart in the reference): thickness [m], relative
+    permittivity and the voltage of the conductor behind it, in the thin-layer approximation -- one-dimensional along
+    the normal, no conduction along the solid.  ``u`` is the potential, ``v`` its test function; the piece is added to
+    ``F`` like a :func:`Boundary_flux`.  On the layer the potential's natural condition becomes dPhi/dn = sigma/eps0 -
+    eps_r (Phi - voltage)/thickness, and the surface charge sigma collects e sum_s Z_s Gamma_s.n of whatever wall term
+    each species has there ('flux source' with its emission, 'Neumann', nothing for 'zero flux'), implicitly, inside the
+    Newton residual (include/fedm_hip.h, "dielectric-coated electrodes").  The potential gets no DirichletBC on that
+    boundary: the conductor is behind the layer.  Limits: LFA models with a Poisson equation, one GPU, the coupled step;
+    :func:`Electrode_currents` and :func:`External_circuit` do not yet see a coated electrode.
+    ``problem.device.set_layer_voltage({tag: U})`` changes the voltage between solves, ``dielectric_charge()`` reads the
+    surface and displacement charge per tag; the accept follows the state shift by itself."""
+    for name, x in (("thickness", thickness), ("eps_r", eps_r)):
+        if not isinstance(x, (int, float)) or isinstance(x, bool) or not x > 0.0:
+            raise ValueError(f"fedm.Dielectric_layer: {name} must be a positive number")
+    if not isinstance(voltage, (int, float)) or isinstance(voltage, bool):
+        raise ValueError("fedm.Dielectric_layer: voltage must be a number (set_layer_voltage changes it between solves)")
+    return DielectricTerm(u=u, v=v, tag=ds_temp.tag, ds=ds_temp, thickness=float(thickness), eps_r=float(eps_r),
+                          voltage=float(voltage), r=r)
+
+
+def _lower_layers(pieces, ns, poisson):
+    """The Dielectric_layer pieces of an LFA form as device.Dielectric, or None when there are none."""
+    from .device import Dielectric
+    layers = [p for p in pieces if isinstance(p, DielectricTerm)]
+    if not layers:
+        return None
+    out = Dielectric(thickness={}, eps_r={}, voltage={})
+    for p in layers:
+        where = f"Dielectric_layer on tag {p.tag}"
+        if not poisson:
+            raise ValueError(f"{where}: the model has no Poisson equation")
+        if getattr(p.u, "index", None) != ns:
+            raise ValueError(f"{where}: u must be the potential, the last component of the mixed space")
+        if p.tag in out.thickness:
+            raise ValueError(f"{where}: the tag has a layer already")
+        out.thickness[p.tag], out.eps_r[p.tag], out.voltage[p.tag] = p.thickness, p.eps_r, p.voltage
+    return out
+
+
 def _axisymmetric(r):
     """r = Expression('x[0]') (cylindrical) vs the default 0.5/pi (fedm/functions.py:251)."""
     if isinstance(r, (int, float)):
@@ -319,6 +364,11 @@ def compile_forms(F, quadrature_degree=None):
     pieces = F.pieces if isinstance(F, FormSum) else [F]
     from . import lmea
     if lmea.is_lmea(pieces):
+        for p in pieces:
+            if isinstance(p, DielectricTerm):
+                # refused, never dropped: the LMEA facets are another kernel family's and have no mirror
+                raise ValueError(f"fedm.Dielectric_layer on tag {p.tag}: the LMEA family has no dielectric layers "
+                                 "(LFA models only)")
         qd = quadrature_degree if quadrature_degree is not None else forms.parameters["form_compiler"]["quadrature_degree"]
         if qd is None or qd < 0:
             raise NotImplementedError("set parameters['form_compiler']['quadrature_degree'] (fedm-gd.py:28)")
@@ -417,8 +467,10 @@ def compile_forms(F, quadrature_degree=None):
             if Z[i] not in (0.0,) and abs(Z[i] - zi) > 1e-9 * max(1.0, abs(zi)):
                 raise ValueError("charge in the Poisson source differs from the flux sign")
             Z[i] = zi
-    n_tags = max([b.tag for b in bterms] + (list(photo.zero_tags) if photo is not None else []), default=0)
-    tags_mf = next((b.ds.subdomain_data for b in bterms if b.ds.subdomain_data is not None), None)
+    layers = _lower_layers(pieces, ns, bool(poissons))
+    layer_terms = [p for p in pieces if isinstance(p, DielectricTerm)]
+    n_tags = max([b.tag for b in bterms + layer_terms] + (list(photo.zero_tags) if photo is not None else []), default=0)
+    tags_mf = next((b.ds.subdomain_data for b in bterms + layer_terms if b.ds.subdomain_data is not None), None)
     if tags_mf is None and photo is not None:
         tags_mf = photo.subdomain_data
     if photo is not None and photo.zero_tags and tags_mf is None:
@@ -442,6 +494,8 @@ def compile_forms(F, quadrature_degree=None):
             "set parameters['form_compiler']['quadrature_degree'] (UFL's automatic degree "
             "estimation is reproduced only for the time-of-flight case, see DESIGN.md)")
     extra = {}
+    if layers is not None:
+        extra["dielectric"] = layers
     if any(w is not None for w in drift_w):
         extra["drift_w"] = drift_w
     if ext_sources:

@@ -250,7 +250,9 @@ const char *fedm_last_error(void);
  *    fedm_gd_fields_setup, fedm_gd_probe_setup and fedm_gd_fields with the FEDM_GD_FIELD_* kinds.
  *    fedm_currents_setup, fedm_currents_solve, fedm_currents_get_psi and fedm_currents with fedm_currents.
  *    fedm_circuit_setup, fedm_circuit_measure, fedm_circuit_advance and fedm_circuit_get with fedm_circuit_desc and
- *    fedm_circuit_state. */
+ *    fedm_circuit_state.
+ *    fedm_ctx_create_dielectric, fedm_dielectric_set_voltage, fedm_dielectric_accept, fedm_dielectric_get and
+ *    fedm_dielectric_set with fedm_dielectric_desc and fedm_dielectric_totals. */
 #define FEDM_ABI_VERSION 10
 int fedm_abi_version(void);
 
@@ -1107,6 +1109,62 @@ int fedm_circuit_measure(fedm_ctx *ctx);
 int fedm_circuit_advance(fedm_ctx *ctx, const double V[FEDM_CURRENTS_MAX], struct fedm_circuit_state *out);
 /* What the device holds.  Refused (-2): no set-up; a null argument. */
 int fedm_circuit_get(fedm_ctx *ctx, struct fedm_circuit_state *out);
+
+/* ---- dielectric-coated electrodes (LFA models, one GPU, coupled step) ---------------------------------------------
+ * A boundary tag T may be a dielectric layer of thickness d_T and relative permittivity epsr_T with a conductor at
+ * voltage U_T behind it, treated as one-dimensional along the outward normal n (thin layer, no conduction along the
+ * solid).  With the surface charge density sigma the potential's natural condition on T is
+ *     dPhi/dn = sigma/eps0 - epsr_T (Phi - U_T)/d_T,        d sigma/dt = e sum_s Z_s Gamma_s . n,
+ * Gamma_s . n being whatever wall term species s has on T (the 'flux source' expression with its emission, the Neumann
+ * drift term, nothing for 'zero flux').  The device keeps, per vertex a of a layer, the charge moment
+ *     q_a = int_T sigma phi_a 2 pi r ds    [C; C/m planar]
+ * and its history.  W_a,s(u): what the facet kernels add to residual entry (a, s) on the layer's facets.  With
+ * w = dt/dt_old the charge is a function of the iterate,
+ *     q_a(u) = [(1 + w)^2 q_a^n - w^2 q_a^(n-1)]/(1 + 2w) + dt (1 + w)/(1 + 2w) e sum_s Z_s W_a,s(u),
+ * the variable-step BDF2 quotient of the species rows, so plasma charge + surface charge is conserved by the scheme.
+ * The Poisson row of a layer vertex gains, in its own measure and scaling (charge_over_eps),
+ *     R_Phi,a += sum_q W_q (epsr_T/d_T)(Phi_q - U_T) phi_a - q_a(u)/eps0
+ * and the Jacobian its exact derivative: the Robin mass term in the (Phi, Phi) plane, and every entry (a, b, s, col, v)
+ * that a layer facet makes in a species row mirrored as (a, b, Phi, col, -kappa Z_s v), kappa = charge_over_eps
+ * dt (1 + w)/(1 + 2w).  The (Phi, Phi) plane of such a context is therefore not constant (fedm_plane_masks).
+ * fedm_jacobian_poisson_only and fedm_poisson_solve (species frozen) hold the Robin term and the accepted charge
+ * q^n alone -- nothing of the mirror, which depends on the iterate: the multigrid hierarchy is built from that plane.
+ * A vertex that is on a layer and a Dirichlet vertex of the potential keeps its Dirichlet row; its q_a is kept all the
+ * same.  A vertex on facets of several layers counts for the lowest of their tags in the totals. */
+typedef struct {
+    int32_t is_layer[FEDM_MAX_TAGS];    /* 1: tag t + 1 is a layer                                                     */
+    double thickness[FEDM_MAX_TAGS];    /* d [m], > 0                                                                  */
+    double eps_r[FEDM_MAX_TAGS];        /* relative permittivity, > 0                                                  */
+    double voltage[FEDM_MAX_TAGS];      /* U at the start [V] (fedm_dielectric_set_voltage)                            */
+} fedm_dielectric_desc;
+struct fedm_dielectric_totals {
+    double charge[FEDM_MAX_TAGS];        /* sum_a q_a of the tag's vertices [C; C/m planar]                            */
+    double displacement[FEDM_MAX_TAGS];  /* eps0 epsr/d int (Phi - U) 2 pi r ds over the tag's facets, at u_new        */
+    double voltage[FEDM_MAX_TAGS];       /* U as it stands                                                             */
+    int32_t n_layer_vertices, pad_;
+};
+/* fedm_ctx_create_walls with layers (walls null: none; layers null or without a layer: that call, kernel for kernel).
+ * q = q_old = 0 at the start.  Refused (-2, nothing allocated, fedm_last_error says why and names the tag): a layer on
+ * a model without the Poisson equation; a context with ghost vertices (one GPU only); d or epsr that is not finite or
+ * not positive; a voltage that is not finite; a layer tag beyond the model's n_tags.  Layer models run the
+ * second-generation assembly, never the one-pass kernels, and never the facets' launch fused with the Dirichlet rows
+ * when a layer vertex has a Dirichlet row of the potential. */
+int fedm_ctx_create_dielectric(const fedm_mesh_desc *mesh, const fedm_model_desc *model, const fedm_wall_desc *walls,
+                               const fedm_dielectric_desc *layers, int n_tables, const int32_t *tab_ptr,
+                               const double *tab_x, const double *tab_y, int device, fedm_ctx **out);
+/* The calls below are refused (-2) on an LMEA context ("the LMEA family has no dielectric layers") and on a context
+ * without a layer. */
+/* U of every tag (entries of tags that are no layer are ignored), from the next assembly on.  Refused: not finite. */
+int fedm_dielectric_set_voltage(fedm_ctx *ctx, const double U[FEDM_MAX_TAGS]);
+/* After an accepted step: q_old <- q, q <- q(u_new) with the context's dt and dt_old -- a residual-only pass over the
+ * facets, colour by colour without atomics, so two runs give the same bytes.  A rejected step needs nothing undone.
+ * No read-back, no synchronisation. */
+int fedm_dielectric_accept(fedm_ctx *ctx);
+/* The totals (one fixed-order reduction, one read-back) and q, q_old per vertex ([n_vertices], 0 off the layers); any
+ * of the three may be null. */
+int fedm_dielectric_get(fedm_ctx *ctx, struct fedm_dielectric_totals *totals, double *q, double *q_old);
+/* q and q_old per vertex ([n_vertices]; entries off the layers are ignored; null: left alone), for restarts. */
+int fedm_dielectric_set(fedm_ctx *ctx, const double *q, const double *q_old);
 
 /* timed micro-benchmarks on the resident state (HIP events on the library's stream):
  * kind 0 = residual+Jacobian assembly, 1 = SpMV, 2 = residual only, 3 = one multigrid cycle on the
