@@ -146,6 +146,15 @@ def _pack(levels, dense_coarse=True, restrictions=None):
     return n, A, P, R, coarse, keep
 
 
+def pack_hierarchy(levels, nu, omega):
+    """One scalar solve's ``PhotoHierarchy`` (``fedm_photo_setup``, ``fedm_currents_solve``; one level: Jacobi, no
+    coarse inverse), and the objects its pointers refer to: they must outlive the call that takes the struct."""
+    n, A, P, R, coarse, keep = _pack(levels, dense_coarse=len(levels) > 1)
+    h = _lib.PhotoHierarchy(n_levels=n, nu=int(nu), omega=float(omega), A=A, P=P, R=R)
+    h.coarse_inverse = coarse.ctypes.data_as(C.POINTER(C.c_double)) if coarse is not None else None
+    return h, (A, P, R, coarse, keep)
+
+
 def install(handle, levels, nu=2, omega=0.67, dense_coarse=True, restrictions=None):
     """Upload a hierarchy built by :func:`build_hierarchy` into a device context.
     ``dense_coarse=False``: no inverse of the last level (a global hierarchy takes over there,

@@ -311,10 +311,7 @@ __global__ void currents_merge_kernel(int n, const unsigned char *__restrict__ f
 void currents_release(Ctx &c) {
     Currents *k = c.currents;
     if (!k) return;
-    if (k->cg) {
-        photo_cg_free(*k->cg);
-        delete k->cg;
-    }
+    k->cg.release();
     void *ptrs[] = {k->psi, k->sum_part, k->flag_part, k->result, k->psi_new, k->rhs, k->x, k->b, k->fixed};
     for (void *p : ptrs)
         if (p) hipFree(p);
@@ -359,20 +356,17 @@ int form_capacitance(Ctx &c, const double *psi, int n_psi, double cap[CUR_MAX][C
 
 int ensure_solve_buffers(Ctx &c) {
     Currents &k = *c.currents;
-    if (k.cg) return 0;
+    if (k.fixed) return 0;
     const size_t nvp = (size_t)c.nvp;
-    k.cg = new Photo();
     if (device_array<double>(k.psi_new, nullptr, nvp * CUR_MAX) || device_array<double>(k.rhs, nullptr, nvp * CUR_MAX) ||
         device_array<double>(k.x, nullptr, nvp) || device_array<double>(k.b, nullptr, nvp) ||
-        device_array<unsigned char>(k.fixed, nullptr, nvp) || photo_cg_alloc(*k.cg, nvp)) {
-        // nothing half-made stays behind (photo_cg_alloc has freed its own): the next call starts from nothing again
+        device_array<unsigned char>(k.fixed, nullptr, nvp) || k.cg.alloc(nvp)) {
+        // nothing half-made stays behind (the scratch has freed its own): the next call starts from nothing again
         void *ptrs[] = {k.psi_new, k.rhs, k.x, k.b, k.fixed};
         for (void *p : ptrs)
             if (p) hipFree(p);
         k.psi_new = k.rhs = k.x = k.b = nullptr;
         k.fixed = nullptr;
-        delete k.cg;
-        k.cg = nullptr;
         return -1;
     }
     return 0;
@@ -454,52 +448,27 @@ int fedm_currents_solve(fedm_ctx *h, const fedm_photo_hierarchy *laplace, const 
     if (!c.currents || c.currents->n_psi == 0) return refuse(who, "fedm_currents_setup has not been called");
     Currents &k = *c.currents;
     if (!(rtol > 0.0) || max_it < 0) return refuse(who, "rtol must be positive and max_it not negative");
-    const fedm_photo_hierarchy &t = *laplace;
-    if (t.n_levels < 1 || !t.A || (t.n_levels > 1 && (!t.P || !t.R || !t.coarse_inverse || t.nu < 1)))
-        return refuse(who, "bad hierarchy (levels with their prolongators, restrictions and a dense coarsest inverse; "
-                           "V(nu,nu) with nu >= 1)");
-    const fedm_csr &A0 = t.A[0];
-    if (A0.n_rows != c.nv || A0.n_cols != c.nv || !A0.indptr || !A0.indices || !A0.values)
-        return refuse(who, "the operator has " + std::to_string(A0.n_rows) + " rows, the mesh " + std::to_string(c.nv) +
-                               " vertices");
     for (size_t i = 0; i < (size_t)k.n_psi * c.nv; ++i)
         if (!std::isfinite(rhs[i]))
             return refuse(who, "rhs[" + std::to_string(i / c.nv) + "][" + std::to_string(i % c.nv) + "] is not finite");
+    FEDM_HIP_CHECK(hipSetDevice(c.device));
+    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
+    if (ensure_solve_buffers(c)) return -1;
+    EllMat A;
+    Amg *M = nullptr;
+    auto drop = [&] { release_hierarchy(A, M); };
+    if (const int rc = upload_hierarchy(c, who, "", *laplace, A, M)) {
+        drop();
+        return rc;
+    }
     // the conductors' vertices: the unit rows of the eliminated operator (and the padding)
+    const fedm_csr &A0 = laplace->A[0];
     std::vector<unsigned char> fixed((size_t)c.nvp, 1);
     for (int v = 0; v < c.nv; ++v) {
         bool unit = true;
         for (int64_t j = A0.indptr[v]; j < A0.indptr[v + 1] && unit; ++j)
             unit = A0.values[j] == (A0.indices[j] == v ? 1.0 : 0.0);
         fixed[v] = unit && A0.indptr[v + 1] > A0.indptr[v] ? 1 : 0;
-    }
-    FEDM_HIP_CHECK(hipSetDevice(c.device));
-    FEDM_HIP_CHECK(hipStreamSynchronize(c.stream));
-    if (ensure_solve_buffers(c)) return -1;
-    EllMat A;
-    Amg *M = nullptr;
-    auto drop = [&] {
-        A.release();
-        if (M) {
-            M->release();
-            delete M;
-        }
-    };
-    A.single = false;
-    if (const int rc = A.from_csr(A0, true)) {
-        set_error(std::string(who) + ": operator upload failed (bad CSR or out of memory)");
-        drop();
-        return rc < -1 ? -2 : -1;
-    }
-    if (A.n_rows_p != c.nvp) {
-        drop();
-        return refuse(who, "the operator's padded rows differ from the context's");
-    }
-    if (t.n_levels > 1) {   // plain sweeps on every level, as a photoionisation term's
-        if (const int rc = build_amg(c, c.nv, t.n_levels, t.A, t.P, t.R, t.coarse_inverse, t.nu, t.omega, &M, t.n_levels + 1)) {
-            drop();
-            return rc;
-        }
     }
     const size_t nvp = (size_t)c.nvp;
     // (between A / M and drop(): an early return would leak them, so the uploads' status is collected and looked at once)
@@ -514,24 +483,19 @@ int fedm_currents_solve(fedm_ctx *h, const fedm_photo_hierarchy *laplace, const 
     }
     const dim3 gv((c.nvp + 255) / 256), bl(256);
     int rc = 0;
-    // scalar_pcg takes its scratch vectors from Ctx::photo: ours stand in for the duration of the solves (fields.hip)
-    Photo *const kept = c.photo;
-    c.photo = k.cg;
     for (int g = 0; g < CUR_MAX; ++g) {
         int its = 0;
         if (g < k.n_psi && rc == 0) {
             hipLaunchKernelGGL(currents_split_kernel, gv, bl, 0, c.stream, c.nvp, k.fixed, k.psi + g * nvp, k.rhs + g * nvp,
                                k.x, k.b);
-            const ScalarCgResult cg = scalar_pcg(c, A, M, k.b, k.x, rtol, max_it);
+            const ScalarCgResult cg = scalar_pcg(c, k.cg, A, M, k.b, k.x, rtol, max_it);
             its = cg.it;
-            if (!std::isfinite(cg.rnorm) || !std::isfinite(cg.bnorm)) rc = FEDM_DIVERGED_NAN;
-            else if (cg.rnorm > rtol * cg.bnorm) rc = FEDM_DIVERGED_LINEAR;
+            rc = cg.status(rtol);
             hipLaunchKernelGGL(currents_merge_kernel, gv, bl, 0, c.stream, c.nvp, k.fixed, k.psi + g * nvp, k.x,
                                k.psi_new + g * nvp);
         }
         if (iterations) iterations[g] = its;
     }
-    c.photo = kept;
     double cap[CUR_MAX][CUR_MAX] = {};
     if (rc == 0) {
         if (const int rc2 = form_capacitance(c, k.psi_new, k.n_psi, cap)) {

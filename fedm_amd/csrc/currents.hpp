@@ -1,8 +1,8 @@
 // Electrode currents (include/fedm_hip.h, fedm_currents_setup / fedm_currents_solve / fedm_currents): what the kernels
 // and the C ABI in currents.hip share with the context's teardown.
 #pragma once
-#include "photo.hpp"
 #include "postproc.hpp"
+#include "scalar_cg.hpp"
 
 namespace fedm {
 
@@ -25,12 +25,12 @@ struct Currents {
     double *sum_part = nullptr;   // [CUR_SUMS][POST_BLOCKS]
     int *flag_part = nullptr;     // [POST_BLOCKS]
     CurResult *result = nullptr;
-    // fedm_currents_solve (allocated at its first call): the candidates, one system and the vectors scalar_pcg borrows
+    // fedm_currents_solve (allocated at its first call): the candidates, one system and scalar_pcg's scratch
     double *psi_new = nullptr;    // [CUR_MAX][nvp]
     double *rhs = nullptr;        // [CUR_MAX][nvp] the caller's right-hand sides
     double *x = nullptr, *b = nullptr;   // [nvp] the free vertices' values and their right-hand side (0 on the unit rows)
     unsigned char *fixed = nullptr;      // [nvp] 1: a unit row of the operator (a conductor's vertex), and the padding
-    Photo *cg = nullptr;          // r, z, p, q, partials, red alone: Ctx::photo points here for the duration of a solve
+    ScalarCgWork cg;
 };
 
 #ifdef __HIPCC__

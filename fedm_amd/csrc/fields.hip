@@ -230,10 +230,7 @@ void fields_release(Ctx &c) {
     Fields *f = c.fields;
     if (!f) return;
     f->M.release();
-    if (f->cg) {
-        photo_cg_free(*f->cg);
-        delete f->cg;
-    }
+    f->cg.release();
     void *ptrs[] = {f->v_ptr, f->v_idx, f->m, f->cell_b, f->out, f->first, f->flag, f->rhs, f->p_vert, f->p_w, f->p_out};
     for (void *p : ptrs)
         if (p) hipFree(p);
@@ -259,13 +256,8 @@ int setup_impl(Ctx &c, const fedm_csr *mass, const char *who) {
     FEDM_HIP_CHECK(hipMemcpy(cells.data(), c.d_cells, sizeof(int) * cells.size(), hipMemcpyDeviceToHost));
     FEDM_HIP_CHECK(hipMemcpy(coords.data(), c.d_coords, sizeof(double) * coords.size(), hipMemcpyDeviceToHost));
     // vertex -> (cell, corner) in ascending order, and the lumped mass added in that order
-    std::vector<int> v_ptr((size_t)c.nv + 1, 0), v_idx((size_t)3 * c.nc);
-    for (size_t k = 0; k < cells.size(); ++k) ++v_ptr[cells[k] + 1];
-    for (int v = 0; v < c.nv; ++v) v_ptr[v + 1] += v_ptr[v];
-    {
-        std::vector<int> fill(v_ptr.begin(), v_ptr.end() - 1);
-        for (size_t k = 0; k < cells.size(); ++k) v_idx[fill[cells[k]]++] = (int)k;
-    }
+    std::vector<int> v_ptr, v_idx;
+    vertex_cell_lists(c.nv, cells, v_ptr, v_idx);
     std::vector<double> m((size_t)c.nvp, 0.0);
     for (int v = 0; v < c.nv; ++v) {
         double s = 0.0;
@@ -292,8 +284,7 @@ int setup_impl(Ctx &c, const fedm_csr *mass, const char *who) {
             return rc < -1 ? -2 : -1;
         }
         if (f.M.n_rows_p != c.nvp) return refuse(who, "the mass matrix's padded rows differ from the context's");
-        f.cg = new Photo();
-        if (device_array<double>(f.rhs, nullptr, nvp) || photo_cg_alloc(*f.cg, nvp)) return -1;
+        if (device_array<double>(f.rhs, nullptr, nvp) || f.cg.alloc(nvp)) return -1;
         f.have_mass = true;
     }
     FEDM_HIP_CHECK(hipDeviceSynchronize());
@@ -327,26 +318,20 @@ int evaluate(Ctx &c, const double *u, int n_req, const int *slot, const FieldsLa
     launch(u, raw, dst);
     int rc = 0;
     if (raw) {
-        // the load vector of request k sits in dst[k]: it moves to rhs, and dst[k] becomes the solution from 0.
-        // scalar_pcg takes its scratch vectors from Ctx::photo: ours stand in for the duration of the solve.
-        Photo *const kept = c.photo;
-        c.photo = f.cg;
+        // the load vector of request k sits in dst[k]: it moves to rhs, and dst[k] becomes the solution from 0
         for (int k = 0; k < n_req; ++k) {
             if (slot[k] < 0) continue;
             double *x = dst + (size_t)k * c.nvp;
             hipMemcpyAsync(f.rhs, x, sizeof(double) * c.nvp, hipMemcpyDeviceToDevice, c.stream);
             hipMemsetAsync(x, 0, sizeof(double) * c.nvp, c.stream);
-            const ScalarCgResult cg = scalar_pcg(c, f.M, nullptr, f.rhs, x, o.rtol, o.max_it);
+            const ScalarCgResult cg = scalar_pcg(c, f.cg, f.M, nullptr, f.rhs, x, o.rtol, o.max_it);
             its[k] += cg.it;
-            if (!std::isfinite(cg.rnorm) || !std::isfinite(cg.bnorm)) {
-                hipMemsetAsync(f.flag, 0xff, sizeof(int), c.stream);
-            } else if (cg.rnorm > o.rtol * cg.bnorm) {
-                rc = FEDM_DIVERGED_LINEAR;
-            }
+            const int status = cg.status(o.rtol);
+            if (status == FEDM_DIVERGED_NAN) hipMemsetAsync(f.flag, 0xff, sizeof(int), c.stream);
+            else if (status == FEDM_DIVERGED_LINEAR) rc = status;
             hipLaunchKernelGGL(fields_finite_kernel, dim3((c.nvp + FIELDS_THREADS - 1) / FIELDS_THREADS), b, 0, c.stream,
                                c.nvp, x, f.flag);
         }
-        c.photo = kept;
     }
     return rc;
 }

@@ -5,7 +5,7 @@
 #include <functional>
 #include <string>
 
-#include "photo.hpp"
+#include "scalar_cg.hpp"
 
 namespace fedm {
 
@@ -20,11 +20,11 @@ struct Fields {
     double *first = nullptr;      // [FEDM_FIELDS_MAX_REQ][nvp] X(u_old) while X(u_new) is formed (a blend of two states)
     double *h_out = nullptr;      // pinned [FEDM_FIELDS_MAX_REQ][nvp]: the nodal results on their way to the caller's rows
     int *flag = nullptr;          // [1] not-finite flag of a call
-    // consistent projection: the P1 mass matrix, one right-hand side and the vectors scalar_pcg borrows
+    // consistent projection: the P1 mass matrix, one right-hand side and scalar_pcg's scratch
     bool have_mass = false;
     EllMat M;
     double *rhs = nullptr;        // [nvp]
-    Photo *cg = nullptr;          // r, z, p, q, partials, red alone: Ctx::photo points here for the duration of a solve
+    ScalarCgWork cg;
     // probes
     int n_points = 0;
     int *p_vert = nullptr;        // [n_points][3]

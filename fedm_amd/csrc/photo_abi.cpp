@@ -1,24 +1,18 @@
 // C ABI of libfedm_hip.so (include/fedm_hip.h): photoionisation in the Helmholtz approximation.  Host logic only: the
-// kernels and the conjugate gradients are in photo.hip.
+// kernels are in photo.hip, the conjugate gradients in scalar_cg.hip.  The one place that assigns Ctx::photo.
 #include <cmath>
 #include <cstring>
 
+#include "photo.hpp"
 #include "postproc.hpp"
-#include "solver.hpp"
 
 namespace fedm {
 
 void photo_release(Ctx &c) {
     Photo *ph = c.photo;
     if (!ph) return;
-    for (int m = 0; m < PHOTO_MAX_TERMS; ++m) {
-        ph->A[m].release();
-        if (ph->M[m]) {
-            ph->M[m]->release();
-            delete ph->M[m];
-        }
-    }
-    photo_cg_free(*ph);
+    for (int m = 0; m < PHOTO_MAX_TERMS; ++m) release_hierarchy(ph->A[m], ph->M[m]);
+    ph->cg.release();
     void *ptrs[] = {ph->y, ph->g, ph->cell_g, ph->v_ptr, ph->v_idx, ph->zero};
     for (void *p : ptrs)
         if (p) hipFree(p);
@@ -71,13 +65,8 @@ int setup_impl(Ctx &c, const fedm_photo_desc &d, const fedm_photo_hierarchy *ter
     std::vector<int8_t> tags((size_t)3 * c.nc);
     FEDM_HIP_CHECK(hipMemcpy(cells.data(), c.d_cells, sizeof(int) * cells.size(), hipMemcpyDeviceToHost));
     FEDM_HIP_CHECK(hipMemcpy(tags.data(), c.d_ftags, sizeof(int8_t) * tags.size(), hipMemcpyDeviceToHost));
-    std::vector<int> v_ptr((size_t)c.nv + 1, 0), v_idx((size_t)3 * c.nc);
-    for (size_t k = 0; k < cells.size(); ++k) ++v_ptr[cells[k] + 1];
-    for (int v = 0; v < c.nv; ++v) v_ptr[v + 1] += v_ptr[v];
-    {
-        std::vector<int> fill(v_ptr.begin(), v_ptr.end() - 1);
-        for (size_t k = 0; k < cells.size(); ++k) v_idx[fill[cells[k]]++] = (int)k;
-    }
+    std::vector<int> v_ptr, v_idx;
+    vertex_cell_lists(c.nv, cells, v_ptr, v_idx);
     std::vector<unsigned char> zero((size_t)c.nvp, 0);
     for (int cell = 0; cell < c.nc; ++cell)
         for (int i = 0; i < 3; ++i) {   // facet i lies opposite vertex i
@@ -91,36 +80,18 @@ int setup_impl(Ctx &c, const fedm_photo_desc &d, const fedm_photo_hierarchy *ter
         return -1;
     const size_t nvp = (size_t)c.nvp;
     if (device_array<double>(ph.y, nullptr, nvp * d.n_terms) || device_array<double>(ph.g, nullptr, nvp) ||
-        device_array<double>(ph.cell_g, nullptr, (size_t)3 * c.nc) || photo_cg_alloc(ph, nvp))
+        device_array<double>(ph.cell_g, nullptr, (size_t)3 * c.nc) || ph.cg.alloc(nvp))
         return -1;
     for (int m = 0; m < d.n_terms; ++m) {
-        const fedm_photo_hierarchy &t = terms[m];
-        const std::string term = "term " + std::to_string(m);
-        if (t.n_levels < 1 || !t.A || (t.n_levels > 1 && (!t.P || !t.R || !t.coarse_inverse || t.nu < 1)))
-            return refuse(who, term + ": bad hierarchy (levels with their prolongators, restrictions and a dense coarsest "
-                                      "inverse; V(nu,nu) with nu >= 1)");
-        if (t.A[0].n_rows != c.nv || t.A[0].n_cols != c.nv)
-            return refuse(who, term + ": the operator has " + std::to_string(t.A[0].n_rows) + " rows, the mesh " +
-                               std::to_string(c.nv) + " vertices");
+        const std::string term = "term " + std::to_string(m) + ": ";
+        if (const int rc = upload_hierarchy(c, who, term, terms[m], ph.A[m], ph.M[m])) return rc;
         // the zero vertices' rows must be unit rows: y stays 0 there through every sweep and product
+        const fedm_csr &A0 = terms[m].A[0];
         for (int v = 0; v < c.nv; ++v) {
             if (!zero[v]) continue;
-            const int64_t b = t.A[0].indptr[v], e = t.A[0].indptr[v + 1];
-            for (int64_t k = b; k < e; ++k)
-                if (t.A[0].values[k] != (t.A[0].indices[k] == v ? 1.0 : 0.0))
-                    return refuse(who, term + ": the row of zero vertex " + std::to_string(v) + " is not a unit row");
-        }
-        ph.A[m].single = false;
-        const int rc = ph.A[m].from_csr(t.A[0], true);
-        if (rc) {
-            set_error("fedm_photo_setup: " + term + ": operator upload failed (bad CSR or out of memory)");
-            return rc < -1 ? -2 : -1;
-        }
-        if (t.n_levels > 1) {
-            // plain sweeps on every level (composite operators from level n_levels on, i.e. nowhere)
-            if (const int rc2 = build_amg(c, c.nv, t.n_levels, t.A, t.P, t.R, t.coarse_inverse, t.nu, t.omega, &ph.M[m],
-                                          t.n_levels + 1))
-                return rc2;
+            for (int64_t k = A0.indptr[v]; k < A0.indptr[v + 1]; ++k)
+                if (A0.values[k] != (A0.indices[k] == v ? 1.0 : 0.0))
+                    return refuse(who, term + "the row of zero vertex " + std::to_string(v) + " is not a unit row");
         }
     }
     FEDM_HIP_CHECK(hipDeviceSynchronize());
@@ -167,15 +138,17 @@ int fedm_photo_update(fedm_ctx *h, double rtol, int max_it, int iterations[4]) {
     for (int m = 0; m < PHOTO_MAX_TERMS; ++m) {
         int its = 0;
         if (m < ph.desc.n_terms) {
-            const ScalarCgResult cg = scalar_pcg(c, ph.A[m], ph.M[m], ph.g, ph.y + (size_t)m * c.nvp, rtol, max_it);
+            const ScalarCgResult cg = scalar_pcg(c, ph.cg, ph.A[m], ph.M[m], ph.g, ph.y + (size_t)m * c.nvp, rtol, max_it);
             its = cg.it;
             ph.stats[PH_CG_ITS0 + m] += its;
-            if (!std::isfinite(cg.rnorm) || !std::isfinite(cg.bnorm)) {
+            ph.stats[PH_VCYCLES] += cg.vcycles;
+            const int status = cg.status(rtol);
+            if (status == FEDM_DIVERGED_NAN) {
                 // a NaN on the way (or an operator that is not positive definite): the term goes back to 0, so that the
                 // tables written below are finite and the next update starts from a clean vector, not from the NaN
                 rc = FEDM_DIVERGED_NAN;
                 FEDM_HIP_CHECK(hipMemsetAsync(ph.y + (size_t)m * c.nvp, 0, sizeof(double) * c.nvp, c.stream));
-            } else if (cg.rnorm > rtol * cg.bnorm) {
+            } else if (status == FEDM_DIVERGED_LINEAR) {
                 ++ph.stats[PH_EXHAUSTED];
                 if (rc == 0) rc = FEDM_DIVERGED_LINEAR;
             }

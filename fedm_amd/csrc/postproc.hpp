@@ -2,16 +2,17 @@
 // diagnostics (diag.hip), field output (fields.hip, gd_fields.hip), the LMEA balance (gd_balance.hip) and the electrode
 // currents (currents.hip) -- and nobody else includes.  Their pattern: a first pass writes slot-major partials in a fixed
 // order, one workgroup finishes them, one read-back, and every bad argument is refused with a message.  Host side: the
-// refusal, device arrays, the scalar CG's scratch, the read-back, the two families' dispatch and the weighting
-// potential's set-up.  Device side: the reductions' cores, one copy each, so that a change of the order or of the tie
-// rule reaches every pass that promises bitwise reproducibility with it.
+// refusal, device arrays, the vertices' cell lists, the upload of a scalar solve's hierarchy (the solver itself is
+// scalar_cg.hpp's), the read-back, the two families' dispatch and the weighting potential's set-up.  Device side: the
+// reductions' cores, one copy each, so that a change of the order or of the tie rule reaches every pass that promises
+// bitwise reproducibility with it.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <string>
 #include <type_traits>
 
-#include "photo.hpp"
+#include "solver.hpp"
 #ifdef __HIPCC__
 #include <climits>
 
@@ -36,23 +37,44 @@ int device_array(T *&dst, const T *src, size_t n) {
     return 0;
 }
 
-// the vectors scalar_pcg borrows from a Photo: r, z, p, q, partials, red
-inline void photo_cg_free(Photo &ph) {
-    void *ptrs[] = {ph.r, ph.z, ph.p, ph.q, ph.partials, ph.red};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    ph.r = ph.z = ph.p = ph.q = ph.partials = ph.red = nullptr;
+// vertex -> its (cell, corner) pairs: v_ptr[nv + 1], and v_idx[3 nc] = cell * 3 + corner, ascending within a vertex --
+// the order of every sum over a vertex's cells
+inline void vertex_cell_lists(int nv, const std::vector<int> &cells, std::vector<int> &v_ptr, std::vector<int> &v_idx) {
+    v_ptr.assign((size_t)nv + 1, 0);
+    v_idx.resize(cells.size());
+    for (size_t k = 0; k < cells.size(); ++k) ++v_ptr[cells[k] + 1];
+    for (int v = 0; v < nv; ++v) v_ptr[v + 1] += v_ptr[v];
+    std::vector<int> fill(v_ptr.begin(), v_ptr.end() - 1);
+    for (size_t k = 0; k < cells.size(); ++k) v_idx[fill[cells[k]]++] = (int)k;
 }
-// all six, zero-filled, or none (-1): nothing half-made stays behind
-inline int photo_cg_alloc(Photo &ph, size_t nvp) {
-    if (device_array<double>(ph.r, nullptr, nvp) || device_array<double>(ph.z, nullptr, nvp) ||
-        device_array<double>(ph.p, nullptr, nvp) || device_array<double>(ph.q, nullptr, nvp) ||
-        device_array<double>(ph.partials, nullptr, (size_t)2 * PHOTO_RED_BLOCKS) ||
-        device_array<double>(ph.red, nullptr, 4)) {
-        photo_cg_free(ph);
-        return -1;
+
+// What scalar_pcg solves with, from one fedm_photo_hierarchy of c.nv vertices: the finest operator in double precision
+// into A and, with more than one level, its V-cycles (plain sweeps on every level: composite operators from level
+// n_levels + 1 on, i.e. nowhere) into M, which stays null for Jacobi.  `what` goes before the reason of a refusal
+// ("term 2: " or nothing).  On an error (-1, -2) the caller releases what has been made, with release_hierarchy.
+inline int upload_hierarchy(Ctx &c, const char *who, const std::string &what, const fedm_photo_hierarchy &t, EllMat &A,
+                            Amg *&M) {
+    if (t.n_levels < 1 || !t.A || (t.n_levels > 1 && (!t.P || !t.R || !t.coarse_inverse || t.nu < 1)))
+        return refuse(who, what + "bad hierarchy (levels with their prolongators, restrictions and a dense coarsest inverse; "
+                                  "V(nu,nu) with nu >= 1)");
+    const fedm_csr &A0 = t.A[0];
+    if (A0.n_rows != c.nv || A0.n_cols != c.nv || !A0.indptr || !A0.indices || !A0.values)
+        return refuse(who, what + "the operator has " + std::to_string(A0.n_rows) + " rows, the mesh " +
+                               std::to_string(c.nv) + " vertices");
+    A.single = false;
+    if (const int rc = A.from_csr(A0, true)) {
+        set_error(std::string(who) + ": " + what + "operator upload failed (bad CSR or out of memory)");
+        return rc < -1 ? -2 : -1;
     }
-    return 0;
+    if (A.n_rows_p != c.nvp) return refuse(who, what + "the operator's padded rows differ from the context's");
+    if (t.n_levels == 1) return 0;
+    return build_amg(c, c.nv, t.n_levels, t.A, t.P, t.R, t.coarse_inverse, t.nu, t.omega, &M, t.n_levels + 1);
+}
+inline void release_hierarchy(EllMat &A, Amg *&M) {
+    A.release();
+    if (M) M->release();
+    delete M;
+    M = nullptr;
 }
 
 // the one read-back of a call: what the finish left, once the stream has run dry, and any launch's error
@@ -140,8 +162,7 @@ int weighting_setup(Ctx &c, const char *who, int max_groups, bool groups_need_po
 #ifdef __HIPCC__
 // ---- device: the reductions ----------------------------------------------------------------------
 // Workgroups of a reduction's first pass at the most (beyond: a stride loop), and their threads.  The finish is one
-// workgroup with one thread per first-pass workgroup, so the two must be equal.  (photo.hpp's PHOTO_RED_BLOCKS stays:
-// photo_abi.cpp and the host side above size the scalar CG's partials with it, where no device code is seen.)
+// workgroup with one thread per first-pass workgroup, so the two must be equal.
 constexpr int POST_BLOCKS = 256;
 constexpr int POST_THREADS = 256;
 static_assert(POST_BLOCKS == POST_THREADS, "the finish kernels bring one first-pass workgroup's partials per thread");

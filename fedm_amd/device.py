@@ -1168,11 +1168,7 @@ class DeviceProblem:
         ``max_it`` or meets a NaN raises ``RuntimeError`` and leaves the installed potentials as they were."""
         from . import amg
         rhs = np.ascontiguousarray(rhs, dtype=np.float64)
-        n, Ac, Pc, Rc, coarse, held = amg._pack(levels, dense_coarse=len(levels) > 1)
-        h = _lib.PhotoHierarchy()
-        h.n_levels, h.nu, h.omega = n, int(nu), float(omega)
-        h.A, h.P, h.R = Ac, Pc, Rc
-        h.coarse_inverse = coarse.ctypes.data_as(C.POINTER(C.c_double)) if coarse is not None else None
+        h, held = amg.pack_hierarchy(levels, nu, omega)
         its = (C.c_int * _lib.CURRENTS_MAX)()
         rc = self.lib.fedm_currents_solve(self._h, C.byref(h), _dp(rhs), float(rtol), int(max_it), its)
         self.last_currents_iterations = [int(v) for v in its[:getattr(self, "_currents_n", 0)]]

@@ -130,11 +130,8 @@ def install(lib, handle, photo: Photoionization, coords, cells, facet_tags, axis
         levels = [(A, None)]
         if photo.multigrid:
             levels = amg.build_hierarchy(A, theta=photo.theta, max_coarse=photo.max_coarse, fixed=fixed, coords=coords)
-        n, Ac, Pc, Rc, coarse, held = amg._pack(levels, dense_coarse=len(levels) > 1)
-        keep.append((Ac, Pc, Rc, coarse, held))
-        terms[m].n_levels, terms[m].nu, terms[m].omega = n, int(photo.nu), float(photo.omega)
-        terms[m].A, terms[m].P, terms[m].R = Ac, Pc, Rc
-        terms[m].coarse_inverse = coarse.ctypes.data_as(C.POINTER(C.c_double)) if coarse is not None else None
+        terms[m], held = amg.pack_hierarchy(levels, photo.nu, photo.omega)
+        keep.append(held)
         sizes.append([a.shape[0] for a, _ in levels])
     desc = photo.to_c()
     rc = lib.fedm_photo_setup(handle, C.byref(desc), terms)

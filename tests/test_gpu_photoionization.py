@@ -332,6 +332,42 @@ def test_reproducible_and_idempotent(cases, key, multigrid):
     assert (st["vcycles"] > 0) == multigrid
 
 
+def test_other_scalar_solves_leave_the_photoionisation_alone(cases):
+    """A consistent field projection and a solve of the weighting potentials run the same conjugate gradients as the
+    Helmholtz terms, each with a workspace of its own: neither moves a counter, a solution or the source the assembly
+    sees.  A has the two calls between its updates, B does not.  The residual is taken under the global colouring, the
+    assembly that is bitwise reproducible (test_assembly_uses_the_table)."""
+    case = cases(("tensor", "closed", True))
+    a, b = case.problem(), case.problem()
+    assert all(len(levels) >= 2 for levels in a.photo_levels)
+    its_first = a.photo_update()
+    assert b.photo_update() == its_first and all(i > 0 for i in its_first)
+    a.set_assembly("colour")
+    assert a.assembly_variant() == "global colouring"
+
+    def seen(p):
+        y, g = p.get_photo()
+        F, fnorm = p.residual()
+        return y.tobytes(), g.tobytes(), F.tobytes(), fnorm
+    stats, before = a.photo_stats(), seen(a)
+    assert stats["vcycles"] > 0
+
+    a.fields_setup(consistent=True)
+    fv = a.fields(["E_r"], projection="consistent")
+    assert fv.finite and fv.cg_iterations[0] > 0
+    its_psi = a.currents_setup(boundary_tags=[1, 2], max_coarse=40)
+    assert len(a.currents_levels) >= 2 and len(its_psi) == 2 and all(i > 0 for i in its_psi)
+
+    assert a.photo_stats() == stats                      # (a) entry for entry: the V-cycles of the currents' solve are not here
+    assert seen(a) == before                             # (b), (c)
+    its_a, its_b = a.photo_update(), b.photo_update()    # (d)
+    assert its_a == its_b
+    (ya, ga), (yb, gb) = a.get_photo(), b.get_photo()
+    assert ya.tobytes() == yb.tobytes() and ga.tobytes() == gb.tobytes()
+    assert a.photo_stats() == b.photo_stats()
+    a.set_assembly("patch")
+
+
 # The step runs on every case and the state is held to the oracle's on every case.  The Newton COUNT is compared wherever
 # it is well defined, which the test decides from the oracle's residual history alone: no residual within 20 % of the
 # tolerance.  That leaves out one case of the eight, ("delaunay", "tabulated", plane), whose residuals after iterations 3

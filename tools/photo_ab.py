@@ -14,7 +14,7 @@ assembly kernel it takes and ``fedm_time_kernel`` kind 0 of it.
     python tools/photo_ab.py --spacing 2e-5 --repeats 3   # a quick look
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/photo_ab.py --updates-only 40
         # the update's kernels by name (photo_cell_load_kernel, photo_vertex_sum_kernel: the load vector; ell_spmv_kernel,
-        # photo_dots_kernel, photo_cg_update_kernel, ...: the solves; photo_table_kernel: the table write)
+        # scalar_cg_dots_kernel, scalar_cg_update_kernel, ...: the solves; photo_table_kernel: the table write)
 
 Writes profiles/photoionization.json stamped with ``git describe --always --dirty`` (``--commit`` where the tree that
 runs has no history).
